@@ -503,6 +503,34 @@ def cpu_baseline(frames, levels, fp_channels, pointcnn_img_c=None):
     return res
 
 
+DUMP_BYTES = 64 << 20   # --dump-outputs: all arrays together
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: `arrays` (name -> tensor) as DIR/<name>.npy in float32, DUMP_BYTES at most in all.  An array larger
+    than its even share is replaced by the elements at a fixed set of flat indices (seed 0, sorted), so that two runs or
+    two builds with the same arguments can be compared element for element."""
+    os.makedirs(directory, exist_ok=True)
+    share = (DUMP_BYTES - 1024 * len(arrays)) // len(arrays) // 4      # elements per array (npy headers are < 1 KB)
+    for name, t in arrays.items():
+        a = t.detach().float()
+        if a.numel() > share:
+            pick = np.sort(np.random.default_rng(0).choice(a.numel(), share, replace=False))
+            a = a.reshape(-1)[torch.from_numpy(pick).to(a.device)]
+        np.save(os.path.join(directory, name + ".npy"), a.cpu().numpy().astype(np.float32))
+
+
+def step_outputs(loss, model, inputs=None):
+    """what one train step gives its caller: the loss, and the parameters and gradients it leaves behind"""
+    params = list(model.parameters())
+    out = {"loss": loss,
+           "parameters": torch.cat([p.detach().reshape(-1) for p in params]),
+           "gradients": torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1) for p in params])}
+    if inputs is not None and "img_fts" in inputs and inputs["img_fts"].grad is not None:
+        out["img_fts_grad"] = inputs["img_fts"].grad
+    return out
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -557,6 +585,11 @@ def parse_args(argv=None):
     ap.add_argument("--rehearse-on-one-gpu", action="store_true",
                     help="N > 1 ranks that all use GPU 0 with gloo collectives: the whole multi-rank code path of this script on a "
                          "one-GPU box (RCCL needs one GPU per rank); the figure it prints is not a scaling measurement")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32): loss, parameters "
+                         "and gradients (flattened in model.parameters() order) and, with an image feature map, its gradient; an "
+                         "array over its share of %d MB is a fixed, seeded sample of its elements (the same indices every run)"
+                         % (DUMP_BYTES >> 20))
     ap.add_argument("--stub", action="store_true",
                     help="CPU test hook: the ranks join a gloo group and time a stand-in step (no HIP); exercises the "
                          "launcher / barrier / max-over-ranks / one-JSON-line plumbing without a GPU")
@@ -601,9 +634,12 @@ def stub_main(args):
     dp.fence(ctx)
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        net(x).sum().backward()
+        loss = net(x).sum()
+        loss.backward()
     dp.fence(ctx)
     dt = dp.max_over_ranks(time.perf_counter() - t0, ctx)
+    if args.dump_outputs and ctx.rank == 0:
+        dump_outputs(args.dump_outputs, step_outputs(loss, w))
     if ctx.rank == 0:
         print(json.dumps({"metric": "stub frames/sec (CPU plumbing test)", "value": round(ctx.world * per_rank * args.steps / dt, 3),
                           "unit": "frames/s", "n_gpus": ctx.world, "ranks": ctx.world, "steps": args.steps, "warmup": args.warmup,
@@ -669,7 +705,7 @@ def main():
     scaling = args.scaling if args.scaling != "auto" else "strong"   # BASELINE config 4: a GLOBAL batch of 8 frames over the ranks
     headline_per_gpu = args.frames_per_gpu or (B if scaling == "weak" else max(1, B // world))
 
-    def measure(per_gpu):
+    def measure(per_gpu, dump_dir=None):
         """K timed steps at `per_gpu` frames per rank under the contract of the file header -> the figures the JSON line needs"""
         import types
         torch.manual_seed(1234)  # same initial weights on every rank (the reference broadcasts from rank 0)
@@ -801,6 +837,8 @@ def main():
             # (the last step's path drop may have switched the image branch off -- one step in ten at 0.9 / 0.9 -- so an all-zero
             # gradient is legitimate here; tests/test_graph_step.py checks that the gradient lands on the projected pixels)
             assert g is not None and torch.isfinite(g).all().item(), "the gradient of the image feature map is missing or not finite"
+        if dump_dir and rank == 0:
+            dump_outputs(dump_dir, step_outputs(loss, model, inputs))
 
         out = types.SimpleNamespace(per_gpu=per_gpu, use_graph=use_graph, dt=dt, t_enqueued=t_enqueued, align=align, workload=workload,
                                     levels=levels, fp_channels=fp_channels, multiclass=multiclass, img_c=img_c, in_step_us=timer.mean_us(),
@@ -811,7 +849,7 @@ def main():
         torch.cuda.empty_cache()
         return out
 
-    M = measure(headline_per_gpu)
+    M = measure(headline_per_gpu, args.dump_outputs)
     per_gpu, use_graph, dt, t_enqueued, multiclass, img_c = M.per_gpu, M.use_graph, M.dt, M.t_enqueued, M.multiclass, M.img_c
     weak = None
     if world > 1 and args.scaling == "auto" and not args.frames_per_gpu and headline_per_gpu != B:

@@ -1,6 +1,7 @@
 """Generate the committed golden vectors in tests/golden/*.npz.
 
 Run from the repo root:  python tests/golden/make_golden.py
+(or with one of three_nn_origin, ref_cpu, ref_gpu [OUT_DIR] to write that fixture alone)
 
 Every fixture holds seeded inputs and the outputs of the CPU oracle (oracle/hf_oracle.c) for
 them.  Before anything is written, the oracle is cross-checked here against the reference's own
@@ -22,8 +23,8 @@ import oracle  # noqa: E402
 OUT = os.path.dirname(os.path.abspath(__file__))
 
 
-def save(name, **arrays):
-    path = os.path.join(OUT, name + ".npz")
+def save(name, out_dir=None, **arrays):
+    path = os.path.join(out_dir or OUT, name + ".npz")
     np.savez_compressed(path, **arrays)
     print("%-28s %7.1f KB" % (name + ".npz", os.path.getsize(path) / 1024))
 
@@ -121,9 +122,54 @@ def three_nn_origin():
     save("three_nn_origin", **arrays)
 
 
+def _test_module(name):
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import importlib
+    return importlib.import_module(name)
+
+
+def _flat(prefix, outputs):
+    return {prefix + "/" + k: v for k, v in outputs.items()}
+
+
+def ref_cpu():
+    """ref_cpu.npz: OUTPUTS OF THE REFERENCE's own CPU programs (oracle/_ref/libhfref_{qbp,itp}.so) on the seeded inputs of
+    the tests that compare against them (tests/test_oracle.py, and the lattice test of tests/test_ops_gpu.py), so that those
+    tests run where the reference builds are absent too.  Inputs are regenerated by the tests from their seeds."""
+    assert oracle.ref_available("qbp") and oracle.ref_available("itp"), \
+        "needs oracle/_ref/libhfref_{qbp,itp}.so (make -C oracle, with the reference checkout present)"
+    t = _test_module("test_oracle")
+    arrays = {}
+    arrays.update(_flat("grouping", t.ref_grouping_run(oracle)))
+    arrays.update(_flat("interpolate", t.ref_interpolate_run(oracle)))
+    arrays.update(_flat("threenn_origin_n2", t.ref_threenn_origin_run(oracle)))
+    arrays.update(_flat("lattice", t.ref_lattice_run(oracle)))
+    g = _test_module("test_ops_gpu")
+    arrays.update(_flat("gpu_lattice", g.ref_gpu_lattice_run(oracle)))
+    save("ref_cpu", **arrays)
+
+
+def ref_gpu(out_dir=None):
+    """ref_gpu_kernels.npz: OUTPUTS OF THE REFERENCE's CUDA kernels compiled unmodified by hipcc (oracle/_ref/libhfref_gpu.so)
+    on the seeded inputs of tests/test_ops_gpu.py::test_reference_kernels_*.  Needs a GPU and oracle/_ref."""
+    g = _test_module("test_ops_gpu")
+    R = g._ref_gpu_lib()
+    assert R is not None, "needs oracle/_ref/libhfref_gpu.so"
+    arrays = {}
+    arrays.update(_flat("grouping_sampling", g.ref_grouping_sampling_run(R)))
+    a, b = g.ref_bev_iou_inputs(oracle)
+    arrays.update(_flat("bev_iou", g.ref_bev_iou_run(R, a, b)))
+    arrays.update(_flat("crop", g.ref_crop_run(R, g.ref_crop_inputs())))
+    save("ref_gpu_kernels", out_dir=out_dir, **arrays)
+
+
 def main():
     if sys.argv[1:] == ["three_nn_origin"]:                  # one fixture on its own (the others stay byte-identical)
         return three_nn_origin()
+    if sys.argv[1:] == ["ref_cpu"]:
+        return ref_cpu()
+    if sys.argv[1:2] == ["ref_gpu"]:                         # ref_gpu [OUT_DIR]: on a GPU machine
+        return ref_gpu(*sys.argv[2:3])
     have_ref = all(oracle.ref_available(k) for k in ("qbp", "sel", "itp"))
     print("reference CPU builds available:", have_ref)
 

@@ -7,6 +7,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -35,3 +36,32 @@ def test_self_launch_two_ranks(scaling, per_rank):
 def test_single_rank_needs_no_launcher():
     r = _run()
     assert r["n_gpus"] == 1 and r["config"]["frames_per_gpu"] == 8
+
+
+def test_dump_outputs_are_float32_and_repeatable(tmp_path):
+    """--dump-outputs DIR: the last timed step's loss / parameters / gradients as .npy, identical from run to run"""
+    runs = []
+    for k in range(2):
+        d = tmp_path / ("run%d" % k)
+        r = _run("--dump-outputs", str(d))
+        assert r["steps"] == 3 and r["ms_per_step"] > 0
+        runs.append({f: np.load(d / f) for f in sorted(os.listdir(d))})
+    assert set(runs[0]) == {"loss.npy", "parameters.npy", "gradients.npy"}
+    for name, a in runs[0].items():
+        assert a.dtype == np.float32 and np.isfinite(a).all(), name
+        assert np.array_equal(a, runs[1][name]), name
+
+
+def test_dump_outputs_samples_large_arrays_within_the_budget(tmp_path):
+    sys.path.insert(0, ROOT)
+    import torch
+    import bench
+    big = {"a": torch.arange(30 << 20, dtype=torch.float32), "b": torch.ones(5, 7, dtype=torch.float64)}
+    for k in range(2):
+        bench.dump_outputs(str(tmp_path / str(k)), big)
+    total = sum(os.path.getsize(tmp_path / "0" / f) for f in os.listdir(tmp_path / "0"))
+    assert total <= bench.DUMP_BYTES
+    a0, a1 = np.load(tmp_path / "0" / "a.npy"), np.load(tmp_path / "1" / "a.npy")
+    assert a0.dtype == np.float32 and np.array_equal(a0, a1) and (np.diff(a0) >= 0).all()   # the same sorted sample each time
+    assert a0.size < (30 << 20)
+    assert np.array_equal(np.load(tmp_path / "0" / "b.npy"), np.ones((5, 7), np.float32))

@@ -1,13 +1,16 @@
-"""host-side data formats: synthetic round trips everywhere, and -- only where the reference
-checkout is present (this container, never the GPU box) -- its own 13 KITTI test frames read in place."""
+"""host-side data formats: synthetic round trips, and four of the reference's KITTI test frames
+(tests/golden/kitti: calib, labels, and the velodyne scans xz-compressed) read by the same readers."""
+import lzma
 import os
+import shutil
 
 import numpy as np
 import pytest
 
 from heterofusionrcnn_amd import kitti_io
 
-REF = "/root/reference/hf/tests/datasets/Kitti/object/training"
+KITTI = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "kitti")
+KITTI_FRAMES = ["000000", "000001", "000002", "000003"]
 
 
 def _write_calib(path, p2, r0, tr):
@@ -85,10 +88,17 @@ def test_handoff_and_result_files_round_trip(tmp_path):
     assert kitti_io.read_labels(tmp_path / "missing.txt")[1].shape == (0, 7)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference KITTI test frames not present on this machine")
-def test_reference_kitti_frames_read_in_place():
+def test_reference_kitti_frames_read_in_place(tmp_path):
+    # the frames as a KITTI training directory: calib / label_2 as committed, velodyne/*.bin unpacked
+    REF = str(tmp_path)
+    for sub in ("calib", "label_2"):
+        shutil.copytree(os.path.join(KITTI, sub), os.path.join(REF, sub))
+    os.mkdir(os.path.join(REF, "velodyne"))
+    for name in KITTI_FRAMES:
+        with lzma.open(os.path.join(KITTI, "velodyne", name + ".bin.xz")) as src, open(os.path.join(REF, "velodyne", name + ".bin"), "wb") as dst:
+            shutil.copyfileobj(src, dst)
     names = sorted(f[:-4] for f in os.listdir(os.path.join(REF, "velodyne")) if f.endswith(".bin"))
-    assert len(names) >= 10
+    assert names == KITTI_FRAMES
     for name in names[:4]:
         calib = kitti_io.read_calib(os.path.join(REF, "calib", name + ".txt"))
         assert calib["p2"][2, 2] == 1.0 and abs(np.linalg.det(calib["r0_rect"]) - 1) < 1e-3

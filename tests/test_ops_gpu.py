@@ -335,20 +335,35 @@ def test_three_nn_against_reference_cpu_outputs_at_the_origin(hf):
                 assert np.array_equal(host(dist)[:, row].view(np.uint32), g[name + "_dist"][:, 0].view(np.uint32)), (name, fn.__name__)
 
 
-def test_three_nn_translated_lattice_against_reference_cpu(hf, oracle_mod):
-    """where u - x is exact (dyadic lattice) the reference expression on (u, known) has the bits of threenn_cpu on the cloud
-    translated by -u: the HIP kernels against reference-compiled code with a NON-zero query (tests/test_oracle.py has the
-    oracle's twin).  Needs oracle/_ref (travels with the snapshot)."""
-    from heterofusionrcnn_amd.interpolate import three_nn_all_pairs
-    if not oracle_mod.ref_available("itp"):
-        pytest.skip("oracle/_ref/libhfref_itp.so not built")
+def ref_gpu_lattice_inputs():
     rng = np.random.default_rng(23)
     known = (rng.integers(-2048, 2048, (700, 3)) / 64.0).astype(np.float32)
     unknown = (rng.integers(-2048, 2048, (512, 3)) / 64.0).astype(np.float32)
+    return known, unknown
+
+
+def ref_gpu_lattice_run(oracle_mod):
+    known, unknown = ref_gpu_lattice_inputs()
     rd, ri = oracle_mod.ref_threenn_origin((unknown[:, None, :] - known[None, :, :]).astype(np.float32))
+    return {"dist": rd, "idx": ri}
+
+
+def test_three_nn_translated_lattice_against_reference_cpu(hf, oracle_mod):
+    """where u - x is exact (dyadic lattice) the reference expression on (u, known) has the bits of threenn_cpu on the cloud
+    translated by -u: the HIP kernels against reference-compiled code with a NON-zero query (tests/test_oracle.py has the
+    oracle's twin).  threenn_cpu's outputs are committed (tests/golden/ref_cpu.npz); oracle/_ref is run too where built."""
+    from heterofusionrcnn_amd.interpolate import three_nn_all_pairs
+    known, unknown = ref_gpu_lattice_inputs()
+    g = load_golden("ref_cpu")
+    sources = [("golden", {"dist": g["gpu_lattice/dist"], "idx": g["gpu_lattice/idx"]})]
+    if oracle_mod.ref_available("itp"):
+        sources.append(("live", ref_gpu_lattice_run(oracle_mod)))
     for fn in (hf.three_nn, three_nn_all_pairs):
         dist, idx = fn(dev(unknown[None]), dev(known[None]))
-        assert np.array_equal(host(idx)[0], ri[:, 0]) and np.array_equal(host(dist)[0].view(np.uint32), rd[:, 0].view(np.uint32))
+        for source, ref in sources:
+            rd, ri = ref["dist"], ref["idx"]
+            assert np.array_equal(host(idx)[0], ri[:, 0]) and np.array_equal(host(dist)[0].view(np.uint32), rd[:, 0].view(np.uint32)), \
+                (source, fn.__name__)
 
 
 @pytest.mark.parametrize("kind", ["lattice", "same_x", "clustered", "two_known", "nonfinite", "max_lds", "beyond_lds"])
@@ -699,54 +714,120 @@ def test_full_size_nms_properties(hf):
 
 
 # ------------------------------------------------------------------ reference CUDA kernels compiled by hipcc
-def _ref_gpu():
+# Each test compares the HIP path with the reference kernels' outputs on seeded inputs, taken from the committed fixture
+# tests/golden/ref_gpu_kernels.npz (made by tests/golden/make_golden.py ref_gpu on a GPU with oracle/_ref built) and,
+# where oracle/_ref/libhfref_gpu.so is present, from the live kernels as well.
+REF_GPU_GOLDEN = "ref_gpu_kernels"
+
+
+def _ref_gpu_lib():
     path = os.path.join(ROOT, "oracle", "_ref", "libhfref_gpu.so")
-    if not os.path.exists(path):
-        pytest.skip("oracle/_ref/libhfref_gpu.so not in this snapshot")
-    return ctypes.CDLL(path)
+    return ctypes.CDLL(path) if os.path.exists(path) else None
+
+
+def _ref_sources(name, run, *args):
+    """[(source, {output name: numpy array})]: the committed fixture, then the live reference kernels if they were built"""
+    g = load_golden(REF_GPU_GOLDEN)
+    out = [("golden", {k[len(name) + 1:]: g[k] for k in g if k.startswith(name + "/")})]
+    assert out[0][1], "tests/golden/%s.npz has no %s outputs" % (REF_GPU_GOLDEN, name)
+    R = _ref_gpu_lib()
+    if R is not None:
+        out.append(("live", run(R, *args)))
+    return out
 
 
 def _p(t):
     return ctypes.c_void_p(t.data_ptr())
 
 
-def test_reference_kernels_grouping_sampling(hf):
-    R = _ref_gpu()
+def _sha256(a):
+    import hashlib
+    return np.frombuffer(hashlib.sha256(np.ascontiguousarray(a).tobytes()).digest(), np.uint8)
+
+
+REF_RADII = (0.5, 1.5, 4.0)
+# the reference gradient is kept as its difference from the float64 scatter sum of the same terms (a few rounding errors of
+# the kernel's fp32 atomics), in int16 multiples of 2^-24: the value rebuilt from it lies within 2^-25 of the kernel's, so a
+# bound of 2e-4 - 2^-25 against it is a bound of 2e-4 against the kernel
+REF_GRAD_UNIT = 2.0 ** -24
+REF_GRAD_ATOL = 2e-4
+
+
+def _scatter_sum64(idx, go, n):
+    b, _, _, c = go.shape
+    out = np.zeros((b, n, c), np.float64)
+    for i in range(b):
+        np.add.at(out[i], idx[i].reshape(-1), go[i].reshape(-1, c).astype(np.float64))
+    return out
+
+
+def _grad_residual(grad, idx, go):
+    r = np.rint((grad.astype(np.float64) - _scatter_sum64(idx, go, grad.shape[1])) / REF_GRAD_UNIT)
+    assert np.abs(r).max() < 2 ** 15, "gradient residual out of the int16 range"
+    return r.astype(np.int16)
+
+
+def ref_grouping_sampling_inputs():
     rng = np.random.default_rng(21)
     b, n, m, ns, c = 4, 4096, 1024, 32, 16
     xyz = kitti_uniform(rng, b, n)
     xyz[:, n - 400:] = xyz[:, :400]
+    feats = rng.standard_normal((b, n, c)).astype(np.float32)
+    go = rng.standard_normal((b, m, ns, c)).astype(np.float32)
+    return (b, n, m, ns, c), xyz, feats, go
+
+
+def ref_grouping_sampling_run(R):
+    """the reference chain FPS -> gather -> ball query (three radii) -> group / group grad (the last radius' rows)"""
+    (b, n, m, ns, c), xyz, feats, go = ref_grouping_sampling_inputs()
+    x = dev(xyz)
+    temp = torch.empty((32, n), dtype=torch.float32, device="cuda")
+    fps = torch.zeros((b, m), dtype=torch.int32, device="cuda")
+    assert R.hfref_farthest_point_sample(b, n, m, _p(x), _p(temp), _p(fps)) == 0
+    q = torch.empty((b, m, 3), dtype=torch.float32, device="cuda")
+    assert R.hfref_gather_point(b, n, m, _p(x), _p(fps), _p(q)) == 0
+    out = {"fps": fps, "new_xyz": q}
+    for r in REF_RADII:
+        idx = torch.zeros((b, m, ns), dtype=torch.int32, device="cuda")
+        cnt = torch.zeros((b, m), dtype=torch.int32, device="cuda")
+        assert R.hfref_query_ball_point(b, n, m, ctypes.c_float(r), ns, _p(x), _p(q), _p(idx), _p(cnt)) == 0
+        out["idx_%g_sha256" % r], out["cnt_%g" % r] = idx, cnt
+    f, g = dev(feats), dev(go)
+    grouped = torch.empty((b, m, ns, c), dtype=torch.float32, device="cuda")
+    assert R.hfref_group_point(b, n, c, m, ns, _p(f), _p(idx), _p(grouped)) == 0
+    gp = torch.zeros((b, n, c), dtype=torch.float32, device="cuda")
+    assert R.hfref_group_point_grad(b, n, c, m, ns, _p(g), _p(idx), _p(gp)) == 0
+    out = {k: _sha256(host(v)) if k.endswith("_sha256") else host(v) for k, v in out.items()}
+    out["grouped_sha256"] = _sha256(host(grouped))          # 8 MB of copies: kept as a digest (the check is bit equality)
+    out["grad_points_residual"] = _grad_residual(host(gp), host(idx), go)
+    return out
+
+
+def test_reference_kernels_grouping_sampling(hf):
+    (b, n, m, ns, c), xyz, feats, go = ref_grouping_sampling_inputs()
     x = dev(xyz)
     # FPS: the real 512-thread tree reduction with its tie behaviour
-    temp = torch.empty((32, n), dtype=torch.float32, device="cuda")
-    ref_fps = torch.zeros((b, m), dtype=torch.int32, device="cuda")
-    assert R.hfref_farthest_point_sample(b, n, m, _p(x), _p(temp), _p(ref_fps)) == 0
     fps = hf.farthest_point_sample(m, x)
-    assert torch.equal(fps, ref_fps)
-    ref_q = torch.empty((b, m, 3), dtype=torch.float32, device="cuda")
-    assert R.hfref_gather_point(b, n, m, _p(x), _p(fps), _p(ref_q)) == 0
     q = hf.gather_point(x, fps)
-    assert torch.equal(q, ref_q)
-    for r in (0.5, 1.5, 4.0):
-        ref_idx = torch.zeros((b, m, ns), dtype=torch.int32, device="cuda")
-        ref_cnt = torch.zeros((b, m), dtype=torch.int32, device="cuda")
-        assert R.hfref_query_ball_point(b, n, m, ctypes.c_float(r), ns, _p(x), _p(q), _p(ref_idx), _p(ref_cnt)) == 0
+    mine = {"fps": host(fps), "new_xyz": host(q)}
+    for r in REF_RADII:
         idx, cnt = hf.query_ball_point(r, ns, x, q)
-        assert torch.equal(idx, ref_idx) and torch.equal(cnt, ref_cnt), r
-    feats = dev(rng.standard_normal((b, n, c)).astype(np.float32))
-    ref_g = torch.empty((b, m, ns, c), dtype=torch.float32, device="cuda")
-    assert R.hfref_group_point(b, n, c, m, ns, _p(feats), _p(idx), _p(ref_g)) == 0
-    assert torch.equal(hf.group_point(feats, idx), ref_g)
-    go = dev(rng.standard_normal((b, m, ns, c)).astype(np.float32))
-    ref_gp = torch.zeros((b, n, c), dtype=torch.float32, device="cuda")
-    assert R.hfref_group_point_grad(b, n, c, m, ns, _p(go), _p(idx), _p(ref_gp)) == 0
-    f2 = feats.clone().requires_grad_(True)
-    hf.group_point(f2, idx).backward(go)
-    torch.testing.assert_close(f2.grad, ref_gp, rtol=0, atol=2e-4)   # atomics: order differs, sums of <= ~100 terms
+        mine["idx_%g_sha256" % r], mine["cnt_%g" % r] = _sha256(host(idx)), host(cnt)   # neighbour rows: bit equality
+    f = dev(feats)
+    grouped_sha = _sha256(host(hf.group_point(f, idx)))
+    f2 = f.clone().requires_grad_(True)
+    hf.group_point(f2, idx).backward(dev(go))
+    for source, ref in _ref_sources("grouping_sampling", ref_grouping_sampling_run):
+        for k, v in mine.items():
+            assert np.array_equal(v, ref[k]), (source, k)
+        assert np.array_equal(grouped_sha, ref["grouped_sha256"]), source
+        # atomics: order differs, sums of <= ~100 terms
+        ref_grad = _scatter_sum64(host(idx), go, n) + ref["grad_points_residual"] * REF_GRAD_UNIT
+        err = np.abs(host(f2.grad).astype(np.float64) - ref_grad).max()
+        assert err <= REF_GRAD_ATOL - 0.5 * REF_GRAD_UNIT, (source, err)
 
 
-def test_reference_kernels_bev_iou(hf, oracle_mod):
-    R = _ref_gpu()
+def ref_bev_iou_inputs(oracle_mod):
     # a fixture whose pairwise a x a IoUs (the ones NMS compares) all keep a margin from both thresholds: the keep
     # vector then cannot depend on the last ulps of sinf / cosf / atan2f, and equality is asserted unconditionally
     for seed in range(22, 60):
@@ -757,61 +838,97 @@ def test_reference_kernels_bev_iou(hf, oracle_mod):
             break
     else:
         raise AssertionError("no margin-safe fixture found")
-    b = a[:64].copy()
+    return a, a[:64].copy()
+
+
+REF_NMS_THRESH = (0.7, 0.05)
+
+
+def ref_bev_iou_run(R, a, b):
     ad, bd = dev(a), dev(b)
-    ref_ov = torch.zeros((len(a), len(b)), device="cuda")
-    ref_iou = torch.zeros((len(a), len(b)), device="cuda")
-    assert R.hfref_compute_bev_iou(len(a), _p(ad), len(b), _p(bd), _p(ref_ov), _p(ref_iou)) == 0
-    ov, iou = hf.compute_bev_iou(ad, bd)
-    torch.testing.assert_close(iou, ref_iou, rtol=0, atol=TOL)
-    torch.testing.assert_close(ov, ref_ov, rtol=0, atol=3e-5)
-    assert torch.equal(iou == 0, ref_iou == 0)
-    # NMS: reference mask kernel + the host sweep of bev_iou.cpp:87-112 (restated in the oracle)
+    ov = torch.zeros((len(a), len(b)), device="cuda")
+    iou = torch.zeros((len(a), len(b)), device="cuda")
+    assert R.hfref_compute_bev_iou(len(a), _p(ad), len(b), _p(bd), _p(ov), _p(iou)) == 0
+    out = {"overlap": host(ov), "iou": host(iou)}
     n = len(a)
-    cb = (n + 63) // 64
-    for thresh in (0.7, 0.05):
-        ref_mask = torch.zeros((n, cb), dtype=torch.int64, device="cuda")
-        assert R.hfref_nms_mask(_p(ad), _p(ref_mask), n, ctypes.c_float(thresh)) == 0
-        want, kept = oracle_mod.nms_sweep(host(ref_mask).view(np.uint64))
-        keep, num = hf.oriented_nms(ad, thresh, return_count=True)
-        assert np.array_equal(host(keep), want), "keep differs from the reference kernels"
-        assert int(host(num)[0]) == kept
-        assert torch.equal(hf.nms_mask(ad, thresh), ref_mask)
+    for thresh in REF_NMS_THRESH:
+        mask = torch.zeros((n, (n + 63) // 64), dtype=torch.int64, device="cuda")
+        assert R.hfref_nms_mask(_p(ad), _p(mask), n, ctypes.c_float(thresh)) == 0
+        out["nms_mask_%g" % thresh] = host(mask)
+    return out
 
 
-def test_reference_kernels_crop(hf):
-    """the reference appends in atomic order: compare as sets (and exactly where cnt <= R leaves no choice)"""
-    R = _ref_gpu()
+def test_reference_kernels_bev_iou(hf, oracle_mod):
+    a, b = ref_bev_iou_inputs(oracle_mod)
+    ad, bd = dev(a), dev(b)
+    ov, iou = hf.compute_bev_iou(ad, bd)
+    for source, ref in _ref_sources("bev_iou", ref_bev_iou_run, a, b):
+        ref_ov, ref_iou = dev(ref["overlap"]), dev(ref["iou"])
+        torch.testing.assert_close(iou, ref_iou, rtol=0, atol=TOL, msg=source)
+        torch.testing.assert_close(ov, ref_ov, rtol=0, atol=3e-5, msg=source)
+        assert torch.equal(iou == 0, ref_iou == 0), source
+        # NMS: reference mask kernel + the host sweep of bev_iou.cpp:87-112 (restated in the oracle)
+        for thresh in REF_NMS_THRESH:
+            ref_mask = ref["nms_mask_%g" % thresh]
+            want, kept = oracle_mod.nms_sweep(ref_mask.view(np.uint64))
+            keep, num = hf.oriented_nms(ad, thresh, return_count=True)
+            assert np.array_equal(host(keep), want), "keep differs from the reference kernels (%s)" % source
+            assert int(host(num)[0]) == kept, source
+            assert np.array_equal(host(hf.nms_mask(ad, thresh)), ref_mask), source
+
+
+REF_CROP_SHAPE = (2, 4096, 8, 24, 64)   # batch, points, channels, boxes, resize
+
+
+def ref_crop_inputs():
     import sys
     sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
     from make_golden import box_3d_to_8co, random_boxes3d
     rng = np.random.default_rng(23)
-    bsz, p, c, nb, r = 2, 4096, 8, 24, 64
+    bsz, p, c, nb, r = REF_CROP_SHAPE
     pts = kitti_uniform(rng, bsz, p)
     pts[:, :, 1] = rng.uniform(0, 2, (bsz, p)).astype(np.float32)
     b3 = random_boxes3d(rng, nb)
     b3[:, 1] = 2.2
     b3[:, 3:6] += rng.uniform(0, 12, (nb, 1)).astype(np.float32) * np.array([1, 1, 0.3], np.float32)
-    t = dict(pts=dev(pts), fts=dev(rng.standard_normal((bsz, p, c)).astype(np.float32)),
-             inten=dev(rng.uniform(-.5, .5, (bsz, p, 1)).astype(np.float32)), mask=dev(rng.random((bsz, p)) < 0.2),
-             boxes=dev(box_3d_to_8co(b3)), box_ind=dev(rng.integers(0, bsz, nb).astype(np.int32)))
-    mine = hf.pc_crop_and_sample(t["pts"], t["fts"], t["inten"], t["mask"], t["boxes"], t["box_ind"], r)
-    ref = [torch.zeros_like(x) for x in mine]
-    ref[5].fill_(True)
+    return dict(pts=pts, fts=rng.standard_normal((bsz, p, c)).astype(np.float32),
+                inten=rng.uniform(-.5, .5, (bsz, p, 1)).astype(np.float32), mask=rng.random((bsz, p)) < 0.2,
+                boxes=box_3d_to_8co(b3), box_ind=rng.integers(0, bsz, nb).astype(np.int32))
+
+
+def ref_crop_run(R, inputs):
+    bsz, p, c, nb, r = REF_CROP_SHAPE
+    t = {k: dev(v) for k, v in inputs.items()}
+    f32 = dict(dtype=torch.float32, device="cuda")
+    ref = [torch.zeros((nb, r, 3), **f32), torch.zeros((nb, r, c), **f32), torch.zeros((nb, r, 1), **f32),
+           torch.zeros((nb, r), dtype=torch.bool, device="cuda"), torch.zeros((nb, r), dtype=torch.int32, device="cuda"),
+           torch.ones((nb,), dtype=torch.bool, device="cuda")]
     assert R.hfref_pc_crop_and_sample(_p(t["pts"]), _p(t["fts"]), _p(t["inten"]), _p(t["mask"]), _p(t["boxes"]),
                                       _p(t["box_ind"]), nb, bsz, p, r, c, 1, *[_p(x) for x in ref]) == 0
-    assert torch.equal(mine[5], ref[5])
-    mi, ri = host(mine[4]), host(ref[4])
-    checked = 0
-    for bx in range(nb):
-        if not host(mine[5])[bx]:
-            continue
-        row = mi[bx]
-        cnt = next((s for s in range(1, r) if row[s] <= row[s - 1]), r)
-        if cnt < r:  # all inside points taken: same set, ours ascending; pad slots are copies of taken ones
-            assert sorted(set(ri[bx].tolist())) == row[:cnt].tolist()
-            checked += 1
-    assert checked >= 3
+    return {"crop_ind": host(ref[4]), "non_empty": host(ref[5])}
+
+
+def test_reference_kernels_crop(hf):
+    """the reference appends in atomic order: compare as sets (and exactly where cnt <= R leaves no choice)"""
+    inputs = ref_crop_inputs()
+    t = {k: dev(v) for k, v in inputs.items()}
+    nb, r = REF_CROP_SHAPE[3:]
+    mine = hf.pc_crop_and_sample(t["pts"], t["fts"], t["inten"], t["mask"], t["boxes"], t["box_ind"], r)
+    assert tuple(mine[4].shape) == (nb, r) and tuple(mine[5].shape) == (nb,)
+    mi, mne = host(mine[4]), host(mine[5])
+    for source, ref in _ref_sources("crop", ref_crop_run, inputs):
+        assert np.array_equal(mne, ref["non_empty"]), source
+        ri = ref["crop_ind"]
+        checked = 0
+        for bx in range(nb):
+            if not mne[bx]:
+                continue
+            row = mi[bx]
+            cnt = next((s for s in range(1, r) if row[s] <= row[s - 1]), r)
+            if cnt < r:  # all inside points taken: same set, ours ascending; pad slots are copies of taken ones
+                assert sorted(set(ri[bx].tolist())) == row[:cnt].tolist(), source
+                checked += 1
+        assert checked >= 3, source
 
 
 # ------------------------------------------------------------------ streams / re-entrancy

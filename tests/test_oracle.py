@@ -1,6 +1,6 @@
 """CPU tests (-m "not gpu"): the oracle against the committed golden vectors, the reference's
-own CPU programs (oracle/_ref, present only where /root/reference was available at build time)
-and the known answers recoverable from the reference demos."""
+own CPU programs (their committed outputs, and oracle/_ref live where it was built) and the known
+answers recoverable from the reference demos."""
 import numpy as np
 import pytest
 
@@ -187,38 +187,86 @@ def test_crop_padding_rule(oracle_mod):
             assert row[s] == row[(s - cnt) % cnt]
 
 
-# ---- against the reference's own CPU programs (only where oracle/_ref was built) ----
-def _need_ref(oracle_mod, kind):
-    if not oracle_mod.ref_available(kind):
-        pytest.skip("oracle/_ref/libhfref_%s.so not built (no /root/reference on this box)" % kind)
+# ---- against the reference's own CPU programs ----
+# Their outputs on seeded inputs are committed in tests/golden/ref_cpu.npz (tests/golden/make_golden.py ref_cpu, where
+# oracle/_ref was built); where oracle/_ref/libhfref_<kind>.so is present the live programs are compared as well.
+REF_CPU_GOLDEN = "ref_cpu"
+
+
+def _ref_sources(oracle_mod, kind, name, run):
+    """[(source, {output name: array})]: the committed outputs, then the live reference build of `kind` if present"""
+    g = load_golden(REF_CPU_GOLDEN)
+    out = [("golden", {k[len(name) + 1:]: g[k] for k in g if k.startswith(name + "/")})]
+    assert out[0][1], "tests/golden/%s.npz has no %s outputs" % (REF_CPU_GOLDEN, name)
+    if oracle_mod.ref_available(kind):
+        out.append(("live", run(oracle_mod)))
+    return out
+
+
+def _sha256(a):
+    import hashlib
+    return np.frombuffer(hashlib.sha256(np.ascontiguousarray(a).tobytes()).digest(), np.uint8)
+
+
+REF_GROUPING_CASES = ((2, 1024, 256, 0.1, 32, 16), (3, 777, 130, 0.25, 64, 5), (1, 128, 8, 0.3, 32, 16))
+
+
+def ref_grouping_inputs():
+    rng = np.random.default_rng(7)
+    for (b, n, m, r, ns, c) in REF_GROUPING_CASES:
+        x1 = rng.random((b, n, 3), dtype=np.float32)
+        x2 = rng.random((b, m, 3), dtype=np.float32)
+        pts = rng.standard_normal((b, n, c)).astype(np.float32)
+        go = rng.standard_normal((b, m, ns, c)).astype(np.float32)
+        yield r, ns, x1, x2, pts, go
+
+
+def ref_grouping_run(oracle_mod):
+    """query_ball_point_cpu -> group_point_cpu / group_point_grad_cpu on the reference's own rows"""
+    out = {}
+    for case, (r, ns, x1, x2, pts, go) in enumerate(ref_grouping_inputs()):
+        idx = oracle_mod.ref_query_ball_point(r, ns, x1, x2)
+        out["idx%d" % case] = idx
+        out["grouped_sha256_%d" % case] = _sha256(oracle_mod.ref_group_point(pts, idx))   # pure copies: a digest
+        out["grad%d" % case] = oracle_mod.ref_group_point_grad(pts.shape, idx, go)
+    return out
 
 
 def test_oracle_vs_reference_cpu_grouping(oracle_mod):
-    _need_ref(oracle_mod, "qbp")
-    rng = np.random.default_rng(7)
-    for (b, n, m, r, ns, c) in ((2, 1024, 256, 0.1, 32, 16), (3, 777, 130, 0.25, 64, 5), (1, 128, 8, 0.3, 32, 16)):
-        x1 = rng.random((b, n, 3), dtype=np.float32)
-        x2 = rng.random((b, m, 3), dtype=np.float32)
+    mine = {}
+    for case, (r, ns, x1, x2, pts, go) in enumerate(ref_grouping_inputs()):
         idx, _ = oracle_mod.query_ball_point(r, ns, x1, x2)
-        assert np.array_equal(idx, oracle_mod.ref_query_ball_point(r, ns, x1, x2))
-        pts = rng.standard_normal((b, n, c)).astype(np.float32)
-        assert np.array_equal(oracle_mod.group_point(pts, idx), oracle_mod.ref_group_point(pts, idx))
-        go = rng.standard_normal((b, m, ns, c)).astype(np.float32)
-        assert np.array_equal(oracle_mod.group_point_grad(pts.shape, idx, go),
-                              oracle_mod.ref_group_point_grad(pts.shape, idx, go))
+        mine["idx%d" % case] = idx
+        mine["grouped_sha256_%d" % case] = _sha256(oracle_mod.group_point(pts, idx))
+        mine["grad%d" % case] = oracle_mod.group_point_grad(pts.shape, idx, go)
+    for source, ref in _ref_sources(oracle_mod, "qbp", "grouping", ref_grouping_run):
+        assert set(ref) == set(mine), source
+        for k, v in mine.items():
+            assert np.array_equal(v, ref[k]), (source, k)
 
 
-def test_oracle_vs_reference_cpu_interpolate(oracle_mod):
-    _need_ref(oracle_mod, "itp")
+def ref_interpolate_inputs():
     rng = np.random.default_rng(8)
     b, n, m, c = 2, 300, 77, 9
     idx = rng.integers(0, m, (b, n, 3)).astype(np.int32)
     w = rng.random((b, n, 3), dtype=np.float32)
     pts = rng.standard_normal((b, m, c)).astype(np.float32)
-    assert np.array_equal(oracle_mod.three_interpolate(pts, idx, w), oracle_mod.ref_three_interpolate(pts, idx, w))
     go = rng.standard_normal((b, n, c)).astype(np.float32)
-    assert np.array_equal(oracle_mod.three_interpolate_grad(pts.shape, idx, w, go),
-                          oracle_mod.ref_three_interpolate_grad(pts.shape, idx, w, go))
+    return idx, w, pts, go
+
+
+def ref_interpolate_run(oracle_mod):
+    idx, w, pts, go = ref_interpolate_inputs()
+    return {"out": oracle_mod.ref_three_interpolate(pts, idx, w), "grad": oracle_mod.ref_three_interpolate_grad(pts.shape, idx, w, go)}
+
+
+def test_oracle_vs_reference_cpu_interpolate(oracle_mod):
+    idx, w, pts, go = ref_interpolate_inputs()
+    out = oracle_mod.three_interpolate(pts, idx, w)
+    grad = oracle_mod.three_interpolate_grad(pts.shape, idx, w, go)
+    for source, ref in _ref_sources(oracle_mod, "itp", "interpolate", ref_interpolate_run):
+        assert np.array_equal(out, ref["out"]), source
+        assert np.array_equal(grad, ref["grad"]), source
 
 
 def _threenn_cases():
@@ -226,20 +274,28 @@ def _threenn_cases():
     return {k[:-6]: g[k] for k in g if k.endswith("_known")}, g
 
 
+def ref_threenn_origin_run(oracle_mod):
+    cases, _ = _threenn_cases()
+    out = {}
+    for name, known in cases.items():
+        out[name + "_dist"], out[name + "_idx"] = oracle_mod.ref_threenn_origin(known, n=2)
+    return out
+
+
 def test_oracle_three_nn_vs_reference_cpu_at_the_origin(oracle_mod):
     """a5 pin: oracle.three_nn (restating tf_interpolate_g.cu:22-65, unbuildable here) against the reference's compiled
     threenn_cpu for unknown points at the origin -- bit-for-bit, distances and indices (see oracle.ref_threenn_origin)."""
-    _need_ref(oracle_mod, "itp")
     cases, _ = _threenn_cases()
     assert set(cases) == {"random", "large", "ties", "lattice", "m1", "m2", "m3", "ramps", "all_equal"}
-    for name, known in cases.items():
-        b, m, _ = known.shape
-        rd, ri = oracle_mod.ref_threenn_origin(known, n=2)
-        od, oi = oracle_mod.three_nn(np.zeros((b, 2, 3), np.float32), known)
-        assert np.array_equal(oi, ri), name
-        assert np.array_equal(od.view(np.uint32), rd.view(np.uint32)), name
-        if m < 3:                                             # sentinels: double 1e40 -> +inf in fp32, index 0
-            assert np.isinf(rd[:, :, m:]).all() and (ri[:, :, m:] == 0).all(), name
+    for source, ref in _ref_sources(oracle_mod, "itp", "threenn_origin_n2", ref_threenn_origin_run):
+        for name, known in cases.items():
+            b, m, _ = known.shape
+            rd, ri = ref[name + "_dist"], ref[name + "_idx"]
+            od, oi = oracle_mod.three_nn(np.zeros((b, 2, 3), np.float32), known)
+            assert np.array_equal(oi, ri), (source, name)
+            assert np.array_equal(od.view(np.uint32), rd.view(np.uint32)), (source, name)
+            if m < 3:                                             # sentinels: double 1e40 -> +inf in fp32, index 0
+                assert np.isinf(rd[:, :, m:]).all() and (ri[:, :, m:] == 0).all(), (source, name)
 
 
 def test_oracle_three_nn_golden_from_reference_cpu(oracle_mod):
@@ -258,16 +314,27 @@ def test_oracle_three_nn_golden_from_reference_cpu(oracle_mod):
                 assert i[r, s_] < i[r, s_ + 1]
 
 
-def test_oracle_three_nn_translated_lattice_vs_reference_cpu(oracle_mod):
-    """The subtraction of tf_interpolate_g.cu:47 against reference-compiled code where it is exact: on a dyadic lattice
-    (multiples of 2^-6 below 64) ux - x is representable, so the reference's d for (u, known) has the bits of threenn_cpu's
-    x2*x2+y2*y2+z2*z2 on the cloud translated by -u.  One batch element per query (threenn_cpu advances both clouds per batch)."""
-    _need_ref(oracle_mod, "itp")
+def ref_lattice_inputs():
     rng = np.random.default_rng(22)
     known = (rng.integers(-2048, 2048, (300, 3)) / 64.0).astype(np.float32)
     unknown = (rng.integers(-2048, 2048, (128, 3)) / 64.0).astype(np.float32)
     shifted = (known[None, :, :] - unknown[:, None, :]).astype(np.float32)         # exact
-    assert np.array_equal(shifted.astype(np.float64), known[None].astype(np.float64) - unknown[:, None].astype(np.float64))
+    return known, unknown, shifted
+
+
+def ref_lattice_run(oracle_mod):
+    _, _, shifted = ref_lattice_inputs()
     rd, ri = oracle_mod.ref_threenn_origin(-shifted)                               # (u - x): the sign the kernel squares
+    return {"dist": rd, "idx": ri}
+
+
+def test_oracle_three_nn_translated_lattice_vs_reference_cpu(oracle_mod):
+    """The subtraction of tf_interpolate_g.cu:47 against reference-compiled code where it is exact: on a dyadic lattice
+    (multiples of 2^-6 below 64) ux - x is representable, so the reference's d for (u, known) has the bits of threenn_cpu's
+    x2*x2+y2*y2+z2*z2 on the cloud translated by -u.  One batch element per query (threenn_cpu advances both clouds per batch)."""
+    known, unknown, shifted = ref_lattice_inputs()
+    assert np.array_equal(shifted.astype(np.float64), known[None].astype(np.float64) - unknown[:, None].astype(np.float64))
     od, oi = oracle_mod.three_nn(unknown[None], known[None])
-    assert np.array_equal(oi[0], ri[:, 0]) and np.array_equal(od[0].view(np.uint32), rd[:, 0].view(np.uint32))
+    for source, ref in _ref_sources(oracle_mod, "itp", "lattice", ref_lattice_run):
+        rd, ri = ref["dist"], ref["idx"]
+        assert np.array_equal(oi[0], ri[:, 0]) and np.array_equal(od[0].view(np.uint32), rd[:, 0].view(np.uint32)), source
