@@ -106,6 +106,11 @@ _SIGNATURES = {
     "hf_rpn_loss_workspace": [],
     "hf_rpn_loss_fwd": [ctypes.c_longlong, _i, _i, _i] + [_vp] * 11 + [_f, _f, _f, _vp, _vp, _sz, _vp],
     "hf_rpn_loss_bwd": [ctypes.c_longlong, _i, _i, _i] + [_vp] * 11 + [_f, _f, _f, _vp, _vp, _vp, _vp, _vp],
+    "hf_rcnn_loss_workspace": [],
+    "hf_rcnn_loss_fwd": [ctypes.c_longlong, _i, _i, _i] + [_vp] * 13 + [_f] * 5 + [_vp, _vp, _sz, _vp],
+    "hf_rcnn_loss_bwd": [ctypes.c_longlong, _i, _i, _i] + [_vp] * 13 + [_f] * 5 + [_vp, _vp, _vp, _vp, _vp],
+    "hf_rcnn_targets_workspace": [_i, _i, _i],
+    "hf_rcnn_proposal_targets": [_i, _i, _i, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _i, _f, _f, _i, _i] + [_vp] * 6 + [_sz, _vp],
     "hf_bin_box_decode": [ctypes.c_longlong, _i] + [_vp] * 13 + [_f, _f, _vp, _vp],
     "hf_bin_box_encode": [ctypes.c_longlong, _i, _i] + [_vp] * 7 + [_f, _f, _f, _f] + [_vp] * 8 + [_vp],
     "hf_bin_head_decode": [ctypes.c_longlong, _i, _i, _i, _i] + [_vp] * 6 + [_f, _f, _vp, _vp, _vp],
@@ -131,6 +136,8 @@ _RESTYPES = {
     "hf_fps_workspace": _sz,
     "hf_ball_query_workspace": _sz,
     "hf_rpn_loss_workspace": _sz,
+    "hf_rcnn_loss_workspace": _sz,
+    "hf_rcnn_targets_workspace": _sz,
     "hf_oriented_nms_workspace": _sz,
     "hf_bn_workspace": _sz,
     "hf_three_nn_workspace": _sz,

@@ -403,6 +403,155 @@ __global__ __launch_bounds__(256) void rpn_loss_finalize_kernel(int nblk, long l
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// The RCNN loss (rcnn_model.py:783-810 masks and targets, :1148-1262 loss, hf/core/losses.py:131-200) in two passes.
+// Masks are formed here from the RoI's IoU with its assigned GT (strict comparisons, as tf.less / tf.greater):
+//   cls    (iou < neg_hi or iou > pos_lo) and non-empty; target class 0 where iou < neg_hi, else gt_cls (a class outside
+//          0..k is tf.one_hot's all-zero row: no loss, no gradient, still counted);
+//   reg    iou > reg_lo and non-empty; the head row and the x / z targets of class max(gt_cls - 1, 0) (never index -1).
+// Forward: per-block partial sums (box cls, bin cls, regression, #cls, #reg).  Backward: gradients w.r.t. the class logits and
+// the head times the device upstream scalar; grad_head is zero-filled by the entry point, only reg rows are written.
+// ------------------------------------------------------------------------------------------
+struct RcnnLossArgs {
+    long long rows;
+    int k, nbx, nbt;                        // head row = [bx nbx | rx nbx | bz nbx | rz nbx | bt nbt | rt nbt | ry | size 3]
+    const float *cls_logits, *head, *iou;   // (rows, k + 1), (rows, k, d), (rows)
+    const int *gt_cls, *non_empty;          // (rows): 0..k, 0 / 1
+    const int *bin_x, *bin_z, *bin_t;
+    const float *res_x, *res_z, *res_t, *res_y, *res_size;
+    float neg_hi, pos_lo, reg_lo, cls_w, reg_w;
+};
+
+template <bool BWD>
+__global__ __launch_bounds__(256) void rcnn_loss_kernel(RcnnLossArgs a, float *__restrict__ partial, const float *__restrict__ counts,
+                                                       const float *__restrict__ upstream, float *__restrict__ grad_cls,
+                                                       float *__restrict__ grad_head)
+{
+    __shared__ float red[5][256];
+    const int d = 4 * a.nbx + 2 * a.nbt + 4;
+    const int k1 = a.k + 1;
+    float s_box = 0.f, s_bin = 0.f, s_reg = 0.f, s_nc = 0.f, s_nr = 0.f;
+    float cls_scale = 0.f, bin_scale = 0.f, reg_scale = 0.f;
+    if (BWD) {
+        const float g = upstream[0];
+        const float inv_c = counts[0] > 0.f ? 1.0f / counts[0] : 0.f, inv_r = counts[1] > 0.f ? 1.0f / counts[1] : 0.f;
+        cls_scale = a.cls_w * inv_c * g;
+        bin_scale = a.cls_w * inv_r * g;
+        reg_scale = a.reg_w * inv_r * g;
+    }
+    for (long long r = blockIdx.x * static_cast<long long>(blockDim.x) + threadIdx.x; r < a.rows;
+         r += static_cast<long long>(gridDim.x) * blockDim.x) {
+        const float iou = a.iou[r];
+        const int gc = a.gt_cls[r];
+        const bool ne = a.non_empty[r] != 0;
+        const bool neg = iou < a.neg_hi;
+        const bool cmask = (neg || iou > a.pos_lo) && ne;
+        const bool rmask = iou > a.reg_lo && ne;
+        const int tgt = neg ? 0 : gc;
+        const bool hot = tgt >= 0 && tgt < k1;
+        if (cmask) {
+            float lg[kLossMaxK1], mx = -INFINITY;
+#pragma unroll
+            for (int j = 0; j < kLossMaxK1; ++j) { lg[j] = j < k1 ? a.cls_logits[r * k1 + j] : -INFINITY; mx = fmaxf(mx, lg[j]); }
+            float se = 0.f, lt = 0.f;
+#pragma unroll
+            for (int j = 0; j < kLossMaxK1; ++j) { if (j == tgt) lt = lg[j]; lg[j] = j < k1 ? expf(lg[j] - mx) : 0.f; se += lg[j]; }
+            if (!BWD) {
+                s_nc += 1.0f;
+                if (hot) s_box += logf(se) + mx - lt;
+            } else if (hot) {
+                const float is = 1.0f / se;
+#pragma unroll
+                for (int j = 0; j < kLossMaxK1; ++j)
+                    if (j < k1) grad_cls[r * k1 + j] = cls_scale * (lg[j] * is - (j == tgt ? 1.0f : 0.0f));
+            }
+        }
+        if (BWD && !(cmask && hot))
+            for (int j = 0; j < k1; ++j) grad_cls[r * k1 + j] = 0.0f;
+        if (!rmask) continue;
+        const int c = min(max(gc - 1, 0), a.k - 1);
+        const float *h = a.head + (r * a.k + c) * d;
+        float *gh = BWD ? grad_head + (r * a.k + c) * d : nullptr;
+        if (!BWD) s_nr += 1.0f;
+        const int tb[3] = { a.bin_x[r * a.k + c], a.bin_z[r * a.k + c], a.bin_t[r] };
+        const float tr[3] = { a.res_x[r * a.k + c], a.res_z[r * a.k + c], a.res_t[r] };
+        int off = 0;
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+            const int nb = q < 2 ? a.nbx : a.nbt;
+            const int tq = min(max(tb[q], 0), nb - 1);
+            float v[kLossMaxBins], m2 = -INFINITY;
+#pragma unroll
+            for (int j = 0; j < kLossMaxBins; ++j) { v[j] = j < nb ? h[off + j] : -INFINITY; m2 = fmaxf(m2, v[j]); }
+            float s2 = 0.f, vt = 0.f;
+#pragma unroll
+            for (int j = 0; j < kLossMaxBins; ++j) { if (j == tq) vt = v[j]; v[j] = j < nb ? expf(v[j] - m2) : 0.f; s2 += v[j]; }
+            const float res = h[off + nb + tq];             // the residual of the TRUE bin (_gather_cls_residuals)
+            if (!BWD) {
+                s_bin += logf(s2) + m2 - vt;
+                s_reg += smooth_l1(res - tr[q]);
+            } else {
+                const float is2 = 1.0f / s2;
+#pragma unroll
+                for (int j = 0; j < kLossMaxBins; ++j)
+                    if (j < nb) gh[off + j] = bin_scale * (v[j] * is2 - (j == tq ? 1.0f : 0.0f));
+                gh[off + nb + tq] = reg_scale * smooth_l1_grad(res - tr[q]);
+            }
+            off += 2 * nb;
+        }
+        const float dy = h[off] - a.res_y[r];
+        if (!BWD) s_reg += smooth_l1(dy); else gh[off] = reg_scale * smooth_l1_grad(dy);
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const float ds = h[off + 1 + j] - a.res_size[r * 3 + j];
+            if (!BWD) s_reg += smooth_l1(ds); else gh[off + 1 + j] = reg_scale * smooth_l1_grad(ds);
+        }
+    }
+    if (BWD) return;
+    const int t = threadIdx.x;
+    red[0][t] = s_box; red[1][t] = s_bin; red[2][t] = s_reg; red[3][t] = s_nc; red[4][t] = s_nr;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if (t < w) {
+#pragma unroll
+            for (int q = 0; q < 5; ++q) red[q][t] += red[q][t + w];
+        }
+        __syncthreads();
+    }
+    if (t < 5) partial[blockIdx.x * 5 + t] = red[t][0];
+}
+
+// one workgroup: the five column sums in fp64 -> out = [box cls, bin cls, regression, #cls, #reg, total]; a term whose count is 0
+// is 0 (the reference's tf.cond(n > 0, x / n, x * 0))
+__global__ __launch_bounds__(256) void rcnn_loss_finalize_kernel(int nblk, float cls_w, float reg_w, const float *__restrict__ partial,
+                                                                float *__restrict__ out)
+{
+    __shared__ double red[5][256];
+    const int t = threadIdx.x;
+    double s[5] = { 0.0, 0.0, 0.0, 0.0, 0.0 };
+    for (int i = t; i < nblk; i += 256)
+#pragma unroll
+        for (int q = 0; q < 5; ++q) s[q] += static_cast<double>(partial[i * 5 + q]);
+#pragma unroll
+    for (int q = 0; q < 5; ++q) red[q][t] = s[q];
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if (t < w) {
+#pragma unroll
+            for (int q = 0; q < 5; ++q) red[q][t] += red[q][t + w];
+        }
+        __syncthreads();
+    }
+    if (t == 0) {
+        const double nc = red[3][0], nr = red[4][0];
+        const double box = nc > 0.0 ? red[0][0] * cls_w / nc : 0.0;
+        const double bin = nr > 0.0 ? red[1][0] * cls_w / nr : 0.0;
+        const double reg = nr > 0.0 ? red[2][0] * reg_w / nr : 0.0;
+        out[0] = static_cast<float>(box); out[1] = static_cast<float>(bin); out[2] = static_cast<float>(reg);
+        out[3] = static_cast<float>(nc); out[4] = static_cast<float>(nr); out[5] = static_cast<float>(box + bin + reg);
+    }
+}
+
 constexpr int kLossBlocks = 1024;
 
 static int glue_grid(long long items, int block)
@@ -530,6 +679,65 @@ HF_API int hf_rpn_loss_bwd(long long rows, int k, int nbx, int nbt, const float 
     int nblk = static_cast<int>((rows + 255) / 256);
     if (nblk > kLossBlocks * 4) nblk = kLossBlocks * 4;
     hipLaunchKernelGGL((rpn_loss_kernel<true>), dim3(nblk), dim3(256), 0, st, a, nullptr, out5 + 3, upstream, grad_seg, grad_head);
+    return launch_status();
+}
+
+HF_API size_t hf_rcnn_loss_workspace(void) { return sizeof(float) * 5 * kLossBlocks; }
+
+static int rcnn_loss_args(long long rows, int k, int nbx, int nbt, const float *cls_logits, const float *head, const float *iou,
+                          const int *gt_cls, const int *non_empty, const int *bin_x, const float *res_x, const int *bin_z,
+                          const float *res_z, const int *bin_theta, const float *res_theta, const float *res_y,
+                          const float *res_size, float neg_hi, float pos_lo, float reg_lo, float cls_w, float reg_w, RcnnLossArgs &a)
+{
+    if (!loss_args_ok(rows, k, nbx, nbt, cls_logits, head, iou)) return HF_EINVAL;
+    if (rows > 0 && (!gt_cls || !non_empty || !bin_x || !res_x || !bin_z || !res_z || !bin_theta || !res_theta || !res_y || !res_size))
+        return HF_EINVAL;
+    a = RcnnLossArgs{ rows, k, nbx, nbt, cls_logits, head, iou, gt_cls, non_empty, bin_x, bin_z, bin_theta, res_x, res_z, res_theta,
+                      res_y, res_size, neg_hi, pos_lo, reg_lo, cls_w, reg_w };
+    return HF_OK;
+}
+
+HF_API int hf_rcnn_loss_fwd(long long rows, int k, int nbx, int nbt, const float *cls_logits, const float *head, const float *iou,
+                            const int *gt_cls, const int *non_empty, const int *bin_x, const float *res_x, const int *bin_z,
+                            const float *res_z, const int *bin_theta, const float *res_theta, const float *res_y,
+                            const float *res_size, float cls_neg_hi, float cls_pos_lo, float reg_pos_lo, float cls_weight,
+                            float reg_weight, float *out6, void *workspace, size_t workspace_bytes, hf_stream_t stream)
+{
+    RcnnLossArgs a;
+    if (rcnn_loss_args(rows, k, nbx, nbt, cls_logits, head, iou, gt_cls, non_empty, bin_x, res_x, bin_z, res_z, bin_theta, res_theta,
+                       res_y, res_size, cls_neg_hi, cls_pos_lo, reg_pos_lo, cls_weight, reg_weight, a) != HF_OK || !out6)
+        return HF_EINVAL;
+    if (!workspace || workspace_bytes < hf_rcnn_loss_workspace()) return HF_EWORKSPACE;
+    int nblk = static_cast<int>((rows + 255) / 256);
+    if (nblk > kLossBlocks) nblk = kLossBlocks;
+    if (nblk < 1) nblk = 1;
+    float *partial = static_cast<float *>(workspace);
+    hipLaunchKernelGGL((rcnn_loss_kernel<false>), dim3(nblk), dim3(256), 0, as_stream(stream), a, partial, nullptr, nullptr, nullptr,
+                       nullptr);
+    hipLaunchKernelGGL(rcnn_loss_finalize_kernel, dim3(1), dim3(256), 0, as_stream(stream), nblk, cls_weight, reg_weight, partial, out6);
+    return launch_status();
+}
+
+HF_API int hf_rcnn_loss_bwd(long long rows, int k, int nbx, int nbt, const float *cls_logits, const float *head, const float *iou,
+                            const int *gt_cls, const int *non_empty, const int *bin_x, const float *res_x, const int *bin_z,
+                            const float *res_z, const int *bin_theta, const float *res_theta, const float *res_y,
+                            const float *res_size, float cls_neg_hi, float cls_pos_lo, float reg_pos_lo, float cls_weight,
+                            float reg_weight, const float *out6, const float *upstream, float *grad_cls, float *grad_head,
+                            hf_stream_t stream)
+{
+    RcnnLossArgs a;
+    if (rcnn_loss_args(rows, k, nbx, nbt, cls_logits, head, iou, gt_cls, non_empty, bin_x, res_x, bin_z, res_z, bin_theta, res_theta,
+                       res_y, res_size, cls_neg_hi, cls_pos_lo, reg_pos_lo, cls_weight, reg_weight, a) != HF_OK)
+        return HF_EINVAL;
+    if (!out6 || !upstream || (rows > 0 && (!grad_cls || !grad_head))) return HF_EINVAL;
+    if (rows == 0) return HF_OK;
+    hipStream_t st = as_stream(stream);
+    const int d = 4 * nbx + 2 * nbt + 4;
+    int rc = hip_status(hipMemsetAsync(grad_head, 0, sizeof(float) * static_cast<size_t>(rows) * k * d, st));
+    if (rc != HF_OK) return rc;
+    int nblk = static_cast<int>((rows + 255) / 256);
+    if (nblk > kLossBlocks * 4) nblk = kLossBlocks * 4;
+    hipLaunchKernelGGL((rcnn_loss_kernel<true>), dim3(nblk), dim3(256), 0, st, a, nullptr, out6 + 3, upstream, grad_cls, grad_head);
     return launch_status();
 }
 

@@ -129,7 +129,11 @@ def project_boxes_to_image(boxes_3d, calib, image_hw):
     lo, hi = pix.min(dim=2).values, pix.max(dim=2).values
     box = torch.cat([lo, hi], dim=-1)
     h, w = image_hw
-    return box, box / torch.tensor([w, h, w, h], dtype=box.dtype, device=box.device)
+    # [w, h, w, h] filled on the device (a host-to-device copy cannot be captured into a graph); tensor division as before
+    denom = box.new_empty(4)
+    denom[0::2] = w
+    denom[1::2] = h
+    return box, box / denom
 
 
 def image_crop_and_resize(img_fts, boxes_norm_yxyx, box_ind, crop_size, extrapolation_value=0.0):

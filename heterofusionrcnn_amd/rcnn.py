@@ -13,7 +13,8 @@
   decode + per-frame oriented NMS          :670-778                tf_decode(proposal centre, proposal heading), class of the best
                                                                    foreground score, empty RoIs dropped, NMS 0.01, 100 boxes
 
-Training losses of the second stage (:780-1000) are not part of BASELINE config 5 (inference) and are not built.
+Training of the second stage (targets and masks :780-870, loss :1148-1262, and the RoI sampling of the reference's data loader)
+lives in rcnn_train.py: device proposal targets (hf_rcnn_proposal_targets), the fused RCNN loss, RcnnTrainer.
 TensorFlow cannot be imported here: the layer semantics follow rpn.py / pointcnn.py (pf.dense = linear -> ELU -> BatchNorm);
 parity unpinned against reference outputs, pinned against the text by tests/test_rcnn.py.
 """
@@ -153,7 +154,9 @@ class RcnnModel(nn.Module):
         flat = proposals.reshape(-1, 7).contiguous()
         box_ind = torch.arange(b, device=xyz.device, dtype=torch.int32).repeat_interleave(n)
         _, box2d_norm = project_boxes_to_image(proposals, calib, cfg.img_hw)                 # (B,n,4) [x1,y1,x2,y2]
-        yxyx = box2d_norm.reshape(-1, 4)[:, [1, 0, 3, 2]]                                   # reorder_projected_boxes
+        xyxy = box2d_norm.reshape(-1, 4)
+        # reorder_projected_boxes; column copies, not a list index (that would copy an index tensor from the host: not capturable)
+        yxyx = torch.stack([xyxy[:, 1], xyxy[:, 0], xyxy[:, 3], xyxy[:, 2]], dim=1)
         boxes8 = modules.box_3d_to_box_8co(expand_proposals(flat, cfg.pooling_context_length)).contiguous()
         crop_pts, crop_fts, crop_int, crop_mask, crop_ind, non_empty = pc_crop_and_sample(
             xyz, rpn_fts.contiguous(), intensity, fg_mask, boxes8, box_ind, cfg.roi_crop_size)

@@ -464,6 +464,62 @@ int hf_rpn_loss_bwd(long long rows, int k, int nbx, int nbt, const float *seg_lo
                     const float *res_theta, const float *res_y, const float *res_size, float seg_weight, float cls_weight,
                     float reg_weight, const float *out5, const float *upstream, float *grad_seg, float *grad_head,
                     hf_stream_t stream);
+/* The RCNN loss (hf/core/models/rcnn_model.py:783-810 masks and targets, :1148-1262 loss, hf/core/losses.py:131-200) over
+ * `rows` RoIs.  cls_logits (rows, k + 1); head (rows, k, 4 nbx + 2 nbt + 4) laid out as hf_bin_head_decode reads it; iou (rows)
+ * the RoI's IoU with its assigned GT; gt_cls (rows) int32 0..k; non_empty (rows) int32 0 / 1; the targets exactly as
+ * hf_bin_box_encode writes them for the RoIs (ref_pts = RoI centre, ref_theta = RoI heading) against their GT boxes.
+ * Masks, formed here with strict comparisons: cls = (iou < cls_neg_hi or iou > cls_pos_lo) and non-empty, target class 0
+ * where iou < cls_neg_hi else gt_cls; reg = iou > reg_pos_lo and non-empty, on the head row / x-z targets of class
+ * max(gt_cls - 1, 0) (a row of class 0 never indexes -1).
+ * hf_rcnn_loss_fwd -> out6 = [box classification, bin classification, regression, #cls boxes, #reg boxes, total]: softmax
+ * cross-entropy summed x cls_weight / #cls; the three bin cross-entropies x cls_weight / #reg; smooth-L1 of the true bin's
+ * x / z / theta residuals, y and the three sizes x reg_weight / #reg; a term whose count is 0 is 0.
+ * hf_rcnn_loss_bwd -> gradients w.r.t. cls_logits and head times *upstream (a device scalar; out6 as the forward wrote it);
+ * grad_head is zero-filled here.  Limits: k + 1 <= 8, nbx, nbt <= 32.  workspace: hf_rcnn_loss_workspace() bytes. */
+size_t hf_rcnn_loss_workspace(void);
+int hf_rcnn_loss_fwd(long long rows, int k, int nbx, int nbt, const float *cls_logits, const float *head, const float *iou,
+                     const int *gt_cls, const int *non_empty, const int *bin_x, const float *res_x, const int *bin_z,
+                     const float *res_z, const int *bin_theta, const float *res_theta, const float *res_y, const float *res_size,
+                     float cls_neg_hi, float cls_pos_lo, float reg_pos_lo, float cls_weight, float reg_weight, float *out6,
+                     void *workspace, size_t workspace_bytes, hf_stream_t stream);
+int hf_rcnn_loss_bwd(long long rows, int k, int nbx, int nbt, const float *cls_logits, const float *head, const float *iou,
+                     const int *gt_cls, const int *non_empty, const int *bin_x, const float *res_x, const int *bin_z,
+                     const float *res_z, const int *bin_theta, const float *res_theta, const float *res_y, const float *res_size,
+                     float cls_neg_hi, float cls_pos_lo, float reg_pos_lo, float cls_weight, float reg_weight, const float *out6,
+                     const float *upstream, float *grad_cls, float *grad_head, hf_stream_t stream);
+
+/* The RCNN's proposal-target layer (hf/datasets/kitti/kitti_dataset.py:440-770, a host NumPy loop in the reference) on the
+ * device.  proposals (b, m, 7) [x, y, z, l, w, h, ry], proposal_count (b) valid rows per frame; gt (b, g, 8)
+ * [x, y, z, l, w, h, ry, cls 1..K], gt_count (b).  Outputs (b, R, 7) rois, (b, R) iou_of_rois, (b, R, 8) gt_of_rois and, when
+ * stats is not NULL, (b, 4) [#fg, #bg, sampled fg, sampled bg] per frame.
+ * IoU: modules.box3d_iou (compute_iou.py:23-64) of every valid (proposal, gt) pair, the BEV overlap of hf_compute_bev_iou.
+ * train = 1 (sample_rois_for_rcnn_training, sample_bg_inds :545-680): per RoI max / first argmax over the GTs, per GT the
+ *   argmax RoI where its max > 0; fg_thresh = min(reg_pos_lo, cls_pos_lo); fg = RoIs with max >= fg_thresh in ascending
+ *   order, then the per-GT argmax RoIs (duplicates kept); easy bg = max < cls_neg_lo; hard bg = cls_neg_lo <= max < cls_neg_hi.
+ *   fg and bg: the first min(round(fg_ratio R), #fg) entries of a random permutation of fg, then R - that many bg; fg only:
+ *   R fg drawn with replacement; bg only: R bg.  bg slots: int(bg hard_bg_ratio) hard then easy when both exist, else all
+ *   from the one that exists, drawn with replacement (floor(u size)).  Output order: fg, then bg.
+ *   aug_method (0 none, 1 'single', 2 'multiple', 3 'normal'): aug_roi_by_noise / random_aug_box3d (:690-770) per slot, up
+ *   to 10 tries for fg and 1 for bg; each try keeps the RoI with probability 0.2, else draws a box; it stops at IoU >=
+ *   fg_thresh with the ASSIGNED gt.  iou_of_rois is that IoU (aug_method 0: the RoI's max IoU).
+ * train = 0 (val, :509-513): R must equal m; every proposal with its max IoU and argmax GT row, no sampling.
+ * Where the reference fails, this defines:
+ *   a frame with no GT (reshape(-1, 0) fails): every RoI is easy bg with IoU 0, gt_of_rois rows are 0, no jitter;
+ *   a frame with neither fg nor bg (pdb.set_trace()): R RoIs of the frame drawn with replacement, their max IoU and argmax
+ *     GT, no jitter (their IoU lies between every loss mask); stats [0, 0, 0, 0];
+ *   proposal_count 0: zero boxes, IoU 0, zero GT rows.
+ * Random numbers: a counter hash of (rng_state[0] = base seed, rng_state[1] = call number, frame, slot, draw); the call
+ * advances rng_state[1] on the device (a replayed graph draws fresh samples).  rng_state: 2 int64 on the device, required
+ * when train = 1, untouched when train = 0.  The draws do not follow NumPy's stream.
+ * Limits: b <= 1024, 1 <= m <= 512, g <= 128, 1 <= R <= 512, aug_method 0..3, fg_ratio and hard_bg_ratio in [0, 1],
+ * cls_neg_lo <= cls_neg_hi; outside them HF_EINVAL, nothing launched.  workspace: hf_rcnn_targets_workspace(b, m, g) bytes
+ * (0 for arguments outside the limits). */
+size_t hf_rcnn_targets_workspace(int b, int m, int g);
+int hf_rcnn_proposal_targets(int b, int m, int g, const float *proposals, const int *proposal_count, const float *gt,
+                             const int *gt_count, float cls_neg_lo, float cls_neg_hi, float cls_pos_lo, float reg_pos_lo,
+                             int roi_per_sample, float fg_ratio, float hard_bg_ratio, int aug_method, int train,
+                             long long *rng_state, float *rois, float *iou_of_rois, float *gt_of_rois, int *stats,
+                             void *workspace, size_t workspace_bytes, hf_stream_t stream);
 /* hf/core/bin_based_box3d_encoder.py:9-139 (tf_decode) for `rows` reference points x k classes: rows = B*p in the RPN
  * (ref_theta NULL = the constant 0), the RoI count in the RCNN.  Per (row, class) inputs are (rows, k[, 3]) arrays;
  * ss / deltas (k,) the per-class XZ search range and bin length; boxes (rows, k, 7) = [x, y, z, l, w, h, ry]. */
