@@ -128,6 +128,10 @@ _SIGNATURES = {
     "hf_xconv_depthwise_gather_grad": [_i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                        _vp, _sz, _vp],
     "hf_xconv_depthwise_gather_grad_workspace": [_i, _i, _i, _i, _i, _i],
+    "hf_kitti_eval_workspace": [_i, ctypes.c_longlong, ctypes.c_longlong],
+    "hf_kitti_eval_overlaps": [_i, _vp, _vp, _vp, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, _i, _i, _vp, _vp, _vp, _vp],
+    "hf_kitti_eval": [_i, _vp, _vp, _vp, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, _i, _i] + [_vp] * 6 + [_i, _i]
+                     + [_vp] * 7 + [_sz, _vp],
     "hf_version": [],
     "hf_strerror": [_i],
     "hf_last_hip_error": [],
@@ -149,6 +153,7 @@ _RESTYPES = {
     "hf_lift_elu_bn_fwd_workspace": _sz,
     "hf_depthwise_k_grad_workspace": _sz,
     "hf_lift_elu_bn_bwd_workspace": _sz,
+    "hf_kitti_eval_workspace": _sz,
     "hf_version": ctypes.c_char_p,
     "hf_strerror": ctypes.c_char_p,
 }

@@ -643,6 +643,59 @@ int hf_adam_multi(int num_chunks, const hf_adam_entry *table, const int *chunk_m
 int hf_copy_multi_max(void);
 int hf_copy_multi(int n, void *const *dst, const void *const *src, const long long *bytes, hf_stream_t stream);
 
+/* ------------------------------------------------------------------ KITTI evaluation (kitti_eval.hip) */
+
+/* The offline KITTI object evaluator, scripts/offline_eval/kitti_native_eval/evaluate_object_3d_offline.cpp (and its _05_iou
+ * twin, which differs only in the overlap table), on the device.  All of it is float64.
+ *
+ * Input: frames in CSR form.  gt_off / det_off (n_frames + 1) int64 are row offsets into gt (n_gt, HF_KITTI_COLS) and
+ * det (n_det, HF_KITTI_COLS); pair_off (n_frames + 1) int64 with pair_off[f+1] - pair_off[f] = rows(gt, f) * rows(det, f)
+ * numbers the (frame, gt g, det d) pairs as pair_off[f] + g * rows(det, f) + d.  Row columns:
+ *   x1 y1 x2 y2 alpha h w l t1 t2 t3 ry extra      extra = truncation (gt) / score (det)
+ * gt_type / det_type (int32): HF_KITTI_CAR ... HF_KITTI_OTHER (the caller maps names case-insensitively); gt_occ (int32).
+ * Per-frame caps: at most HF_KITTI_MAX_GT gt rows (DontCare included) and HF_KITTI_MAX_DET detections; max_gt / max_det are the
+ * caller's largest per-frame counts and must not exceed the caps (HF_EINVAL, nothing launched); offsets that disagree with
+ * them are not checked on the device (such frames are left out, and the results are undefined).
+ *
+ * hf_kitti_eval_overlaps: overlaps (n_pairs, 6) = { image IoU, BEV IoU, 3D IoU, image, BEV, 3D intersection over the
+ * detection (criterion 0) } of every pair; the BEV polygons are the reference's toPolygon rectangles, their intersection an
+ * fp64 Sutherland-Hodgman clip, the union area(det) + area(gt) - intersection; degenerate rectangles give 0, so do the
+ * KITTI DontCare rows (location -1000, dims -1) against a real box.
+ *
+ * hf_kitti_eval: everything else, on the same inputs.  min_overlap (3,3) float64 ON THE DEVICE = MIN_OVERLAP[metric][class],
+ * each in [0, 1); eval_mask bit (metric * 3 + class) = evaluate that pair (the reference evaluates a class for a metric only if
+ * one of its detections qualifies; the caller decides); compute_aos = no detection has alpha == -10.  Outputs, indexed
+ * [metric (image, BEV, 3D)][class (car, pedestrian, cyclist)][difficulty (easy, moderate, hard)] = list l (27 lists):
+ *   thresholds (27, 41) float64, n_thresholds (27) int32  the scores getThresholds selects (<= 41; unused slots 0)
+ *   counts (27, 41, 3) int32                             tp, fp (after DontCare suppression), fn summed over frames
+ *   precision, aos, aos_ground (27, 41) float64          tp / (tp + fp), similarity / (tp + fp), each replaced by the
+ *                                                        maximum over its own and every later slot (std::max_element's
+ *                                                        first-largest); aos only for the image metric with compute_aos,
+ *                                                        aos_ground (heading, |ry_gt - ry_det|) only for BEV and 3D; else 0
+ * Lists outside eval_mask are all zeros.  Every count and the selected thresholds equal the reference's; the similarity sums
+ * are added in the reference's order (GT order within a frame, then frames in order), so two calls give the same bits.
+ * workspace: hf_kitti_eval_workspace(n_frames, n_gt, n_pairs) bytes (HF_EWORKSPACE if smaller), 256-byte aligned.
+ * Scores must not be NaN (the reference sorts them with std::sort). */
+#define HF_KITTI_COLS 13
+#define HF_KITTI_MAX_GT 128
+#define HF_KITTI_MAX_DET 512
+#define HF_KITTI_CAR 0
+#define HF_KITTI_PEDESTRIAN 1
+#define HF_KITTI_CYCLIST 2
+#define HF_KITTI_VAN 3
+#define HF_KITTI_PERSON_SITTING 4
+#define HF_KITTI_DONTCARE 5
+#define HF_KITTI_OTHER 6
+size_t hf_kitti_eval_workspace(int n_frames, long long n_gt, long long n_pairs);
+int hf_kitti_eval_overlaps(int n_frames, const long long *gt_off, const long long *det_off, const long long *pair_off,
+                           long long n_gt, long long n_det, long long n_pairs, int max_gt, int max_det, const double *gt,
+                           const double *det, double *overlaps, hf_stream_t stream);
+int hf_kitti_eval(int n_frames, const long long *gt_off, const long long *det_off, const long long *pair_off, long long n_gt,
+                  long long n_det, long long n_pairs, int max_gt, int max_det, const double *gt, const int *gt_type,
+                  const int *gt_occ, const double *det, const int *det_type, const double *min_overlap, int eval_mask,
+                  int compute_aos, double *thresholds, int *n_thresholds, int *counts, double *precision, double *aos,
+                  double *aos_ground, void *workspace, size_t workspace_bytes, hf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
