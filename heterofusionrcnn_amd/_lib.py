@@ -132,6 +132,11 @@ _SIGNATURES = {
     "hf_kitti_eval_overlaps": [_i, _vp, _vp, _vp, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, _i, _i, _vp, _vp, _vp, _vp],
     "hf_kitti_eval": [_i, _vp, _vp, _vp, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, _i, _i] + [_vp] * 6 + [_i, _i]
                      + [_vp] * 7 + [_sz, _vp],
+    "hf_rpn_batch_points_workspace": [_i, ctypes.c_longlong, ctypes.c_longlong],
+    "hf_rpn_batch_points": [_i, _i, ctypes.c_longlong, ctypes.c_longlong] + [_vp] * 12 + [_sz, _vp],
+    "hf_rpn_point_labels": [_i, _i, _i] + [_vp] * 4 + [_f, _vp, _vp, _vp],
+    "hf_rpn_batch_image_workspace": [_i, ctypes.c_longlong],
+    "hf_rpn_batch_image": [_i, ctypes.c_longlong, ctypes.c_longlong] + [_vp] * 5 + [_i, _i] + [_vp] * 5 + [_sz, _vp],
     "hf_version": [],
     "hf_strerror": [_i],
     "hf_last_hip_error": [],
@@ -154,6 +159,8 @@ _RESTYPES = {
     "hf_depthwise_k_grad_workspace": _sz,
     "hf_lift_elu_bn_bwd_workspace": _sz,
     "hf_kitti_eval_workspace": _sz,
+    "hf_rpn_batch_points_workspace": _sz,
+    "hf_rpn_batch_image_workspace": _sz,
     "hf_version": ctypes.c_char_p,
     "hf_strerror": ctypes.c_char_p,
 }

@@ -257,7 +257,8 @@ __global__ void fuse_concat_grad_kernel(long long rows, int c1, int c2, const fl
 // ------------------------------------------------------------------------------------------
 // The RPN loss (rpn_model.py:1040-1128 + hf/core/losses.py:131-226) in two passes instead of ~80 framework kernels:
 //   segmentation   focal loss on the softmax of the K+1 logits: alpha (1 - p_t)^2 (-log p_t), p_t clipped to [1e-7, 1 - 1e-7],
-//                  summed over all points, x seg_weight / rows;
+//                  summed over all points, x seg_weight / rows.  Label -1 (the ring around a box, kitti_dataset.py:432-438) is
+//                  the all-zero one-hot row of rpn_model.py:713-719: no term and no gradient, still counted in rows;
 //   foreground points (label > 0), on the head row of the labelled class: softmax cross-entropy of the x / z / theta bin
 //                  logits (x cls_weight) and smooth-L1 of the residual of the TRUE bin for x / z / theta, of y and of the three
 //                  sizes (x reg_weight), both / max(number of foreground points, 1).
@@ -271,7 +272,7 @@ struct LossArgs {
     long long rows;
     int k, nbx, nbt;   // classes, x/z bins, theta bins; head row = [bx nbx | rx nbx | bz nbx | rz nbx | bt nbt | rt nbt | ry | size 3]
     const float *seg_logits, *head;
-    const int *label;                       // 0 = background, 1..k
+    const int *label;                       // -1 = ignored, 0 = background, 1..k
     const int *bin_x, *bin_z, *bin_t;       // (rows, k), (rows, k), (rows)
     const float *res_x, *res_z, *res_t, *res_y, *res_size;   // (rows, k), (rows, k), (rows), (rows), (rows, 3)
     float seg_w, cls_w, reg_w;
@@ -312,7 +313,11 @@ __global__ __launch_bounds__(256) void rpn_loss_kernel(LossArgs a, float *__rest
         const float pt = fminf(fmaxf(pt_raw, 1e-7f), 1.0f - 1e-7f);
         const float om = 1.0f - pt;
         if (!BWD) {
-            s_seg += 0.25f * om * om * (-logf(pt));
+            if (lab >= 0) s_seg += 0.25f * om * om * (-logf(pt));   // -1 (ignored): tf.one_hot's all-zero row, no term
+        } else if (lab < 0) {
+#pragma unroll
+            for (int j = 0; j < kLossMaxK1; ++j)
+                if (j < k1) grad_seg[r * k1 + j] = 0.0f;
         } else {
             // d/dpt [alpha (1-pt)^2 (-log pt)] = alpha (2 (1-pt) log pt - (1-pt)^2 / pt); zero where the clip is active
             const float inside = (pt_raw >= 1e-7f && pt_raw <= 1.0f - 1e-7f) ? 1.0f : 0.0f;

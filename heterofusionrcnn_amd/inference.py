@@ -21,7 +21,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import dp, kitti_io
+from . import box_codec, dp, kitti_io
 
 IMAGE_MEAN = (92.8403, 97.7996, 93.5843)        # img_feature_extractor.py:9-11 (R, G, B)
 CLASSES = ("Car", "Pedestrian", "Cyclist")      # rpn_multiclass.config dataset_config.classes
@@ -65,7 +65,10 @@ class ImgVggPyr(nn.Module):
 
     def forward(self, image):
         x = image.permute(0, 3, 1, 2)
-        x = x - torch.tensor(IMAGE_MEAN, device=x.device, dtype=x.dtype).view(1, 3, 1, 1)      # preprocess_input
+        # preprocess_input; on the device the mean is uploaded once, so that a captured train step makes no host copy
+        mean = box_codec.const_f32(x.device, IMAGE_MEAN) if x.is_cuda and x.dtype == torch.float32 else \
+            torch.tensor(IMAGE_MEAN, device=x.device, dtype=x.dtype)
+        x = x - mean.view(1, 3, 1, 1)
         conv1 = self.conv1(x)
         conv2 = self.conv2(F.max_pool2d(conv1, 2))
         conv3 = self.conv3(F.max_pool2d(conv2, 2))

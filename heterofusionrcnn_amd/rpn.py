@@ -350,10 +350,12 @@ def rpn_loss(cfg: RpnConfig, seg_logits, head, label_cls, targets):
     nbx, nbt = cfg.num_bin_xz, cfg.theta_bin_num
     fg = (label_cls > 0)
     fgf = fg.to(seg_logits.dtype)
-    # segmentation: -alpha (1 - p_t)^gamma log(p_t) on the true class, p clipped to [1e-7, 1 - 1e-7]
+    # segmentation: -alpha (1 - p_t)^gamma log(p_t) on the true class, p clipped to [1e-7, 1 - 1e-7]; label -1 (ignored) is
+    # the all-zero one-hot row (rpn_model.py:713-719): no term, still counted in B P
     prob = torch.softmax(seg_logits, dim=-1)
-    pt = torch.gather(prob, 2, label_cls.long().unsqueeze(-1)).squeeze(-1).clamp(1e-7, 1.0 - 1e-7)
-    seg = (0.25 * (1.0 - pt) ** 2 * (-torch.log(pt))).sum() * cfg.seg_loss_weight / float(b * p)
+    pt = torch.gather(prob, 2, label_cls.long().clamp(min=0).unsqueeze(-1)).squeeze(-1).clamp(1e-7, 1.0 - 1e-7)
+    focal = 0.25 * (1.0 - pt) ** 2 * (-torch.log(pt))
+    seg = torch.where(label_cls >= 0, focal, torch.zeros_like(focal)).sum() * cfg.seg_loss_weight / float(b * p)
     # the labelled class's row of the head
     cls0 = targets["cls0"]
     row = torch.gather(head, 2, cls0[:, :, None, None].expand(-1, -1, 1, head.shape[-1])).squeeze(2)   # (B,P,D)

@@ -447,7 +447,8 @@ int hf_fuse_concat_grad(long long rows, int c1, int c2, const float *grad_out, c
                         float *grad_b, hf_stream_t stream);
 /* The RPN loss (hf/core/models/rpn_model.py:1040-1128 with hf/core/losses.py:131-226) in two passes.  rows = B*P points;
  * seg_logits (rows, k+1); head (rows, k, D), D = 4 nbx + 2 nbt + 4 laid out as _parse_rpn_output slices it (:870-935);
- * label (rows) int32: 0 background, 1..k; the targets exactly as hf_bin_box_encode writes them (bin_x / res_x / bin_z / res_z
+ * label (rows) int32: -1 ignored (the reference's all-zero one-hot row: no segmentation term or gradient, still counted in
+ * rows, not foreground), 0 background, 1..k; the targets exactly as hf_bin_box_encode writes them (bin_x / res_x / bin_z / res_z
  * (rows, k), bin_theta / res_theta / res_y (rows), res_size (rows, 3)): the labelled class's entries are picked here
  * (:733-776).  hf_rpn_loss_fwd -> out5 = [segmentation, bin classification, regression, #foreground, total loss]
  * (focal alpha 0.25 gamma 2 on the clipped softmax, x seg_weight / rows; softmax cross-entropy of the three bin groups and
@@ -695,6 +696,57 @@ int hf_kitti_eval(int n_frames, const long long *gt_off, const long long *det_of
                   const int *gt_occ, const double *det, const int *det_type, const double *min_overlap, int eval_mask,
                   int compute_aos, double *thresholds, int *n_thresholds, int *counts, double *precision, double *aos,
                   double *aos_ground, void *workspace, size_t workspace_bytes, hf_stream_t stream);
+
+/* ------------------------------------------------------------------ RPN training batches (csrc/rpn_batch.hip) */
+
+/* The RPN's training sample (hf/datasets/kitti/kitti_dataset.py:291-440, a host NumPy loop in the reference) for b frames
+ * at once.  Random numbers: a counter hash of (rng_state[0] = base seed, rng_state[1] = call number, frame, purpose, index);
+ * each call advances rng_state[1] on the device.  rng_state: 2 int64 on the device.  The draws do not follow NumPy's stream;
+ * the same rng_state gives bit-identical outputs.  No host synchronisation, no float atomics. */
+#define HF_RPN_BATCH_EMPTY 1        /* no point of the frame is in view: its P rows are zeros, src_index -1 */
+#define HF_RPN_BATCH_TOO_MANY_FAR 2 /* more than P points at depth >= 40 m: a random P of them, no near point */
+
+/* Points.  points (total, 4) float32 raw velodyne rows [x, y, z, reflectance] of every frame, frame f = rows
+ * offsets[f] .. offsets[f+1] (int64, b + 1); velo_to_rect (b, 12) fp64 rows 0..2 of R0_rect . Tr_velo_to_cam (padded 4x4,
+ * composed on the host as kitti_io.lidar_to_rect composes it); p2 (b, 12) fp64, the ORIGINAL P2; image_wh (b, 2) int32 the
+ * original image size; flip (b) int32.  max_frame_points >= every frame's row count (sizes the grid).
+ * View filter (obj_utils.py:221-275), fp64: z > 0, then 0 < u < w and 0 < v < h under P2.  Sampling (:341-371) of the n
+ * points in view, near = depth < 40 m: P < n -> every far point and P - n_far near points without replacement; P >= n ->
+ * every point once and P - n extra draws, without replacement when P <= 2 n, else with.  Then shuffled.  Flip: x negated.
+ * Outputs xyz (b, P, 3) float32 (fp64 rounded once), intensity (b, P, 1) = reflectance - 0.5, src_index (b, P) int32 the
+ * frame-local raw row, status (b) int32 HF_RPN_BATCH_* bits.  Limits: b <= 1024, 1 <= P <= 2^20, max_frame_points <= 2^30
+ * and <= total.  workspace: hf_rpn_batch_points_workspace(b, total, max_frame_points) bytes (0 outside the limits). */
+size_t hf_rpn_batch_points_workspace(int b, long long total, long long max_frame_points);
+int hf_rpn_batch_points(int b, int p, long long total, long long max_frame_points, const float *points,
+                        const long long *offsets, const double *velo_to_rect, const double *p2, const int *image_wh,
+                        const int *flip, long long *rng_state, float *xyz, float *intensity, int *src_index, int *status,
+                        void *workspace, size_t workspace_bytes, hf_stream_t stream);
+
+/* Per-point labels, generate_rpn_training_labels (kitti_dataset.py:416-440).  xyz (b, p, 3); boxes (b, g, 7) [x, y, z, l, w,
+ * h, ry] (already flipped); classes (b, g) int32 1..K; gt_count (b) valid boxes per frame; expand (0.2, rpn_multiclass.config
+ * :265).  Each point walks its frame's boxes in order: inside the box -> that class and that box (a later box overwrites an
+ * earlier one); inside exactly one of the box and the box enlarged by l, w, h += 2 expand, y += expand -> class -1 (also
+ * overwrites).  label_reg keeps the last box that contained the point (zeros if none).  Inside test: the corner form of
+ * obj_utils.is_point_inside (:425-482), strict on every face, fp64.  label_cls (b, p) int32 in {-1, 0..K}, label_reg (b, p, 7).
+ * Limits: b <= 1024, 1 <= p <= 2^20, g <= 128. */
+int hf_rpn_point_labels(int b, int p, int g, const float *xyz, const float *boxes, const int *classes, const int *gt_count,
+                        float expand, int *label_cls, float *label_reg, hf_stream_t stream);
+
+/* Images (kitti_dataset.py:376-400, kitti_aug.py:9-14, 121-202).  images: packed uint8 RGB, HWC per frame at byte
+ * image_offsets[f] (int64), size image_wh[f] = (w, h); total_bytes the buffer's size (a frame outside it gives zeros);
+ * max_pixels >= every w * h (sizes the grid).  flip (b), jitter (b) int32.  Flip: source column w - 1 - x.  PCA jitter:
+ * covariance of x / 255 (np.cov, ddof 1) from exact integer sums, 3x3 Jacobi in fp64 (eigenvalues below 0 taken as 0),
+ * noise = (sqrt(e) V) (0.1 N(0, 1)^3), each source value trunc(clip(f64(f32(x) / 255) + noise, 0, 1) * 255).  Resize to
+ * (out_h, out_w) with cv2 INTER_LINEAR's geometry (f = (d + 0.5) S / D - 0.5 in fp64 to fp32, s = floor(f), s < 0 -> (0, 0),
+ * s >= S - 1 -> (S - 1, 0)), fp32 weights, rounded to nearest: image (b, out_h, out_w, 3) float32 in 0..255.  cv2's fixed-
+ * point uint8 path is not restated (bit parity with cv2 is not pinned).  noise (b, 3) fp64 (zeros without jitter);
+ * pca_stats (b, 21) fp64 when not NULL: covariance (3x3 row-major), eigenvalues ascending, eigenvectors (3x3, columns).
+ * Limits: b <= 1024, w, h, out_h, out_w <= 8192, max_pixels <= 2^23.  workspace: hf_rpn_batch_image_workspace(b, max_pixels). */
+size_t hf_rpn_batch_image_workspace(int b, long long max_pixels);
+int hf_rpn_batch_image(int b, long long max_pixels, long long total_bytes, const unsigned char *images,
+                       const long long *image_offsets, const int *image_wh, const int *flip, const int *jitter, int out_h,
+                       int out_w, long long *rng_state, float *image, double *noise, double *pca_stats, void *workspace,
+                       size_t workspace_bytes, hf_stream_t stream);
 
 #ifdef __cplusplus
 }
