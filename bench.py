@@ -1,11 +1,11 @@
 #!/usr/bin/env python3
 """bench.py -- the driver's measurement contract for the hot path.
 
-  python bench.py --gpus N --steps K --warmup W [--scaling auto|weak|strong]
+  python bench.py --gpus N --steps K --warmup W [--scaling auto|weak|strong] [--full]
 
 Default (--scaling auto) = BASELINE config 4's shape: a GLOBAL batch of 8 frames split over the N ranks (strong scaling; 8 frames on
-one GPU, one frame per GPU at N = 8), with the reference's own fixed-per-rank-batch mode (weak: 8 frames per GPU) measured
-right after it and reported under extra.weak_scaling when N > 1.
+one GPU, one frame per GPU at N = 8); with --full and N > 1 the reference's own fixed-per-rank-batch mode (weak: 8 frames per GPU)
+is measured right after it and reported under extra.weak_scaling.
 
 A "step" is one RPN train step (BASELINE.json: "KITTI frames/sec RPN train step") of hf/configs/rpn_multiclass.config
 (BASELINE.json configs[3]) over one batch of synthetic KITTI-shaped frames resident in HBM: the PointCNN backbone (5 X-Conv +
@@ -19,11 +19,14 @@ N > 1: one process per GPU (this script starts them itself when no launcher did)
 (hf/experiments/mpi_run_training.sh + hvd.DistributedOptimizer, hf/core/trainer.py:71).  --workload rpn selects the
 PointNet++ configuration (rpn_cars_pointnet_paper.config), --workload stack the round-1 workload (BASELINE.json configs[1]).
 
-Rank 0 prints ONE JSON line: frames/s (whole job), plus
+Rank 0 prints ONE JSON line: frames/s (whole job), ms_per_step and the config that ran.  A plain run does only that: set up,
+warm up, time the K steps, write --dump-outputs.  --full adds what takes runs of its own, after the timed steps:
   roofline      the fused query_ball_point+group_point kernel at the headline shape
                 (B=8, N=16384, M=4096, K=32), timed live with HIP events on its launch stream;
   cpu_baseline  the CPU oracle's op chain for the same backbone (no GPU), 1 core and all cores, bounded sample;
-  extra         per-op device times and the bev_iou Gboxpairs/s figure BASELINE.json also names.
+  extra         per-op device times and the bev_iou Gboxpairs/s figure BASELINE.json also names, child runs of the other
+                configurations (one frame per GPU, the other graph mode, the PointNet++ step, the VGG branch), weak scaling.
+--no-op-table, --no-cpu-baseline and --no-side-runs leave one of those out of a --full run.
 """
 import argparse
 import json
@@ -572,10 +575,15 @@ def parse_args(argv=None):
     ap.add_argument("--with-vgg", action="store_true",
                     help="rpn_multiclass only: run the image branch too (inference.ImgVggPyr forward + backward on the vendor "
                          "library, trained with the RPN: hf/core/models/rpn_model.py:126-127,223) instead of feeding a resident "
-                         "feature map; the default run reports this under extra.rpn_multiclass_with_vgg")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-op-table", action="store_true")
-    ap.add_argument("--no-side-runs", action="store_true", help="skip the child runs reported in `extra` (other workload, 1 frame per GPU)")
+                         "feature map; a --full run reports this under extra.rpn_multiclass_with_vgg")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what the headline figure does not need: the roofline kernel alone, "
+                         "the per-op table, child runs of the other configurations, the CPU baseline and, with several ranks, "
+                         "weak scaling (off by default: a plain run sets up, warms up, times the steps and prints the line)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-op-table", action="store_true", help="with --full: skip the per-op table")
+    ap.add_argument("--no-side-runs", action="store_true",
+                    help="with --full: skip the child runs reported in `extra` (other workload, 1 frame per GPU)")
     ap.add_argument("--no-prefetch", action="store_true", help="run the geometry ops inline instead of one step ahead")
     ap.add_argument("--prefetch-depth", type=int, default=2, help="batches of geometry in flight (one HIP stream each)")
     ap.add_argument("--prefetch-group", type=int, default=0,
@@ -650,11 +658,12 @@ def stub_main(args):
 
 
 def _child_bench(extra_args, timeout=420):
-    """a side measurement in a CHILD process after the timed region (same contract: barrier, K timed steps, one JSON line)"""
+    """a side measurement in a CHILD process after the timed region: a plain run of this script (same contract: barrier, K timed
+    steps, one JSON line)"""
     import subprocess
     try:
-        child = subprocess.run([sys.executable, os.path.abspath(__file__), "--no-op-table", "--no-cpu-baseline", "--no-side-runs"] +
-                               list(extra_args), capture_output=True, text=True, timeout=timeout)
+        child = subprocess.run([sys.executable, os.path.abspath(__file__)] + list(extra_args), capture_output=True, text=True,
+                               timeout=timeout)
         line = [l for l in child.stdout.splitlines() if l.startswith("{")][-1]
         o = json.loads(line)
         return {"frames_per_s": o["value"], "ms_per_step": o["ms_per_step"], "frames_per_gpu": o["config"]["frames_per_gpu"],
@@ -852,19 +861,13 @@ def main():
     M = measure(headline_per_gpu, args.dump_outputs)
     per_gpu, use_graph, dt, t_enqueued, multiclass, img_c = M.per_gpu, M.use_graph, M.dt, M.t_enqueued, M.multiclass, M.img_c
     weak = None
-    if world > 1 and args.scaling == "auto" and not args.frames_per_gpu and headline_per_gpu != B:
+    if args.full and world > 1 and args.scaling == "auto" and not args.frames_per_gpu and headline_per_gpu != B:
         timer.pairs.clear()
         weak = measure(B)                                            # the reference's own mode (a fixed per-rank batch): reported under extra
 
     result = None
     if rank == 0:
         frames = world * per_gpu * args.steps
-        in_step_us = M.in_step_us  # inside the timed steps: shares the device with the overlapped MLP kernels
-        xyz8 = torch.from_numpy(kitti_uniform(np.random.default_rng(1000), B, N0)).cuda()   # SURVEY 8(d): KITTI-extent uniform points
-        k_us, n_burst = headline_kernel_burst(hf, xyz8)
-        fused_bytes = ball_group_bytes(B, N0, SA[0][0], KNN)
-        # SURVEY.md 8(d): algorithmic bytes of the two ops at their boundary = 24 641 536 B (the figure `frac` is computed from)
-        achieved = SURVEY_TWO_OP_BYTES / (k_us * 1e-6) / 1e9 if k_us else None
         result = {
             "metric": "KITTI frames/sec RPN train step" if args.workload != "stack" else "KITTI frames/sec, PointNet++ SA+FP stack train step (fwd+bwd+Adam)",
             "value": round(frames / dt, 3), "unit": "frames/s", "n_gpus": world, "ranks": world, "steps": args.steps,
@@ -886,28 +889,35 @@ def main():
                        # host time to submit a step (geometry launches, input copies, the graph launch); the rest of ms_per_step is
                        # the host waiting for the device
                        "host_enqueue_ms_per_step": round(1e3 * t_enqueued / args.steps, 3)},
-            "roofline": {"kernel": "query_ball_point+group_point fused (hf_query_ball_group_xyz), B=8 N=16384 M=4096 K=32",
-                         "bound": "hbm", "achieved": round(achieved, 2) if achieved else None, "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5) if achieved else None,
-                         "traffic": measured_traffic(), "algorithmic_bytes": SURVEY_TWO_OP_BYTES,
-                         # the fused kernel never re-reads idx / xyz: its own compulsory traffic is smaller
-                         "fused_kernel_compulsory_bytes": fused_bytes,
-                         "frac_vs_fused_compulsory_bytes": round(fused_bytes / (k_us * 1e-6) / 1e9 / HBM_PEAK_GBS, 5) if k_us else None,
-                         "avg_launch_us": round(k_us, 3) if k_us else None,
-                         "launches_timed": n_burst,
-                         "in_step_avg_launch_us": round(in_step_us, 3) if in_step_us else None,
-                         "in_step_launches": M.in_step_launches,
-                         "in_step_clouds_per_launch": per_gpu * max(M.prefetch_group, 1),
-                         # the geometry-group shape launched alone (in the step it shares the device with the main stream)
-                         "batched_alone": batched_kernel_burst(hf) if world == 1 else None},
         }
+    if rank == 0 and args.full:
+        in_step_us = M.in_step_us  # inside the timed steps: shares the device with the overlapped MLP kernels
+        xyz8 = torch.from_numpy(kitti_uniform(np.random.default_rng(1000), B, N0)).cuda()   # SURVEY 8(d): KITTI-extent uniform points
+        k_us, n_burst = headline_kernel_burst(hf, xyz8)
+        fused_bytes = ball_group_bytes(B, N0, SA[0][0], KNN)
+        # SURVEY.md 8(d): algorithmic bytes of the two ops at their boundary = 24 641 536 B (the figure `frac` is computed from)
+        achieved = SURVEY_TWO_OP_BYTES / (k_us * 1e-6) / 1e9 if k_us else None
+        result["roofline"] = {"kernel": "query_ball_point+group_point fused (hf_query_ball_group_xyz), B=8 N=16384 M=4096 K=32",
+                              "bound": "hbm", "achieved": round(achieved, 2) if achieved else None, "peak": HBM_PEAK_GBS,
+                              "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5) if achieved else None,
+                              "traffic": measured_traffic(), "algorithmic_bytes": SURVEY_TWO_OP_BYTES,
+                              # the fused kernel never re-reads idx / xyz: its own compulsory traffic is smaller
+                              "fused_kernel_compulsory_bytes": fused_bytes,
+                              "frac_vs_fused_compulsory_bytes": round(fused_bytes / (k_us * 1e-6) / 1e9 / HBM_PEAK_GBS, 5) if k_us else None,
+                              "avg_launch_us": round(k_us, 3) if k_us else None,
+                              "launches_timed": n_burst,
+                              "in_step_avg_launch_us": round(in_step_us, 3) if in_step_us else None,
+                              "in_step_launches": M.in_step_launches,
+                              "in_step_clouds_per_launch": per_gpu * max(M.prefetch_group, 1),
+                              # the geometry-group shape launched alone (in the step it shares the device with the main stream)
+                              "batched_alone": batched_kernel_burst(hf) if world == 1 else None}
     if rank == 0 and weak is not None:
         # the reference's own data-parallel mode (a fixed per-rank batch of 8), same contract, measured right after the headline
         result["extra"] = {"weak_scaling": {"frames_per_s": round(world * weak.per_gpu * args.steps / weak.dt, 3),
                                             "ms_per_step": round(1e3 * weak.dt / args.steps, 3), "frames_per_gpu": weak.per_gpu,
                                             "global_batch": world * weak.per_gpu, "hip_graph": weak.use_graph,
                                             "host_enqueue_ms_per_step": round(1e3 * weak.t_enqueued / args.steps, 3)}}
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         if not args.no_op_table:
             result["extra"] = per_op_table(hf, xyz8)
         if not args.no_side_runs:

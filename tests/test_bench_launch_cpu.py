@@ -52,6 +52,15 @@ def test_dump_outputs_are_float32_and_repeatable(tmp_path):
         assert np.array_equal(a, runs[1][name]), name
 
 
+def test_full_is_off_by_default():
+    """a plain run measures the headline alone; the side measurements come with --full"""
+    sys.path.insert(0, ROOT)
+    import bench
+    assert not bench.parse_args(["--steps", "3"]).full
+    a = bench.parse_args(["--full", "--no-side-runs"])
+    assert a.full and a.no_side_runs and not a.no_op_table and not a.no_cpu_baseline
+
+
 def test_dump_outputs_samples_large_arrays_within_the_budget(tmp_path):
     sys.path.insert(0, ROOT)
     import torch

@@ -412,6 +412,23 @@ def test_bench_two_ranks_rehearsed_on_one_gpu(mode):
 
 
 @pytest.mark.gpu
+def test_bench_plain_run_is_the_headline_alone():
+    """`bench.py` without --full: the timed steps and the one JSON line, none of the side measurements that take runs of
+    their own (roofline bursts, per-op table, child runs, CPU baseline)"""
+    import json, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--frames-per-gpu", "1", "--steps", "2", "--warmup", "1"],
+                         capture_output=True, text=True, timeout=300)
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert out.returncode == 0 and len(lines) == 1, out.stdout[-1500:] + out.stderr[-3000:]
+    d = json.loads(lines[0])
+    assert d["metric"] == "KITTI frames/sec RPN train step" and d["unit"] == "frames/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "f32" and d["steps"] == 2 and d["ms_per_step"] > 0 and np.isfinite(d["value"]) and d["value"] > 0
+    assert d["config"]["frames_per_gpu"] == 1
+    assert not {"roofline", "extra", "cpu_baseline"} & set(d), sorted(d)
+
+
+@pytest.mark.gpu
 def test_copy_many_mixed_dtypes_one_launch():
     """graph_step.copy_many (hf_copy_multi): 150 pairs of mixed dtypes, odd byte counts, unaligned views, an empty tensor and a
     non-contiguous pair (which goes to the framework) -- every destination equals its source, nothing beside them is touched"""
