@@ -12,6 +12,8 @@
 // scalar registers / LDS.  fp32, multiply then add in index order (no FMA contraction), like the rest of the library.
 #include "hf_common.h"
 
+#include <initializer_list>
+
 namespace hf {
 
 // The M consecutive floats a (row, channel) pair owns in a (rows, C*M) tensor.  As M scalar accesses a wave's instruction touches
@@ -357,6 +359,188 @@ __global__ __launch_bounds__(kXcThreads) void depthwise_dw_kernel(long long rows
 // `fts` (clouds x n_src rows x c - c0) through the neighbour table `idx` (rows x K, indices inside the row's cloud).  c0 is a multiple of 64, so a block's 64-channel
 // chunk lies on one side.  The gathered rows (K x the table, 1.1 GB for the last decoder layers) were written by
 // group_point and read back here; now the table (134 MB, L2 / MALL resident) is read in place.
+// Channel pairs: a lane owns channels (ch, ch + 1), ch even, so a wave covers 128 channels and every product runs as ONE packed
+// f32 op on the pair (v_pk_mul_f32 / v_pk_add_f32 round each half like the scalar op; -ffp-contract=off keeps them unfused).
+// Packing runs across channels only: every output element keeps its own multiply-then-add sequence in index order.
+typedef float f2 __attribute__((ext_vector_type(2)));
+
+// Where a lane's channel pair comes from.  c0 is a multiple of 64, so a 128-channel wave may straddle the lifted / gathered
+// split at lane 32: the source is picked per lane by select (base pointer and row offset), with no branch around the loads.
+// Element offsets are 32-bit (the launcher checks the tensor sizes).  A lane past the last channel reads a clamped, valid
+// pair and stores nothing; with c odd (`V2` false) the pair is read as two floats, the second one only while ch + 1 < c.
+struct XcPair {
+    const float *base;   // f + ch (lifted) or fts + ch - c0 (gathered)
+    unsigned hi;         // offset of the second channel: 1, or 0 where ch + 1 is past the end
+    bool gathered, live, hi_live;
+};
+
+__device__ __forceinline__ XcPair xc_pair(int ch, int c, int c0, const float *f, const float *fts, bool gather)
+{
+    XcPair s;
+    s.live = ch < c;
+    s.hi_live = ch + 1 < c;
+    const int cc = s.live ? ch : (c - 1) & ~1;   // clamped: a valid even channel
+    s.hi = s.hi_live ? 1u : 0u;
+    s.gathered = gather && cc >= c0;
+    s.base = s.gathered ? fts + (cc - c0) : f + cc;
+    return s;
+}
+
+template <bool V2>
+__device__ __forceinline__ f2 ld_pair(const float *p, unsigned hi)
+{
+    if constexpr (V2) return *reinterpret_cast<const f2 *>(p);
+    else return f2{p[0], p[hi]};
+}
+
+// the 2 * M floats of a channel pair in a (rows, C * M) tensor: channel ch's M values, then ch + 1's
+template <int M, bool V2>
+__device__ __forceinline__ void st_pair_m(float *p, bool hi_live, const f2 (&v)[M])
+{
+    if constexpr (V2) {
+#pragma unroll
+        for (int q = 0; q < M; ++q) {
+            const int e0 = 2 * q, e1 = 2 * q + 1;
+            reinterpret_cast<f2 *>(p)[q] = f2{e0 < M ? v[e0].x : v[e0 - M].y, e1 < M ? v[e1].x : v[e1 - M].y};
+        }
+    } else {
+#pragma unroll
+        for (int m = 0; m < M; ++m) p[m] = v[m].x;
+        if (hi_live) {
+#pragma unroll
+            for (int m = 0; m < M; ++m) p[M + m] = v[m].y;
+        }
+    }
+}
+
+// Rows of a wave: r0 + wave + 4 i (i = 0, 1, ...), as one wave per row walked them, taken R at a time: the R rows' index
+// loads and neighbour gathers are all issued before the first row's products.  A row past the block's end is clamped to the
+// last row (its loads stay valid) and not stored.  Table base of a row's cloud: tracked per wave as the rows ascend, no
+// division per row.
+constexpr int kXcRows = 2;
+
+struct XcCloud {
+    long long next;   // first row of the next cloud
+    unsigned tbase;   // first table row of the current cloud
+};
+
+__device__ __forceinline__ unsigned xc_tbase(XcCloud &cl, long long r, int rows_per_cloud, int n_src)
+{
+    while (r >= cl.next) { cl.next += rows_per_cloud; cl.tbase += static_cast<unsigned>(n_src); }
+    return cl.tbase;
+}
+
+__device__ __forceinline__ XcCloud xc_cloud(long long r, int rows_per_cloud, int n_src)
+{
+    const long long b = r / rows_per_cloud;
+    return XcCloud{(b + 1) * rows_per_cloud, static_cast<unsigned>(b * n_src)};
+}
+
+// the K neighbour pairs of row r: lifted rows r K + j (stride cl_stride), gathered rows tbase + idx[r K + j] (stride c1)
+template <int K, bool GATHER, bool V2>
+__device__ __forceinline__ void xc_gather_row(const XcPair &s, long long r, unsigned tbase, const int *__restrict__ idx,
+                                              unsigned lstride, unsigned c1, f2 (&fv)[K])
+{
+    const unsigned rk = static_cast<unsigned>(r) * K;
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+        const unsigned lo = (rk + j) * lstride;
+        unsigned off = lo;
+        if constexpr (GATHER) {
+            const unsigned go = (tbase + static_cast<unsigned>(idx[rk + j])) * c1;
+            off = s.gathered ? go : lo;
+        }
+        fv[j] = ld_pair<V2>(s.base + off, s.hi);
+    }
+}
+
+// X rows of a trip: one coalesced load per 64 coefficients into registers (issued before the gathers), then into the wave's
+// LDS slots, from where the products read them as broadcasts.  As scalar operands the packed products need each coefficient
+// twice ({x, x} in an SGPR pair): the 64 floats of a row no longer fit and spilled; an LDS broadcast feeds v_pk_mul_f32 with
+// op_sel instead.
+template <int K>
+struct XcXRows {
+    static constexpr int KK = K * K, Q = (KK + 63) / 64;
+    float v[kXcRows][Q];
+    __device__ __forceinline__ void load(const float *__restrict__ x, const long long (&rr)[kXcRows], int lane)
+    {
+#pragma unroll
+        for (int i = 0; i < kXcRows; ++i)
+#pragma unroll
+            for (int q = 0; q < Q; ++q) {
+                const int p = lane + 64 * q;
+                v[i][q] = x[rr[i] * KK + (p < KK ? p : KK - 1)];
+            }
+    }
+    __device__ __forceinline__ void stage(float (*xs)[KK], int lane) const
+    {
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");   // the previous trip's reads are done
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int i = 0; i < kXcRows; ++i)
+#pragma unroll
+            for (int q = 0; q < Q; ++q)
+                if (lane + 64 * q < KK) xs[i][lane + 64 * q] = v[i][q];
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+    }
+};
+
+template <int K, int M, bool GATHER, bool V2>
+__global__ __launch_bounds__(kXcThreads) void xconv_dw_fwd_kernel(long long rows, int c, int c0, int rows_per_block,
+                                                                 const float *__restrict__ x, const float *__restrict__ f,
+                                                                 const float *__restrict__ fts, const int *__restrict__ idx, int n_src,
+                                                                 int rows_per_cloud, const float *__restrict__ wd, float *__restrict__ out)
+{
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
+    const int ch = blockIdx.y * 128 + 2 * lane;
+    const XcPair src = xc_pair(ch, c, c0, f, fts, GATHER);
+    const int cw = src.live ? ch : (c - 1) & ~1;
+    f2 w[K][M];
+#pragma unroll
+    for (int k = 0; k < K; ++k)
+#pragma unroll
+        for (int m = 0; m < M; ++m) w[k][m] = f2{wd[(static_cast<size_t>(k) * c + cw) * M + m], wd[(static_cast<size_t>(k) * c + cw + src.hi) * M + m]};
+    const unsigned lstride = GATHER ? c0 : c, c1 = c - c0;
+    const long long r0 = static_cast<long long>(blockIdx.x) * rows_per_block;
+    const long long r1 = r0 + rows_per_block < rows ? r0 + rows_per_block : rows;
+    __shared__ float xs[kXcThreads / 64][kXcRows][K * K];
+    XcCloud cl = xc_cloud(r0, rows_per_cloud, n_src);
+    for (long long rb = r0 + wave; rb < r1; rb += 4 * kXcRows) {
+        f2 fv[kXcRows][K];
+        long long rr[kXcRows];
+#pragma unroll
+        for (int i = 0; i < kXcRows; ++i) rr[i] = rb + 4 * i < r1 ? rb + 4 * i : r1 - 1;
+        XcXRows<K> xrow;
+        xrow.load(x, rr, lane);
+#pragma unroll
+        for (int i = 0; i < kXcRows; ++i) {
+            const unsigned tb = GATHER ? xc_tbase(cl, rr[i], rows_per_cloud, n_src) : 0u;
+            xc_gather_row<K, GATHER, V2>(src, rr[i], tb, idx, lstride, c1, fv[i]);
+        }
+        xrow.stage(xs[wave], lane);
+#pragma unroll
+        for (int i = 0; i < kXcRows; ++i) {
+            if (rb + 4 * i >= r1) break;
+            const float *xr = xs[wave][i];
+            f2 o[M];
+#pragma unroll
+            for (int m = 0; m < M; ++m) o[m] = f2{0.f, 0.f};
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+                f2 t = xr[k * K] * fv[i][0];
+#pragma unroll
+                for (int j = 1; j < K; ++j) t = t + xr[k * K + j] * fv[i][j];
+#pragma unroll
+                for (int m = 0; m < M; ++m) o[m] = o[m] + t * w[k][m];
+            }
+            if (src.live) st_pair_m<M, V2>(out + static_cast<size_t>(rr[i] * c + ch) * M, src.hi_live, o);
+        }
+    }
+}
+
+// Lane-per-channel source of xconv_dw_bwd_fw_kernel (64 channels per block column): c0 is a multiple of 64, so a chunk lies
+// on one side of the lifted / gathered split.
 struct XcSource {
     const float *base;   // + the lane's channel
     long long stride;
@@ -370,47 +554,6 @@ __device__ __forceinline__ XcSource xc_source(int ch, int c, int c0, const float
     else if (ch - (ch & 63) < c0) { s.base = f + ch; s.stride = c0; s.gathered = false; }
     else { s.base = fts + (ch - c0); s.stride = c - c0; s.gathered = true; }
     return s;
-}
-
-template <int K, int M, bool GATHER>
-__global__ __launch_bounds__(kXcThreads) void xconv_dw_fwd_kernel(long long rows, int c, int c0, int rows_per_block,
-                                                                 const float *__restrict__ x, const float *__restrict__ f,
-                                                                 const float *__restrict__ fts, const int *__restrict__ idx, int n_src,
-                                                                 int rows_per_cloud, const float *__restrict__ wd, float *__restrict__ out)
-{
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
-    const int ch = blockIdx.y * 64 + lane;
-    const bool live = ch < c;
-    const XcSource src = xc_source(live ? ch : blockIdx.y * 64, c, c0, f, fts, GATHER ? idx : nullptr);
-    float w[K][M];
-#pragma unroll
-    for (int k = 0; k < K; ++k)
-#pragma unroll
-        for (int m = 0; m < M; ++m) w[k][m] = live ? wd[(static_cast<size_t>(k) * c + ch) * M + m] : 0.f;
-    const long long r0 = static_cast<long long>(blockIdx.x) * rows_per_block;
-    const long long r1 = r0 + rows_per_block < rows ? r0 + rows_per_block : rows;
-    for (long long r = r0 + wave; r < r1; r += kXcThreads / 64) {
-        const float *xr = x + r * (K * K);
-        float fv[K];
-        const long long tbase = (GATHER && src.gathered) ? static_cast<long long>(static_cast<unsigned>(r) / static_cast<unsigned>(rows_per_cloud)) * n_src : 0;
-#pragma unroll
-        for (int j = 0; j < K; ++j) {
-            const long long srow = (GATHER && src.gathered) ? tbase + idx[r * K + j] : r * K + j;
-            fv[j] = live ? src.base[srow * src.stride] : 0.f;
-        }
-        float o[M];
-#pragma unroll
-        for (int m = 0; m < M; ++m) o[m] = 0.f;
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            float t = xr[k * K] * fv[0];
-#pragma unroll
-            for (int j = 1; j < K; ++j) t = t + xr[k * K + j] * fv[j];
-#pragma unroll
-            for (int m = 0; m < M; ++m) o[m] = o[m] + t * w[k][m];
-        }
-        if (live) store_m<M>(out, static_cast<size_t>(r * c + ch) * M, o);
-    }
 }
 
 // gradients w.r.t. F and Wd, same mapping: per (row, channel) the gradient of F_X (K values), F_X itself (recomputed) and
@@ -821,9 +964,9 @@ HF_API int hf_depthwise_k_grad_ws(long long rows, int k, int c, int m, const flo
     else if (k == 12 && m == 1) { CALL(12, 1) } else if (k == 12 && m == 2) { CALL(12, 2) }                             \
     else return HF_EINVAL;
 
-static void xdw_grid(long long rows, int c, dim3 &grid, int &rows_per_block, int blocks_per_cu = 8)
+static void xdw_grid(long long rows, int c, dim3 &grid, int &rows_per_block, int blocks_per_cu = 8, int chunk = 64)
 {
-    const int cchunks = div_up(c, 64);
+    const int cchunks = div_up(c, chunk);
     long long rchunks = (blocks_per_cu * kNumCU + cchunks - 1) / cchunks;   // ~8 blocks per CU in total (forward, dX)
     if (rchunks > (rows + 3) / 4) rchunks = (rows + 3) / 4;
     if (rchunks < 1) rchunks = 1;
@@ -831,17 +974,39 @@ static void xdw_grid(long long rows, int c, dim3 &grid, int &rows_per_block, int
     grid = dim3(static_cast<unsigned>((rows + rows_per_block - 1) / rows_per_block), cchunks);
 }
 
+// The forward kernel takes channel pairs: 128 channels per block column.  It indexes with 32-bit element offsets: the tensors
+// it addresses by (row, neighbour) -- rows x k x c (F, or F_delta) and the feature table -- must hold fewer than 2^32 elements.  `V2`: pairs are read and written as 8-byte
+// accesses, which needs c even (then every pair starts on an even element) and 8-byte aligned tensors.
+static bool xdw_offsets_fit(long long rows, int k, int c, long long src_rows)
+{
+    return rows * k * static_cast<long long>(c) < (1ll << 32) && src_rows * static_cast<long long>(c) < (1ll << 32);
+}
+
+static bool xdw_v2(int c, std::initializer_list<const void *> ptrs)
+{
+    if (c & 1) return false;
+    for (const void *p : ptrs)
+        if (reinterpret_cast<uintptr_t>(p) & 7) return false;
+    return true;
+}
+
+static void xdw_pair_grid(long long rows, int c, dim3 &grid, int &rpb, int blocks_per_cu) { xdw_grid(rows, c, grid, rpb, blocks_per_cu, 128); }
+
 static int xdw_forward(long long rows, int k, int c, int c0, int m, const float *x, const float *f, const float *fts, const int *idx,
                        int n_src, int rows_per_cloud, const float *wd, float *out, hipStream_t st)
 {
+    if (!xdw_offsets_fit(rows, k, c, idx ? static_cast<long long>(rows / rows_per_cloud) * n_src : 0)) return HF_EINVAL;
     dim3 grid;
     int rpb;
-    xdw_grid(rows, c, grid, rpb);
-#define HF_XDW_FWD(KK, MM)                                                                                             \
-    if (idx) hipLaunchKernelGGL((xconv_dw_fwd_kernel<KK, MM, true>), grid, dim3(kXcThreads), 0, st, rows, c, c0, rpb, x, f, fts, idx, n_src, rows_per_cloud, wd, out); \
-    else hipLaunchKernelGGL((xconv_dw_fwd_kernel<KK, MM, false>), grid, dim3(kXcThreads), 0, st, rows, c, c0, rpb, x, f, fts, idx, n_src, rows_per_cloud, wd, out);
+    xdw_pair_grid(rows, c, grid, rpb, 8);
+    const bool v2 = xdw_v2(c, {f, fts, out});
+#define HF_XDW_FWD_V(KK, MM, V)                                                                                        \
+    if (idx) hipLaunchKernelGGL((xconv_dw_fwd_kernel<KK, MM, true, V>), grid, dim3(kXcThreads), 0, st, rows, c, c0, rpb, x, f, fts, idx, n_src, rows_per_cloud, wd, out); \
+    else hipLaunchKernelGGL((xconv_dw_fwd_kernel<KK, MM, false, V>), grid, dim3(kXcThreads), 0, st, rows, c, c0, rpb, x, f, fts, idx, n_src, rows_per_cloud, wd, out);
+#define HF_XDW_FWD(KK, MM) if (v2) { HF_XDW_FWD_V(KK, MM, true) } else { HF_XDW_FWD_V(KK, MM, false) }
     HF_XDW_DISPATCH(HF_XDW_FWD)
 #undef HF_XDW_FWD
+#undef HF_XDW_FWD_V
     return launch_status();
 }
 
