@@ -111,6 +111,7 @@ _SIGNATURES = {
     "hf_rcnn_loss_bwd": [ctypes.c_longlong, _i, _i, _i] + [_vp] * 13 + [_f] * 5 + [_vp, _vp, _vp, _vp, _vp],
     "hf_rcnn_targets_workspace": [_i, _i, _i],
     "hf_rcnn_proposal_targets": [_i, _i, _i, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _i, _f, _f, _i, _i] + [_vp] * 6 + [_sz, _vp],
+    "hf_box3d_iou_matrix": [_i, _i, _i] + [_vp] * 5 + [_vp],
     "hf_bin_box_decode": [ctypes.c_longlong, _i] + [_vp] * 13 + [_f, _f, _vp, _vp],
     "hf_bin_box_encode": [ctypes.c_longlong, _i, _i] + [_vp] * 7 + [_f, _f, _f, _f] + [_vp] * 8 + [_vp],
     "hf_bin_head_decode": [ctypes.c_longlong, _i, _i, _i, _i] + [_vp] * 6 + [_f, _f, _vp, _vp, _vp],
@@ -137,6 +138,8 @@ _SIGNATURES = {
     "hf_rpn_point_labels": [_i, _i, _i] + [_vp] * 4 + [_f, _vp, _vp, _vp],
     "hf_rpn_batch_image_workspace": [_i, ctypes.c_longlong],
     "hf_rpn_batch_image": [_i, ctypes.c_longlong, ctypes.c_longlong] + [_vp] * 5 + [_i, _i] + [_vp] * 5 + [_sz, _vp],
+    "hf_rpn_handoff_pack": [_i, _i, _i] + [_vp] * 5 + [_vp],
+    "hf_rcnn_batch_inputs": [_i, _i, _i] + [_vp] * 7 + [_vp],
     "hf_version": [],
     "hf_strerror": [_i],
     "hf_last_hip_error": [],

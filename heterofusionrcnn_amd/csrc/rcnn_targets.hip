@@ -332,6 +332,24 @@ __global__ __launch_bounds__(256) void rcnn_jitter_kernel(TgtArgs a)
     a.iou_out[idx] = tiou;
 }
 
+// the (b, m, g) 3D IoU matrix of hf_box3d_iou_matrix: the pairs of rcnn_iou_kernel through the same box3d_iou_dev, zeros in the
+// padding (a proposal row >= proposal_count[f] or a GT column >= gt_count[f])
+__global__ __launch_bounds__(256) void box3d_iou_matrix_kernel(int b, int m, int g, const float *__restrict__ proposals,
+                                                               const int *__restrict__ pcount, const float *__restrict__ gt,
+                                                               const int *__restrict__ gcount, float *__restrict__ iou)
+{
+    const long long idx = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x;
+    const long long total = static_cast<long long>(b) * m * g;
+    if (idx >= total) return;
+    const int j = static_cast<int>(idx % g);
+    const int i = static_cast<int>((idx / g) % m);
+    const int f = static_cast<int>(idx / (static_cast<long long>(g) * m));
+    float v = 0.0f;
+    if (i < pcount[f] && j < gcount[f])
+        v = box3d_iou_dev(proposals + (static_cast<long long>(f) * m + i) * 7, gt + (static_cast<long long>(f) * g + j) * 8);
+    iou[idx] = v;
+}
+
 }  // namespace hf
 
 using namespace hf;
@@ -375,5 +393,17 @@ HF_API int hf_rcnn_proposal_targets(int b, int m, int g, const float *proposals,
     hipLaunchKernelGGL(rcnn_sample_kernel, dim3(b), dim3(kTgtThreads), 0, st, a);
     if (train && aug_method != 0)
         hipLaunchKernelGGL(rcnn_jitter_kernel, dim3(div_up(static_cast<long long>(b) * roi_per_sample, 256)), dim3(256), 0, st, a);
+    return launch_status();
+}
+
+HF_API int hf_box3d_iou_matrix(int b, int m, int g, const float *proposals, const int *proposal_count, const float *gt,
+                               const int *gt_count, float *iou, hf_stream_t stream)
+{
+    if (b < 0 || b > kTgtMaxB || m < 1 || m > kTgtMaxM || g < 0 || g > kTgtMaxG) return HF_EINVAL;
+    if (b == 0 || g == 0) return HF_OK;
+    if (!proposals || !proposal_count || !gt || !gt_count || !iou) return HF_EINVAL;
+    const long long pairs = static_cast<long long>(b) * m * g;
+    hipLaunchKernelGGL(box3d_iou_matrix_kernel, dim3(div_up(pairs, 256)), dim3(256), 0, as_stream(stream), b, m, g, proposals,
+                       proposal_count, gt, gt_count, iou);
     return launch_status();
 }

@@ -1,0 +1,182 @@
+"""Export the RPN's hand-off for the second stage: python -m heterofusionrcnn_amd.export_rpn DATASET_DIR MODEL.pt OUT_DIR
+[--split train] [--config rpn_multiclass] [--batch 8]
+
+The reference's `run_inference.py --save_rpn_feature` (hf/core/evaluator.py:934-1065): the trained RPN runs in test mode over
+every frame of the split, once, in order, without augmentation (kitti_data's device assembly: hf_rpn_batch_points,
+hf_rpn_batch_image; the last batch may be short), and writes per frame
+  OUT/proposals_and_scores/NAME.txt   every post_nms_size row (rpn_fixed_num_proposal_nms: the padded rows too), 7 box columns
+                                      and the score, %.3f (kitti_io.save_proposals_and_scores)
+  OUT/rpn_feature/NAME.npy            (P, 5 + c) float32 [x, y, z, intensity, fg, rpn_fts...] from hf_rpn_handoff_pack, one
+                                      device-to-host copy per batch
+  OUT/proposals_iou/NAME.txt          when label_2/NAME.txt exists: the (n, g) 3D IoU of the unrounded proposals x the labels of
+                                      the configured classes (hf_box3d_iou_matrix), %.3f
+and logs the reference's recall line per batch (Recall@3DIoU 0.5 / 0.7: the share of labels whose best proposal exceeds it).
+Files are written by worker threads from pinned host buffers, so the device never waits on the disk.
+"""
+import argparse
+import concurrent.futures
+import os
+import sys
+
+import numpy as np
+import torch
+
+from . import kitti_io
+from . import kitti_data as KD
+from .inference import CLASSES, rescale_p2
+from .rcnn_data import HANDOFF_DIRS, box3d_iou_matrix, handoff_pack
+from .train_rpn import CONFIGS, make_model
+
+
+def read_export_frame(dataset_dir, name, classes, img_hw):
+    """kitti_data.read_frame without augmentation; a frame without a label file has no boxes and no IoU file"""
+    if os.path.isfile(os.path.join(dataset_dir, "label_2", name + ".txt")):
+        fr = KD.read_frame(dataset_dir, name, (), classes, img_hw)
+        fr["has_label"] = True
+        return fr
+    calib = kitti_io.read_calib(os.path.join(dataset_dir, "calib", name + ".txt"))
+    image = KD.read_png(os.path.join(dataset_dir, "image_2", name + ".png"))
+    h0, w0 = image.shape[:2]
+    p2 = calib["p2"]
+    return {"name": name, "augs": (), "points": kitti_io.read_velodyne(os.path.join(dataset_dir, "velodyne", name + ".bin")),
+            "velo_to_rect": KD.velo_to_rect_matrix(calib), "p2": np.asarray(p2, np.float64), "wh": (w0, h0), "image": image,
+            "flip": 0, "jitter": 0, "boxes": np.zeros((0, 7)), "cls": np.zeros((0,), np.int32), "has_label": False,
+            "calib": rescale_p2(p2.astype(np.float32), (w0, h0), (img_hw[1], img_hw[0]))}
+
+
+def recall_counts(iou):
+    """(n, g) IoU -> (#labels with a proposal above 0.5, above 0.7) (box_util.compute_recall_iou)"""
+    if iou.size == 0:
+        return 0, 0
+    best = iou.max(axis=0)
+    return int((best > 0.5).sum()), int((best > 0.7).sum())
+
+
+def _write_batch(out_dir, names, has_label, host, event, gcounts, batch_index, log):
+    """worker thread: wait for the batch's copies, write its files, -> {name: totals}"""
+    event.synchronize()
+    rows, props, scores, iou = host["rows"].numpy(), host["proposals"].numpy(), host["scores"].numpy(), host["iou"].numpy()
+    out, s50, s70, sl, sp = {}, 0, 0, 0, 0
+    for i, name in enumerate(names):
+        kitti_io.save_proposals_and_scores(os.path.join(out_dir, "proposals_and_scores", name + ".txt"), props[i], scores[i])
+        np.save(os.path.join(out_dir, "rpn_feature", name + ".npy"), rows[i])
+        tot = {"proposals": int(props.shape[1]), "labels": 0, "recall_50": 0, "recall_70": 0}
+        if has_label[i]:
+            m = iou[i, :, :gcounts[i]]
+            np.savetxt(os.path.join(out_dir, "proposals_iou", name + ".txt"), m, fmt="%.3f")
+            r50, r70 = recall_counts(m)
+            tot.update(labels=int(gcounts[i]), recall_50=r50, recall_70=r70)
+            s50, s70, sl = s50 + r50, s70 + r70, sl + int(gcounts[i])
+        sp += tot["proposals"]
+        out[name] = tot
+    if log:
+        log("Batch %d: RPN Recall@3DIoU=0.5: %.3f  Recall@3DIoU=0.7: %.3f, num proposals: %d" % (
+            batch_index, s50 / max(sl, 1), s70 / max(sl, 1), sp))
+    return out
+
+
+@torch.no_grad()
+def export(dataset_dir, model, out_dir, split="train", config="rpn_multiclass", batch=8, img_conv=None, workers=8, seed=0,
+           num_points=16384, img_hw=(360, 1200), pre_nms_size=9000, nms_thresh=0.8, post_nms_size=100, classes=CLASSES, log=print):
+    """model: a path to a saved state_dict (train_rpn --save), a state_dict, or a built model (RpnModel / RpnWithImageBranch).
+    -> {name: {"proposals", "labels", "recall_50", "recall_70"}} for every frame of the split"""
+    if isinstance(model, torch.nn.Module):
+        net = model
+    else:
+        sd = torch.load(model, map_location="cpu") if isinstance(model, (str, os.PathLike)) else model
+        net, _ = make_model(config, img_conv)
+        net.load_state_dict(sd, strict=True)
+    was_training = net.training
+    net.eval()
+    with_image = hasattr(net, "img_net")
+    rpn = net.rpn if with_image else net
+    names = KD.read_split(dataset_dir, split)
+    for d in HANDOFF_DIRS:
+        os.makedirs(os.path.join(out_dir, d), exist_ok=True)
+    device = next(net.parameters()).device
+    rng_state = torch.tensor([int(seed), 0], dtype=torch.int64, device=device)
+    pool = concurrent.futures.ThreadPoolExecutor(max_workers=max(1, int(workers)))
+    ahead = concurrent.futures.ThreadPoolExecutor(max_workers=1)
+    writer = concurrent.futures.ThreadPoolExecutor(max_workers=2)
+    chunks = [names[i:i + batch] for i in range(0, len(names), batch)]
+    read = lambda ch: list(pool.map(lambda n: read_export_frame(dataset_dir, n, list(classes), img_hw), ch))
+    staging = [KD._Staging(), KD._Staging()]
+    host_sets = [{}, {}]
+    writes = [None, None]
+    pending = ahead.submit(read, chunks[0]) if chunks else None
+    totals = {}
+    try:
+        for bi, chunk in enumerate(chunks):
+            frames = pending.result()
+            st = staging[bi % 2]
+            if st.event is not None:
+                st.event.synchronize()
+            packed = KD.pack_frames(frames, st)
+            points, images, meta = KD.upload(packed, device)
+            st.event = torch.cuda.Event()
+            st.event.record()
+            pending = ahead.submit(read, chunks[bi + 1]) if bi + 1 < len(chunks) else None
+            xyz, inten, _, _ = KD.batch_points(points, meta["offsets"], meta["velo_to_rect"], meta["p2"], meta["wh"], meta["flip"],
+                                               rng_state, num_points, packed["max_frame_points"])
+            geo = rpn.geometry(xyz)
+            if with_image:
+                image, _ = KD.batch_image(images, meta["img_offsets"], meta["wh"], meta["flip"], meta["jitter"], rng_state, img_hw,
+                                          packed["max_pixels"])
+                out = rpn.propose(xyz, inten, geo, net.img_net(image), meta["calib"], pre_nms_size, nms_thresh, post_nms_size)
+            else:
+                out = rpn.propose(xyz, inten, geo, None, None, pre_nms_size, nms_thresh, post_nms_size)
+            rows = handoff_pack(xyz, inten, out["fg_mask"], out["rpn_fts"])
+            b, m = out["proposals"].shape[:2]
+            gt = torch.cat([meta["boxes"], meta["cls"].unsqueeze(-1).float()], dim=-1)
+            iou = box3d_iou_matrix(out["proposals"], torch.full((b,), m, dtype=torch.int32, device=device), gt, meta["gt_count"])
+            # the pinned host set of this parity is free once its last writer has finished
+            if writes[bi % 2] is not None:
+                totals.update(writes[bi % 2].result())
+            hs = host_sets[bi % 2]
+            dev = {"rows": rows, "proposals": out["proposals"], "scores": out["proposal_scores"], "iou": iou}
+            for k, t in dev.items():
+                if k not in hs or hs[k].numel() < t.numel():
+                    hs[k] = torch.empty((t.numel() * 5 // 4 + 1,), dtype=t.dtype).pin_memory()
+            host = {k: hs[k][:t.numel()].view(t.shape) for k, t in dev.items()}
+            for k, t in dev.items():
+                host[k].copy_(t, non_blocking=True)
+            done = torch.cuda.Event()
+            done.record()
+            gcounts = [len(f["cls"]) for f in frames]
+            writes[bi % 2] = writer.submit(_write_batch, out_dir, [f["name"] for f in frames], [f["has_label"] for f in frames], host,
+                                           done, gcounts, bi, log)
+        for w in writes:
+            if w is not None:
+                totals.update(w.result())
+    finally:
+        ahead.shutdown(wait=True)
+        pool.shutdown(wait=True)
+        writer.shutdown(wait=True)
+        net.train(was_training)
+    return totals
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(prog="python -m heterofusionrcnn_amd.export_rpn",
+                                 description="Run a trained RPN (train_rpn --save) over a split and write the second stage's "
+                                             "training data: proposals_and_scores/, rpn_feature/ and proposals_iou/ under OUT_DIR.")
+    ap.add_argument("dataset_dir")
+    ap.add_argument("model", help="the state_dict saved by train_rpn --save")
+    ap.add_argument("out_dir")
+    ap.add_argument("--split", default="train", help="a list file, or NAME for NAME.txt next to or inside DATASET_DIR")
+    ap.add_argument("--config", choices=CONFIGS, default="rpn_multiclass")
+    ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--seed", type=int, default=0, help="seed of the point sampling")
+    ap.add_argument("--workers", type=int, default=8, help="host threads that read and decode the files")
+    args = ap.parse_args(argv)
+    totals = export(args.dataset_dir, args.model, args.out_dir, args.split, args.config, args.batch, workers=args.workers,
+                    seed=args.seed)
+    labels = sum(t["labels"] for t in totals.values())
+    print("done: %d frames, %d labels, Recall@3DIoU=0.5: %.3f  Recall@3DIoU=0.7: %.3f" % (
+        len(totals), labels, sum(t["recall_50"] for t in totals.values()) / max(labels, 1),
+        sum(t["recall_70"] for t in totals.values()) / max(labels, 1)))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

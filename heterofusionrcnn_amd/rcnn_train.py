@@ -249,3 +249,22 @@ def rcnn_train_loss(model, inputs, geometry):
     loss, _ = model(inputs["xyz"], inputs["rpn_fts"], inputs["intensity"], inputs["fg_mask"], inputs["proposals"],
                     inputs["proposal_count"], inputs["gt"], inputs["gt_count"], inputs["img_fts"], inputs["calib"])
     return loss
+
+
+# ------------------------------------------------------------------------------------------------ with the image branch
+class RcnnWithImageBranch(nn.Module):
+    """The rcnn_multiclass step with its own VGG pyramid (rcnn_multiclass.config img_feature_extractor; inference.ImgVggPyr, a
+    stock convolutional network on the vendor library), the twin of rpn.RpnWithImageBranch: `img_fts` of forward() and detect()
+    is then the IMAGE (B,H,W,3); everything else is RcnnModel's interface, and `cfg` is exposed, so RcnnTrainer drives it."""
+
+    def __init__(self, rcnn: RcnnModel, img_net: nn.Module):
+        super().__init__()
+        self.rcnn, self.img_net = rcnn, img_net
+        self.cfg = rcnn.cfg
+
+    def forward(self, xyz, rpn_fts, intensity, fg_mask, proposals, img_fts, calib):
+        return self.rcnn(xyz, rpn_fts, intensity, fg_mask, proposals, self.img_net(img_fts), calib)
+
+    @torch.no_grad()
+    def detect(self, xyz, rpn_fts, intensity, fg_mask, proposals, img_fts, calib):
+        return self.rcnn.detect(xyz, rpn_fts, intensity, fg_mask, proposals, self.img_net(img_fts), calib)

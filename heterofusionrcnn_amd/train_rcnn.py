@@ -1,0 +1,98 @@
+"""Train the RCNN from KITTI files and the RPN's hand-off: python -m heterofusionrcnn_amd.train_rcnn DATASET_DIR HANDOFF_DIR
+[--split train] [--steps N] [--batch 2] [--seed S] [--save rcnn.pt] [--no-graph]
+
+HANDOFF_DIR is what export_rpn writes (proposals_and_scores/, rpn_feature/, proposals_iou/).  Batches come from
+rcnn_data.KittiRcnnBatches (host reading one batch ahead, device split of the rows, flip and PCA jitter); the model is
+rcnn_train.RcnnWithImageBranch (the RCNN with its own VGG pyramid, rcnn_multiclass.config), sized from the hand-off
+(RcnnConfig(rpn_fts_channels=c, img_channels=...)); the step is graph_step.TrainStep with the device target layer, the fused
+RCNN loss and optim.MultiTensorAdam, replayed from a captured hipGraph.  --save writes the RcnnTrainer's state_dict (weights,
+image branch, the sampler's rng_state); optim.MultiTensorAdam has no state_dict, so optimizer checkpointing is not supported.
+"""
+import argparse
+import sys
+import time
+
+import torch
+
+from .graph_step import TrainStep
+from .inference import ImgVggPyr
+from .optim import MultiTensorAdam
+from .rcnn import RcnnConfig, RcnnModel
+from .rcnn_data import KittiRcnnBatches
+from .rcnn_train import RcnnTrainer, RcnnWithImageBranch
+
+
+def make_trainer(rpn_fts_channels, img_conv=None, seed=0, path_drop=(0.9, 0.9)):
+    """RcnnTrainer(RcnnWithImageBranch(RcnnModel, ImgVggPyr)) on the current device"""
+    img_net = ImgVggPyr(img_conv) if img_conv else ImgVggPyr()
+    cfg = RcnnConfig(rpn_fts_channels=rpn_fts_channels, img_channels=img_net.out_channel, path_drop=tuple(path_drop))
+    return RcnnTrainer(RcnnWithImageBranch(RcnnModel(cfg), img_net), seed=seed).cuda().train()
+
+
+def train(dataset_dir, handoff_dir, split="train", steps=100, batch=2, seed=0, save=None, log_every=10, workers=8, lr=1e-3,
+          graph=True, img_conv=None, aug_list=None, log=print):
+    """-> (list of the per-step losses, read at the end; the trainer)"""
+    torch.manual_seed(seed)
+    data = KittiRcnnBatches(dataset_dir, handoff_dir, split, mode="train", batch=batch, seed=seed, aug_list=aug_list, workers=workers)
+    trainer = make_trainer(data.channels, img_conv, seed)
+    parts = {}
+
+    def loss_fn(m, inputs, geometry):
+        loss, p = m(inputs["xyz"], inputs["rpn_fts"], inputs["intensity"], inputs["fg_mask"], inputs["proposals"],
+                    inputs["proposal_count"], inputs["gt"], inputs["gt_count"], inputs["img_fts"], inputs["calib"])
+        parts.update(p)   # under a graph: the captured tensors, refreshed by every replay
+        return loss
+
+    cur = data.next()
+    opt = MultiTensorAdam([p for p in trainer.parameters() if p.requires_grad], lr=lr, tf_epsilon=False)
+    step = TrainStep(trainer, opt, cur.train_inputs(), None, graph=graph, loss_fn=loss_fn)
+    losses = []
+    t0 = time.perf_counter()
+    try:
+        for i in range(steps):
+            nxt = data.next() if i + 1 < steps else None
+            losses.append(step(**cur.train_inputs()).clone())
+            if log_every and (i + 1) % log_every == 0:
+                st = parts["stats"].sum(dim=0).tolist()
+                log("step %d loss %.5f cls %.5f bin %.5f reg %.5f fg %d bg %d  %.1f ms/step" % (
+                    i + 1, float(losses[-1]), float(parts["box_classification"]), float(parts["bin_classification"]),
+                    float(parts["regression"]), st[2], st[3], 1e3 * (time.perf_counter() - t0) / (i + 1)))
+            cur = nxt
+        status = data.check_status()
+    finally:
+        data.close()
+    if status["bad_fg"]:
+        log("status: %d frames whose fg column held a value other than 0 / 1" % status["bad_fg"])
+    if save:
+        torch.save(trainer.state_dict(), save)
+    out = [float(v) for v in torch.stack(losses).cpu()] if losses else []
+    return out, trainer
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(prog="python -m heterofusionrcnn_amd.train_rcnn",
+                                 description="Train the RCNN (with its VGG image branch) on KITTI frames (calib/, label_2/, image_2/ "
+                                             "under DATASET_DIR) and the RPN hand-off that export_rpn wrote to HANDOFF_DIR. Saves "
+                                             "the trainer's state_dict only (weights, image branch, the RoI sampler's rng_state): "
+                                             "optimizer checkpointing is not supported (optim.MultiTensorAdam has no state_dict), "
+                                             "so a resumed run restarts Adam's moments.")
+    ap.add_argument("dataset_dir")
+    ap.add_argument("handoff_dir")
+    ap.add_argument("--split", default="train", help="a list file, or NAME for NAME.txt next to or inside DATASET_DIR")
+    ap.add_argument("--steps", type=int, default=100)
+    ap.add_argument("--batch", type=int, default=2, help="frames per step (rcnn_multiclass.config:218)")
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--save", default=None, help="path of the saved trainer state_dict (torch.save)")
+    ap.add_argument("--log-every", type=int, default=10)
+    ap.add_argument("--workers", type=int, default=8, help="host threads that read and decode the files")
+    ap.add_argument("--lr", type=float, default=1e-3)
+    ap.add_argument("--no-graph", action="store_true", help="eager steps instead of the captured hipGraph")
+    args = ap.parse_args(argv)
+    losses, _ = train(args.dataset_dir, args.handoff_dir, args.split, args.steps, args.batch, args.seed, args.save, args.log_every,
+                      args.workers, args.lr, not args.no_graph)
+    print("done: %d steps, first loss %.5f, last loss %.5f" % (len(losses), losses[0], losses[-1]))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

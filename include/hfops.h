@@ -521,6 +521,12 @@ int hf_rcnn_proposal_targets(int b, int m, int g, const float *proposals, const 
                              int roi_per_sample, float fg_ratio, float hard_bg_ratio, int aug_method, int train,
                              long long *rng_state, float *rois, float *iou_of_rois, float *gt_of_rois, int *stats,
                              void *workspace, size_t workspace_bytes, hf_stream_t stream);
+/* The (b, m, g) 3D IoU of proposals (b, m, 7) x GT (b, g, 8) [x, y, z, l, w, h, ry, cls] (hf/core/box_util.py:131-174
+ * proposal_gt_iou3d, written by the RPN's export as proposals_iou): each pair through the device function the target layer
+ * samples with, so the values equal hf_rcnn_proposal_targets' IoU bit for bit.  Rows i >= proposal_count[f] and columns
+ * j >= gt_count[f] are 0.  Limits as hf_rcnn_proposal_targets: b <= 1024, 1 <= m <= 512, g <= 128. */
+int hf_box3d_iou_matrix(int b, int m, int g, const float *proposals, const int *proposal_count, const float *gt,
+                        const int *gt_count, float *iou, hf_stream_t stream);
 /* hf/core/bin_based_box3d_encoder.py:9-139 (tf_decode) for `rows` reference points x k classes: rows = B*p in the RPN
  * (ref_theta NULL = the constant 0), the RoI count in the RCNN.  Per (row, class) inputs are (rows, k[, 3]) arrays;
  * ss / deltas (k,) the per-class XZ search range and bin length; boxes (rows, k, 7) = [x, y, z, l, w, h, ry]. */
@@ -747,6 +753,23 @@ int hf_rpn_batch_image(int b, long long max_pixels, long long total_bytes, const
                        const long long *image_offsets, const int *image_wh, const int *flip, const int *jitter, int out_h,
                        int out_w, long long *rng_state, float *image, double *noise, double *pca_stats, void *workspace,
                        size_t workspace_bytes, hf_stream_t stream);
+
+/* ------------------------------------------------------------------ the RPN -> RCNN hand-off (csrc/rcnn_batch.hip) */
+
+/* One (p, 5 + c) float32 row block per frame, [x, y, z, intensity, fg (0.0 / 1.0), rpn_fts...]: the rpn_feature/NAME.npy
+ * payload of hf/core/evaluator.py:963-983.  Limits: b <= 1024, 1 <= p <= 2^20, 1 <= c <= 4096; outside them HF_EINVAL,
+ * nothing launched. */
+#define HF_RCNN_BATCH_BAD_FG 1   /* a fg column value other than 0 or 1 (read as fg = value != 0) */
+
+/* Export side.  xyz (b, p, 3), intensity (b, p, 1), fg_mask (b, p) uint8 / bool (nonzero -> 1.0), rpn_fts (b, p, c) ->
+ * rows (b, p, 5 + c); rows 16-byte aligned (float4 stores). */
+int hf_rpn_handoff_pack(int b, int p, int c, const float *xyz, const float *intensity, const unsigned char *fg_mask,
+                        const float *rpn_fts, float *rows, hf_stream_t stream);
+/* Load side, with the flip augmentation (kitti_aug.flip_points).  rows (b, p, 5 + c), flip (b) int32 -> xyz (b, p, 3) with x
+ * negated on flipped frames, intensity (b, p, 1), fg_mask (b, p) uint8 (value != 0), rpn_fts (b, p, c) (16-byte aligned),
+ * status (b) int32 HF_RCNN_BATCH_* bits (zeroed by the call). */
+int hf_rcnn_batch_inputs(int b, int p, int c, const float *rows, const int *flip, float *xyz, float *intensity,
+                         unsigned char *fg_mask, float *rpn_fts, int *status, hf_stream_t stream);
 
 #ifdef __cplusplus
 }
