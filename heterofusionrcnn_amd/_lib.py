@@ -86,6 +86,8 @@ _SIGNATURES = {
     "hf_linear_wgrad_gather": [ctypes.c_longlong, _i, _i, _vp, _vp, _i, ctypes.c_longlong, _vp, _vp, _vp, _vp, _sz, _vp],
     "hf_adam_chunk": [],
     "hf_adam_multi": [_i, _vp, _vp, _vp, _f, _f, _f, _f, _f, _i, _vp],
+    "hf_adam_sqnorm_partials": [_i, _vp, _vp, _f, _vp, _vp],
+    "hf_adam_multi_sched": [_i, _vp, _vp, _vp, _vp, _f, _f, _i, _f, _f, _f, _f, _f, _f, _i, _vp],
     "hf_copy_multi_max": [],
     "hf_copy_multi": [_i, _vp, _vp, _vp, _vp],
     "hf_linear_bn_bwd_workspace": [_i],

@@ -21,6 +21,7 @@ import sys
 import numpy as np
 import torch
 
+from . import checkpoint as ckpt_mod
 from . import kitti_io
 from . import kitti_data as KD
 from .inference import CLASSES, rescale_p2
@@ -78,12 +79,14 @@ def _write_batch(out_dir, names, has_label, host, event, gcounts, batch_index, l
 @torch.no_grad()
 def export(dataset_dir, model, out_dir, split="train", config="rpn_multiclass", batch=8, img_conv=None, workers=8, seed=0,
            num_points=16384, img_hw=(360, 1200), pre_nms_size=9000, nms_thresh=0.8, post_nms_size=100, classes=CLASSES, log=print):
-    """model: a path to a saved state_dict (train_rpn --save), a state_dict, or a built model (RpnModel / RpnWithImageBranch).
+    """model: a path to a saved state_dict (train_rpn --save) or to a checkpoint (train_rpn --checkpoint-dir), a state_dict, or a
+    built model (RpnModel / RpnWithImageBranch).
     -> {name: {"proposals", "labels", "recall_50", "recall_70"}} for every frame of the split"""
     if isinstance(model, torch.nn.Module):
         net = model
     else:
         sd = torch.load(model, map_location="cpu") if isinstance(model, (str, os.PathLike)) else model
+        sd = ckpt_mod.model_state(sd)
         net, _ = make_model(config, img_conv)
         net.load_state_dict(sd, strict=True)
     was_training = net.training
@@ -161,7 +164,7 @@ def main(argv=None):
                                  description="Run a trained RPN (train_rpn --save) over a split and write the second stage's "
                                              "training data: proposals_and_scores/, rpn_feature/ and proposals_iou/ under OUT_DIR.")
     ap.add_argument("dataset_dir")
-    ap.add_argument("model", help="the state_dict saved by train_rpn --save")
+    ap.add_argument("model", help="the state_dict saved by train_rpn --save, or a checkpoint file (ckpt-NNNNNNNN.pt)")
     ap.add_argument("out_dir")
     ap.add_argument("--split", default="train", help="a list file, or NAME for NAME.txt next to or inside DATASET_DIR")
     ap.add_argument("--config", choices=CONFIGS, default="rpn_multiclass")

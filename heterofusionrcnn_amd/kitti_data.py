@@ -16,6 +16,7 @@ Random numbers on the device come from a [seed, call] pair that each call advanc
 Nothing here synchronises with the device except check_status().
 """
 import concurrent.futures
+import copy
 import itertools
 import os
 
@@ -271,6 +272,25 @@ class SampleList:
         self.order = [int(perm[i]) for i in dp.shard_frames(len(perm), self.rank, self.world)]
         self._pos = 0
         self.epoch += 1
+        self._rng_after = self.rng.bit_generator.state      # the generator moves only here: position() needs no copy per take
+
+    def position(self):
+        """where take() stands: (host generator state, epoch, order, pos); order is never changed in place, so this is cheap"""
+        return (self._rng_after, self.epoch, self.order, self._pos)
+
+    def state_dict(self, position=None):
+        """a position() (default: the current one) as plain Python values"""
+        rng, epoch, order, pos = self.position() if position is None else position
+        return {"rng": copy.deepcopy(rng), "epoch": int(epoch), "order": [int(i) for i in order], "pos": int(pos),
+                "num_samples": len(self.samples)}
+
+    def load_state_dict(self, state):
+        """continue from a state_dict(): the next take() returns what it returned after that state was recorded"""
+        if int(state["num_samples"]) != len(self.samples):
+            raise ValueError("sample list position: %d samples saved, this split has %d" % (int(state["num_samples"]), len(self.samples)))
+        self.rng.bit_generator.state = copy.deepcopy(state["rng"])
+        self._rng_after = self.rng.bit_generator.state
+        self.epoch, self.order, self._pos = int(state["epoch"]), [int(i) for i in state["order"]], int(state["pos"])
 
     def take(self, n):
         """the next n samples of this rank, crossing into the next epoch when this one runs out"""
@@ -285,7 +305,8 @@ class SampleList:
 
 class RpnBatch(dict):
     """device tensors of one batch (xyz, intensity, label_cls, label_reg, image, calib, gt_boxes, gt_cls, gt_count, status,
-    src_index, noise) plus the host lists names / augs; attribute access reads the dict"""
+    src_index, noise) plus the host lists names / augs and `position` (where the loader stood before drawing this batch: its
+    state_dict(position) is what a checkpoint taken before training on the batch records); attribute access reads the dict"""
 
     def __getattr__(self, k):
         try:
@@ -307,22 +328,41 @@ class KittiRpnBatches:
       step = TrainStep(model, opt, b.train_inputs(), model.geometry(b.xyz))
       ...; step.load(**data.next().train_inputs())
 
-    Host reading runs one batch ahead on `workers` threads; next() issues the copies and the three device calls."""
+    Host reading runs one batch ahead on `workers` threads; next() issues the copies and the three device calls.
+
+    Resuming: state_dict() is the position of the next batch next() returns (host generator, epoch, order, position in it, and
+    the device [seed, call] pair that batch starts from), state_dict(batch.position) that of a batch already drawn (the loader
+    works one batch ahead, the trainers hold one more), and KittiRpnBatches(..., state=that) draws the same frames, flips,
+    sampled points and jitter from there on."""
+
+    RNG_CALLS_PER_BATCH = 2      # hf_rpn_batch_points, hf_rpn_batch_image: each advances rng_state[1] by one (rpn_batch.hip)
 
     def __init__(self, dataset_dir, split, classes=CLASSES, batch=8, num_points=16384, img_hw=(360, 1200),
-                 aug_list=(AUG_FLIPPING, AUG_PCA_JITTER), seed=0, rank=0, world=1, workers=8, device=None):
+                 aug_list=(AUG_FLIPPING, AUG_PCA_JITTER), seed=0, rank=0, world=1, workers=8, device=None, state=None):
         self.dataset_dir, self.classes = dataset_dir, list(classes)
         self.batch, self.num_points, self.img_hw = int(batch), int(num_points), tuple(img_hw)
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         self.list = SampleList(dataset_dir, split, self.classes, aug_list, seed, rank, world)
         self.samples = self.list.samples
-        self.rng_state = torch.tensor([int(seed), 0], dtype=torch.int64, device=self.device)
+        # the device [seed, call] pair, mirrored on the host (the kernels advance the call number by one per call)
+        self._rng_host = [int(seed), 0]
+        if state is not None:
+            self.list.load_state_dict(state["samples"])
+            self._rng_host = [int(v) for v in state["rng_state"]]
+        self.rng_state = torch.tensor(self._rng_host, dtype=torch.int64, device=self.device)
         self._pool = concurrent.futures.ThreadPoolExecutor(max_workers=max(1, int(workers)))
         self._ahead = concurrent.futures.ThreadPoolExecutor(max_workers=1)
         self._staging = [_Staging(), _Staging()]
         self._turn = 0
         self._status = []
+        self._pending_pos = self.list.position()
         self._pending = self._ahead.submit(self._prepare, self.list.take(self.batch), self._staging[0])
+
+    def state_dict(self, position=None):
+        """the position of the batch the next next() returns, or of a batch (batch.position), as plain host values (no
+        synchronisation)"""
+        lp, rng = (self._pending_pos, self._rng_host) if position is None else position
+        return {"samples": self.list.state_dict(lp), "rng_state": [int(v) for v in rng]}
 
     def __len__(self):
         return len(self.samples)
@@ -336,12 +376,15 @@ class KittiRpnBatches:
     # --------------------------------------------------------------- device side
     def next(self):
         packed, names, augs = self._pending.result()
+        position = (self._pending_pos, tuple(self._rng_host))     # raw: state_dict(position) makes it plain values
+        self._rng_host[1] += self.RNG_CALLS_PER_BATCH
         staging = self._staging[self._turn]
         self._turn ^= 1
         with torch.cuda.device(self.device):
             points, images, meta = upload(packed, self.device)
             staging.event = torch.cuda.Event()
             staging.event.record()
+            self._pending_pos = self.list.position()
             self._pending = self._ahead.submit(self._prepare, self.list.take(self.batch), self._staging[self._turn])
             xyz, inten, src, status = batch_points(points, meta["offsets"], meta["velo_to_rect"], meta["p2"], meta["wh"], meta["flip"],
                                                    self.rng_state, self.num_points, packed["max_frame_points"])
@@ -351,7 +394,7 @@ class KittiRpnBatches:
         self._status.append(status)
         return RpnBatch(xyz=xyz, intensity=inten, label_cls=label_cls, label_reg=label_reg, image=image, calib=meta["calib"],
                         gt_boxes=meta["boxes"], gt_cls=meta["cls"], gt_count=meta["gt_count"], status=status, src_index=src,
-                        noise=noise, names=names, augs=augs)
+                        noise=noise, names=names, augs=augs, position=position)
 
     def check_status(self):
         """the one synchronising call: status bits of every batch since the last check -> {"empty": frames with no point in

@@ -9,9 +9,16 @@ allocate fresh gradients; a captured graph does not) the table is rewritten and 
 
 `tf_epsilon=True` (default) is TensorFlow's update  p -= lr sqrt(1-b2^t)/(1-b1^t) m / (sqrt(v) + eps); False is
 torch.optim.Adam's placement of epsilon (tests/test_optim.py pins the arithmetic of that mode to torch's own optimizer).
+
+The reference's train op (slim.learning.create_train_op(..., clip_gradient_norm=1.0), hf/core/trainer.py:77-84, with
+tf.train.exponential_decay, hf/builders/optimizer_builder.py:102-110) is opt-in: `clip_norm > 0` clips every tensor's averaged
+gradient to that L2 norm (one more launch per step: the per-chunk sums of squares, hf_adam_sqnorm_partials), `lr_decay=(decay_steps,
+decay_factor[, staircase=True])` decays the learning rate from the device step counter, so a captured step follows the schedule at
+every replay.  With both off a step is the launch above, unchanged.
 """
 import ctypes
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -23,11 +30,44 @@ class _Entry(ctypes.Structure):
                 ("exp_avg_sq", ctypes.c_void_p), ("numel", ctypes.c_longlong)]
 
 
+def _check_decay(lr_decay):
+    """(decay_steps, decay_factor[, staircase]) -> (float, float, bool), or None"""
+    if lr_decay is None:
+        return None
+    if not 2 <= len(lr_decay) <= 3:
+        raise ValueError("lr_decay must be (decay_steps, decay_factor[, staircase])")
+    steps, factor = float(lr_decay[0]), float(lr_decay[1])
+    staircase = bool(lr_decay[2]) if len(lr_decay) == 3 else True
+    if not (steps > 0 and factor > 0):
+        raise ValueError("lr_decay: decay_steps and decay_factor must be > 0, got %r" % (tuple(lr_decay),))
+    return steps, factor, staircase
+
+
+def lr_at(lr, lr_decay, global_step):
+    """tf.train.exponential_decay(lr, global_step, decay_steps, decay_factor, staircase) in fp32, as the update computes it (Adam
+    step t runs at global step t - 1); lr_decay None: lr"""
+    lr_decay = _check_decay(lr_decay)
+    lr = np.float32(lr)
+    if lr_decay is None:
+        return float(lr)
+    q = np.float32(global_step) / np.float32(lr_decay[0])
+    if lr_decay[2]:
+        q = np.floor(q)
+    return float(lr * np.power(np.float32(lr_decay[1]), q, dtype=np.float32))
+
+
 class MultiTensorAdam:
     """step() semantics of torch.optim.Adam(params, lr, betas, eps) without weight decay / amsgrad.  Parameters whose .grad is
-    None at a step are skipped for that step (their moments stay), as the framework optimizers do."""
+    None at a step are skipped for that step (their moments stay), as the framework optimizers do.
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, tf_epsilon=True, grad_scale=1.0):
+    clip_norm > 0: per-tensor tf.clip_by_norm of the averaged gradient before the update.  lr_decay: (decay_steps, decay_factor,
+    staircase=True) for tf.train.exponential_decay of lr.  state_dict() / load_state_dict(): the moments, the step counter (the
+    global step), the hyper-parameters and a fingerprint of the parameter list (count and shapes)."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, tf_epsilon=True, grad_scale=1.0, clip_norm=0.0, lr_decay=None):
+        if not float(clip_norm) >= 0.0:
+            raise ValueError("clip_norm must be >= 0 (0: no clipping), got %r" % (clip_norm,))
+        self.clip_norm, self.lr_decay = float(clip_norm), _check_decay(lr_decay)
         self.params = [p for p in params if p.requires_grad]
         if not self.params:
             raise ValueError("MultiTensorAdam: no parameter requires a gradient")
@@ -62,6 +102,8 @@ class MultiTensorAdam:
         self._dev_map = torch.empty((self._map_rows, 2), dtype=torch.int32, device=dev)
         self._key, self._chunks = None, 0
         self.total_elements = total
+        # the per-chunk sums of squares of the clipped step (one double per map row), allocated here: never inside a capture
+        self._partials = torch.empty(max(self._map_rows, 1), dtype=torch.float64, device=dev)
 
     def _new_staging(self):
         return [torch.empty(self._table_bytes, dtype=torch.uint8).pin_memory(),
@@ -121,9 +163,59 @@ class MultiTensorAdam:
     def step(self):
         self._refresh()
         self.step_count.add_(1.0)
-        check(_lib.lib().hf_adam_multi(self._chunks, ptr(self._dev_table), ptr(self._dev_map), ptr(self.step_count), self.lr,
-                                       self.betas[0], self.betas[1], self.eps, self.grad_scale, 0 if self.tf_epsilon else 1,
-                                       stream_ptr()), "adam_multi")
+        L = _lib.lib()
+        mode = 0 if self.tf_epsilon else 1
+        if self.clip_norm == 0.0 and self.lr_decay is None:
+            check(L.hf_adam_multi(self._chunks, ptr(self._dev_table), ptr(self._dev_map), ptr(self.step_count), self.lr,
+                                  self.betas[0], self.betas[1], self.eps, self.grad_scale, mode, stream_ptr()), "adam_multi")
+            return
+        if self.clip_norm > 0.0:
+            check(L.hf_adam_sqnorm_partials(self._chunks, ptr(self._dev_table), ptr(self._dev_map), self.grad_scale,
+                                            ptr(self._partials), stream_ptr()), "adam_sqnorm_partials")
+        decay, steps, factor = 0, 1.0, 1.0
+        if self.lr_decay is not None:
+            steps, factor, staircase = self.lr_decay
+            decay = 2 if staircase else 1
+        check(L.hf_adam_multi_sched(self._chunks, ptr(self._dev_table), ptr(self._dev_map), ptr(self.step_count), ptr(self._partials),
+                                    self.clip_norm, self.lr, decay, steps, factor, self.betas[0], self.betas[1], self.eps,
+                                    self.grad_scale, mode, stream_ptr()), "adam_multi_sched")
+
+    def lr_at(self, global_step):
+        """the learning rate of the update at `global_step` (= Adam step global_step + 1), computed on the host: log lines"""
+        return lr_at(self.lr, self.lr_decay, global_step)
+
+    # ---- checkpoints ----
+    def _fingerprint(self):
+        return {"count": len(self.params), "shapes": [tuple(int(d) for d in p.shape) for p in self.params]}
+
+    def hyper_parameters(self):
+        """the settings a checkpoint records (grad_scale is not one: the exchange of the train step sets it)"""
+        return {"lr": self.lr, "betas": tuple(float(b) for b in self.betas), "eps": self.eps, "tf_epsilon": bool(self.tf_epsilon),
+                "clip_norm": self.clip_norm, "lr_decay": self.lr_decay}
+
+    def state_dict(self):
+        """copies (on the parameters' device) of the flat moments and the step counter, the hyper-parameters, the fingerprint;
+        enqueued on the current stream, no synchronisation"""
+        return {"exp_avg": self._exp_avg.detach().clone(), "exp_avg_sq": self._exp_avg_sq.detach().clone(),
+                "step_count": self.step_count.detach().clone(), "hyper_parameters": self.hyper_parameters(),
+                "fingerprint": self._fingerprint()}
+
+    def load_state_dict(self, state):
+        """copy a state_dict() into this optimizer's buffers in place (a captured step keeps reading them); ValueError when the
+        parameter list differs in count or shapes"""
+        fp, mine = state["fingerprint"], self._fingerprint()
+        if int(fp["count"]) != mine["count"] or [tuple(s) for s in fp["shapes"]] != mine["shapes"]:
+            raise ValueError("MultiTensorAdam.load_state_dict: the state holds %d tensors %s, this optimizer %d %s" % (
+                int(fp["count"]), _shape_summary(fp["shapes"]), mine["count"], _shape_summary(mine["shapes"])))
+        if state["exp_avg"].numel() != self._exp_avg.numel() or state["exp_avg_sq"].numel() != self._exp_avg_sq.numel():
+            raise ValueError("MultiTensorAdam.load_state_dict: moment buffers of the wrong length")
+        with torch.no_grad():
+            self._exp_avg.copy_(state["exp_avg"])
+            self._exp_avg_sq.copy_(state["exp_avg_sq"])
+            self.step_count.copy_(state["step_count"].reshape(()))
+        hp = state["hyper_parameters"]
+        self.lr, self.betas, self.eps, self.tf_epsilon = float(hp["lr"]), tuple(hp["betas"]), float(hp["eps"]), bool(hp["tf_epsilon"])
+        self.clip_norm, self.lr_decay = float(hp["clip_norm"]), _check_decay(hp["lr_decay"])
 
     # ---- state hand-over (graph_step.TrainStep undoes its warm-up steps with these) ----
     def snapshot(self):
@@ -133,3 +225,8 @@ class MultiTensorAdam:
         self._exp_avg.copy_(snap[0])
         self._exp_avg_sq.copy_(snap[1])
         self.step_count.copy_(snap[2])
+
+
+def _shape_summary(shapes):
+    shapes = [tuple(s) for s in shapes]
+    return "(%s%s)" % (", ".join(str(s) for s in shapes[:4]), ", ..." if len(shapes) > 4 else "")

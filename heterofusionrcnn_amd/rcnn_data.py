@@ -146,7 +146,7 @@ def read_proposals(path, name):
 
 class RcnnBatch(KD.RpnBatch):
     """device tensors of one batch (xyz, intensity, fg_mask, rpn_fts, proposals, proposal_count, gt, gt_count, image, calib,
-    status, noise) plus the host lists names / augs / p2 (original P2) / image_size (original (w, h))"""
+    status, noise) plus the host lists names / augs / p2 (original P2) / image_size (original (w, h)) and position (train mode)"""
 
     def train_inputs(self):
         """the dict graph_step.TrainStep takes with rcnn_train.rcnn_train_loss (the image in the img_fts slot, which
@@ -166,10 +166,14 @@ class KittiRcnnBatches:
 
     mode="train": endless, shuffled per epoch, aug_list default (flipping, pca_jitter).  mode="val": every frame once in split
     order, no augmentation; iterate (the last batch may be short) or call next() until StopIteration.  keep_unlabelled (val
-    only): frames without a label of the classes stay (gt_count 0; also frames without a label file)."""
+    only): frames without a label of the classes stay (gt_count 0; also frames without a label file).
+
+    Resuming (train mode): state_dict([batch.position]) and KittiRcnnBatches(..., state=...) as kitti_data.KittiRpnBatches."""
+
+    RNG_CALLS_PER_BATCH = 1      # hf_rpn_batch_image advances rng_state[1] by one
 
     def __init__(self, dataset_dir, handoff_dir, split="train", mode="train", batch=2, seed=0, aug_list=None, workers=8,
-                 classes=CLASSES, img_hw=(360, 1200), max_gt=128, rank=0, world=1, keep_unlabelled=False, device=None):
+                 classes=CLASSES, img_hw=(360, 1200), max_gt=128, rank=0, world=1, keep_unlabelled=False, device=None, state=None):
         if mode not in ("train", "val"):
             raise ValueError("mode must be 'train' or 'val'")
         self.dataset_dir, self.handoff_dir, self.mode = dataset_dir, handoff_dir, mode
@@ -189,6 +193,12 @@ class KittiRcnnBatches:
             self._queue = [self.samples[i:i + self.batch] for i in range(0, len(self.samples), self.batch)]
         if not self.samples:
             raise ValueError("no frame to load")
+        self._rng_host = [int(seed), 0]
+        if state is not None:
+            if self.list is None:
+                raise ValueError("a loader position applies to mode='train' only")
+            self.list.load_state_dict(state["samples"])
+            self._rng_host = [int(v) for v in state["rng_state"]]
         first = self.samples[0][0]
         fpath = handoff_paths(handoff_dir, first)
         if not os.path.isfile(fpath["features"]):
@@ -196,7 +206,7 @@ class KittiRcnnBatches:
         self.num_points, w = feature_shape(fpath["features"])
         self.channels = w - 5
         self.num_proposals = max(1, len(read_proposals(fpath["proposals"], first)[0]))
-        self.rng_state = torch.tensor([int(seed), 0], dtype=torch.int64, device=self.device)
+        self.rng_state = torch.tensor(self._rng_host, dtype=torch.int64, device=self.device)
         self._pool = concurrent.futures.ThreadPoolExecutor(max_workers=max(1, int(workers)))
         self._ahead = concurrent.futures.ThreadPoolExecutor(max_workers=1)
         self._staging = [KD._Staging(), KD._Staging()]
@@ -209,8 +219,16 @@ class KittiRcnnBatches:
 
     def _take(self):
         if self.list is not None:
+            self._pending_pos = self.list.position()
             return self.list.take(self.batch)
         return self._queue.pop(0) if self._queue else None
+
+    def state_dict(self, position=None):
+        """train mode: the position of the batch the next next() returns, or of a batch (batch.position), as plain host values"""
+        if self.list is None:
+            raise ValueError("a loader position applies to mode='train' only")
+        lp, rng = (self._pending_pos, self._rng_host) if position is None else position
+        return {"samples": self.list.state_dict(lp), "rng_state": [int(v) for v in rng]}
 
     def _submit(self):
         picks = self._take()
@@ -291,6 +309,8 @@ class KittiRcnnBatches:
         if self._pending is None:
             raise StopIteration
         packed, names, augs, p2, wh = self._pending.result()
+        position = (self._pending_pos, tuple(self._rng_host)) if self.list is not None else None
+        self._rng_host[1] += self.RNG_CALLS_PER_BATCH
         staging = self._staging[self._turn]
         self._turn ^= 1
         b, m, g = packed["b"], self.num_proposals, self.max_gt
@@ -310,7 +330,8 @@ class KittiRcnnBatches:
         self._status.append(status)
         return RcnnBatch(xyz=xyz, intensity=inten, fg_mask=fg, rpn_fts=fts, proposals=meta["proposals"].view(b, m, 7),
                          proposal_count=meta["proposal_count"], gt=meta["gt"].view(b, g, 8), gt_count=meta["gt_count"], image=image,
-                         calib=meta["calib"].view(b, 3, 4), status=status, noise=noise, names=names, augs=augs, p2=p2, image_size=wh)
+                         calib=meta["calib"].view(b, 3, 4), status=status, noise=noise, names=names, augs=augs, p2=p2, image_size=wh,
+                         position=position)
 
     def __iter__(self):
         while True:

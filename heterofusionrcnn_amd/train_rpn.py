@@ -2,8 +2,13 @@
 
 Batches come from kitti_data.KittiRpnBatches (device batch assembly, one batch ahead); the step is graph_step.TrainStep
 (replayed from a captured hipGraph), with the geometry of the next batch prefetched on a side stream.  Configs that fuse the
-image train RpnWithImageBranch(model, ImgVggPyr()), the reference's whole step.  Only the model's state_dict is saved:
-optim.MultiTensorAdam has no state_dict, so optimizer checkpointing is not supported.
+image train RpnWithImageBranch(model, ImgVggPyr()), the reference's whole step.  --save writes the model's state_dict.
+
+--reference-train-op runs the reference's train op (rpn_multiclass.config:204-224 train_config, hf/core/trainer.py:68-84):
+Adam with TensorFlow's epsilon, per-tensor gradient clipping at 1.0 and a staircase exponential decay (0.001 x world, 20 000
+steps, factor 0.8); a NaN / Inf loss then stops the run (check_numerics).  --checkpoint-dir writes a checkpoint (model,
+optimizer, global step, dropout counters, generator states, loader position: checkpoint.py) every --checkpoint-every steps,
+and --resume continues from the newest one up to the global step --steps.
 """
 import argparse
 import math
@@ -12,6 +17,7 @@ import time
 
 import torch
 
+from . import checkpoint as ckpt_mod
 from . import rpn as rpn_mod
 from .graph_step import TrainStep
 from .inference import CLASSES, ImgVggPyr
@@ -34,11 +40,28 @@ def make_model(config, img_conv=None):
 
 
 def train(dataset_dir, split="train", steps=100, batch=8, config="rpn_multiclass", seed=0, save=None, log_every=10, workers=8,
-          lr=1e-3, graph=True, img_conv=None, num_points=16384, log=print):
-    """-> list of the per-step losses (floats, read at the end)"""
+          lr=1e-3, graph=True, img_conv=None, num_points=16384, log=print, clip_norm=0.0, lr_decay=None, tf_epsilon=False,
+          check_numerics=False, checkpoint_dir=None, checkpoint_every=ckpt_mod.CHECKPOINT_INTERVAL, max_checkpoints=None, resume=False):
+    """-> (list of the per-step losses of this run, floats read at the end; the loader status)
+
+    clip_norm / lr_decay / tf_epsilon: optim.MultiTensorAdam's (ckpt_mod.reference_train_op() holds the reference's values);
+    check_numerics: a NaN / Inf loss raises FloatingPointError at the next log point (always before a checkpoint is written);
+    checkpoint_dir: a checkpoint every checkpoint_every global steps, the newest max_checkpoints kept; resume: continue from the
+    newest checkpoint there, `steps` then being the final global step."""
+    settings = ckpt_mod.train_op_settings(lr, lr_decay, clip_norm, tf_epsilon)
+    ck = None
+    if resume:
+        ck, path = ckpt_mod.resume_state(checkpoint_dir, config, settings)
+        log("resuming from %s (global step %d)" % (path, ck["global_step"]))
+    start = ck["global_step"] if ck else 0
+    n_steps = max(0, steps - start) if resume else steps
     torch.manual_seed(seed)
-    data = KittiRpnBatches(dataset_dir, split, CLASSES, batch=batch, num_points=num_points, seed=seed, workers=workers)
+    data = KittiRpnBatches(dataset_dir, split, CLASSES, batch=batch, num_points=num_points, seed=seed, workers=workers,
+                           state=ck["loader"] if ck else None)
     model, with_image = make_model(config, img_conv)
+    if ck:
+        model.load_state_dict(ck["model"], strict=True)
+        ckpt_mod.load_drop_states(model, ck["drop_states"])
     parts = {}
 
     def loss_fn(m, inputs, geometry):
@@ -56,22 +79,33 @@ def train(dataset_dir, split="train", steps=100, batch=8, config="rpn_multiclass
 
     steps_per_epoch = max(1, math.ceil(len(data.samples) / batch))
     cur = data.next()
-    opt = MultiTensorAdam([p for p in model.parameters() if p.requires_grad], lr=lr, tf_epsilon=False)
+    opt = MultiTensorAdam([p for p in model.parameters() if p.requires_grad], lr=lr, tf_epsilon=tf_epsilon, clip_norm=clip_norm,
+                          lr_decay=lr_decay)
+    if ck:
+        opt.load_state_dict(ck["optimizer"])
     step = TrainStep(model, opt, inputs_of(cur), model.geometry(cur.xyz), graph=graph, loss_fn=loss_fn)
+    if ck:
+        ckpt_mod.load_rng_states(ck["rng"])          # after the capture: its warm-up draws were behind the saved run too
+    keeper = ckpt_mod.Checkpointer(checkpoint_dir, checkpoint_every, max_checkpoints, config, settings, model, opt, data, start, log)
     prefetch = GeometryPrefetcher(model.geometry, depth=1)
     prefetch.submit(cur.xyz)
     losses = []
     t0 = time.perf_counter()
-    for i in range(steps):
-        nxt = data.next() if i + 1 < steps else None
+    for i in range(n_steps):
+        g = start + i + 1                            # the global step this iteration completes
+        nxt = data.next() if i + 1 < n_steps else None
         geo = prefetch.get()
         if nxt is not None:
             prefetch.submit(nxt.xyz)
         losses.append(step(geometry=geo, **inputs_of(cur)).clone())
         if log_every and (i + 1) % log_every == 0:
-            log("step %d loss %.5f seg %.5f bin %.5f reg %.5f fg %d  %.1f ms/step" % (
-                i + 1, float(losses[-1]), float(parts["segmentation"]), float(parts["bin_classification"]),
-                float(parts["regression"]), int(parts["num_foreground"]), 1e3 * (time.perf_counter() - t0) / (i + 1)))
+            if check_numerics:
+                keeper.check(losses, start + 1)
+            log("step %d loss %.5f seg %.5f bin %.5f reg %.5f fg %d  lr %.3g  %.1f ms/step" % (
+                g, float(losses[-1]), float(parts["segmentation"]), float(parts["bin_classification"]),
+                float(parts["regression"]), int(parts["num_foreground"]), opt.lr_at(g - 1), 1e3 * (time.perf_counter() - t0) / (i + 1)))
+        if keeper.due(g):
+            keeper.write(g, nxt.position if nxt is not None else None, losses, start + 1)
         if (i + 1) % steps_per_epoch == 0:
             st = data.check_status()
             if st["empty"] or st["too_many_far"]:
@@ -79,6 +113,8 @@ def train(dataset_dir, split="train", steps=100, batch=8, config="rpn_multiclass
         cur = nxt
     st = data.check_status()
     data.close()
+    if check_numerics:
+        keeper.check(losses, start + 1)
     if save:
         torch.save(model.state_dict(), save)
     out = [float(v) for v in torch.stack(losses).cpu()] if losses else []
@@ -87,9 +123,7 @@ def train(dataset_dir, split="train", steps=100, batch=8, config="rpn_multiclass
 
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m heterofusionrcnn_amd.train_rpn",
-                                 description="Train the RPN on KITTI frames (velodyne/, calib/, label_2/, image_2/ under DATASET_DIR). "
-                                             "Saves the model's state_dict only: optimizer checkpointing is not supported "
-                                             "(optim.MultiTensorAdam has no state_dict), so a resumed run restarts Adam's moments.")
+                                 description="Train the RPN on KITTI frames (velodyne/, calib/, label_2/, image_2/ under DATASET_DIR).")
     ap.add_argument("dataset_dir")
     ap.add_argument("--split", default="train", help="a list file, or NAME for NAME.txt next to or inside DATASET_DIR")
     ap.add_argument("--steps", type=int, default=100)
@@ -101,10 +135,14 @@ def main(argv=None):
     ap.add_argument("--workers", type=int, default=8, help="host threads that read and decode the files")
     ap.add_argument("--lr", type=float, default=1e-3)
     ap.add_argument("--no-graph", action="store_true", help="eager steps instead of the captured hipGraph")
+    ckpt_mod.add_train_op_arguments(ap, "rpn_multiclass.config")
     args = ap.parse_args(argv)
     losses, st = train(args.dataset_dir, args.split, args.steps, args.batch, args.config, args.seed, args.save, args.log_every,
-                       args.workers, args.lr, not args.no_graph)
-    print("done: %d steps, first loss %.5f, last loss %.5f, status %s" % (len(losses), losses[0], losses[-1], st))
+                       args.workers, graph=not args.no_graph, **ckpt_mod.train_op_kwargs(args))
+    if losses:
+        print("done: %d steps, first loss %.5f, last loss %.5f, status %s" % (len(losses), losses[0], losses[-1], st))
+    else:
+        print("done: no step left to run, status %s" % (st,))
     return 0
 
 

@@ -641,6 +641,25 @@ int hf_adam_chunk(void);
 int hf_adam_multi(int num_chunks, const hf_adam_entry *table, const int *chunk_map, const float *step, float lr, float beta1,
                   float beta2, float eps, float grad_scale, int mode, hf_stream_t stream);
 
+/* The reference's train op, slim.learning.create_train_op(..., clip_gradient_norm=1.0) on the averaged gradients
+ * (hf/core/trainer.py:68-84) with tf.train.exponential_decay (hf/builders/optimizer_builder.py:102-110), in two launches.
+ * hf_adam_sqnorm_partials: one workgroup per row of chunk_map writes partials[row] = sum over its chunk of (grad_scale g)^2 in fp64
+ * (partials: num_chunks doubles on the device; a fixed reduction order, no atomics: the same gradients give the same bits).
+ * hf_adam_multi_sched: hf_adam_multi's update with
+ *   clip_norm > 0: per-tensor tf.clip_by_norm of x = grad_scale g:  x -> (x clip_norm) / max(norm, clip_norm), norm = sqrtf(fp32 of
+ *                  the fp64 sum of the tensor's partials in row order).  chunk_map must list a tensor's chunks in consecutive rows,
+ *                  in chunk order, and be the map the partials were computed on.  clip_norm == 0: no clipping (partials unused);
+ *   decay 0: lr as given; 1: lr decay_factor^((t - 1) / decay_steps); 2 (staircase): lr decay_factor^floor((t - 1) / decay_steps),
+ *                  t = *step in fp32 (Adam step t runs at global step t - 1).  The counter is exact up to 2^24 steps.
+ * With clip_norm == 0 and decay == 0 the result equals hf_adam_multi's bit for bit.  HF_EINVAL: num_chunks < 0, clip_norm < 0,
+ * decay outside 0..2, decay_steps <= 0 or decay_factor <= 0 with decay on, a null pointer that the call needs, hf_adam_multi's
+ * checks. */
+int hf_adam_sqnorm_partials(int num_chunks, const hf_adam_entry *table, const int *chunk_map, float grad_scale, double *partials,
+                            hf_stream_t stream);
+int hf_adam_multi_sched(int num_chunks, const hf_adam_entry *table, const int *chunk_map, const float *step, const double *partials,
+                        float clip_norm, float lr, int decay, float decay_steps, float decay_factor, float beta1, float beta2, float eps,
+                        float grad_scale, int mode, hf_stream_t stream);
+
 /* ------------------------------------------------------------------ feeding a captured step */
 
 /* n (<= hf_copy_multi_max()) device-to-device copies in ONE launch: dst[i] <- src[i], bytes[i] each (the three arrays live on the
