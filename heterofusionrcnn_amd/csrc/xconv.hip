@@ -726,67 +726,191 @@ __global__ __launch_bounds__(kXcThreads) void xconv_dw_bwd_x_kernel(long long ro
 // lists of hf_index_inverse, as hf_group_point_grad_gather sums them), the dF of every neighbour slot that read it,
 //   dF[r][j][ch] = sum_k X[r][k][j] * (sum_m grad_out[r][ch*M+m] * Wd[k][ch][m]),
 // rebuilt from grad_out on the fly with the multiply / add order of xconv_dw_bwd_fw_kernel: the (rows x K x c1) gradient
-// of the gathered block is never written.  Same mapping as the forward: a lane owns a channel of the table, the waves of a
-// block walk a chunk of table rows; list entries and the X column are wave-uniform.
-template <int K, int M>
+// of the gathered block is never written.  Every table row is written once (0 where nothing names it): no atomics, no zero fill.
+// Layout (the arithmetic per element is that of the one-channel-per-lane form it replaces, so the bits are the same):
+//   - a lane owns CPL consecutive channels of the table as channel pairs (4 channels for M = 1, else 2): a wave covers a
+//     256-channel row with one 16-byte grad_out load per lane and list entry, and every product runs packed across a pair;
+//   - a wave walks kFtsRows table rows at once and takes kFtsEntries list entries of each per trip: the entries (lane reads),
+//     then the X columns and the grad_out rows of all kFtsRows * kFtsEntries slots are issued before the first sum.  Short
+//     lists (2 at the encoder layers) no longer leave a wave with one load in flight;
+//   - a trip's list entries are one load (a lane group per entry), and so are their X columns (X[r][k][j], k = 0..K-1, a lane
+//     per coefficient), staged in the wave's LDS slots and read back as broadcasts (packed products take their scalar factor from a VGPR, see XcXRows);
+//   - slots past a list's end load a clamped, valid entry and are skipped by a wave-uniform branch.
+// `VEC`: c1 is a multiple of CPL and the tensors are 16-byte aligned: a lane's CPL * M floats of grad_out and its CPL results are
+// whole 8- / 16-byte accesses, and a lane is live or dead as a whole.  Else single floats, each channel clamped and guarded.
+// grad_out and grad_fts carry no __restrict__ on purpose: with it the compiler sinks the first entry's grad_out load past the
+// LDS fence into that entry's branch, where it is issued last and waited for with every other load of the trip.
+constexpr int kFtsRows = 2, kFtsEntries = 4;
+typedef float f4 __attribute__((ext_vector_type(4)));
+
+constexpr int xc_fts_pairs(int m) { return m == 1 ? 2 : 1; }   // channel pairs per lane
+
+template <int K, int M, bool VEC>
 __global__ __launch_bounds__(kXcThreads) void xconv_dw_bwd_fts_kernel(long long src_rows, int n_src, long long rows_per_cloud,
                                                                      int c, int c0, int rows_per_block,
                                                                      const float *__restrict__ x, const float *__restrict__ wd,
-                                                                     const float *__restrict__ grad_out,
+                                                                     const float *grad_out,
                                                                      const int *__restrict__ offsets, const int *__restrict__ entries,
-                                                                     float *__restrict__ grad_fts)
+                                                                     float *grad_fts)
 {
+    constexpr int NP = xc_fts_pairs(M), CPL = 2 * NP, T = kFtsRows, E = kFtsEntries, NF = CPL * M, CHUNK = NF % 4 == 0 ? 4 : 2;
+    constexpr int KP = K <= 4 ? 4 : (K <= 8 ? 8 : 16), QPL = 64 / KP, NR = (T * E + QPL - 1) / QPL;   // X columns padded to KP floats
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
-    const int c1 = c - c0, cf = blockIdx.y * 64 + lane, ch = c0 + cf;
-    const bool live = cf < c1;
-    float w[K][M];
+    const int lq = lane / KP, lk = lane % KP < K ? lane % KP : K - 1;
+    const int c1 = c - c0, col0 = blockIdx.y * (64 * CPL), cf0 = col0 + lane * CPL;
+    unsigned cc[CPL];   // the lane's channels in grad_out / wd, clamped to valid ones
+    bool live[CPL];
+#pragma unroll
+    for (int i = 0; i < CPL; ++i) {
+        live[i] = cf0 + i < c1;
+        cc[i] = static_cast<unsigned>(c0 + (live[i] ? cf0 + i : (VEC ? col0 + i : c1 - 1)));
+    }
+    f2 w[K][NP][M];
 #pragma unroll
     for (int k = 0; k < K; ++k)
 #pragma unroll
-        for (int m = 0; m < M; ++m) w[k][m] = live ? wd[(static_cast<size_t>(k) * c + ch) * M + m] : 0.f;
+        for (int p = 0; p < NP; ++p)
+#pragma unroll
+            for (int m = 0; m < M; ++m)
+                w[k][p][m] = f2{wd[(static_cast<size_t>(k) * c + cc[2 * p]) * M + m], wd[(static_cast<size_t>(k) * c + cc[2 * p + 1]) * M + m]};
+    __shared__ __attribute__((aligned(16))) float xs[kXcThreads / 64][T * E][KP];
     const long long s0 = static_cast<long long>(blockIdx.x) * rows_per_block;
     const long long s1 = s0 + rows_per_block < src_rows ? s0 + rows_per_block : src_rows;
     long long bb = s0 / n_src;
-    for (long long s = s0 + wave; s < s1; s += kXcThreads / 64) {
-        while (s >= (bb + 1) * n_src) ++bb;
-        const int pt = static_cast<int>(s - bb * n_src);
-        const int *off = offsets + bb * (n_src + 1);
-        const int *ent = entries + bb * rows_per_cloud * K;
-        const int lo = off[pt], hi = off[pt + 1];
-        float acc = 0.f;
-        // four list entries per trip: their loads are issued together (a dependent scalar load -> row -> vector load chain per
-        // entry kept one load in flight per wave); summed in list order, slots past the end add zero
-        for (int e = lo; e < hi; e += 4) {
-            float a4[4];
+    for (long long sb = s0 + wave * T; sb < s1; sb += (kXcThreads / 64) * T) {
+        int pos[T], hi[T];
+        long long ebase[T];
+        unsigned rbase[T];
+        f2 acc[T][NP];
+        bool more = false;
 #pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const bool valid = e + u < hi;
-                const int slot = ent[valid ? e + u : lo];
-                const long long r = bb * rows_per_cloud + slot / K;
-                const int j = slot % K;
-                const float *xr = x + r * (K * K);
-                float g[M], gfx[K];
-                load_m<M>(grad_out, static_cast<size_t>(r * c + (live ? ch : 0)) * M, g);
-                if (!live) {
+        for (int t = 0; t < T; ++t) {
+            const long long s = sb + t < s1 ? sb + t : s1 - 1;
+            while (s >= (bb + 1) * n_src) ++bb;
+            const int pt = static_cast<int>(s - bb * n_src);
+            const int *off = offsets + bb * (n_src + 1);
+            ebase[t] = bb * rows_per_cloud * K;
+            rbase[t] = static_cast<unsigned>(bb * rows_per_cloud);
+            pos[t] = off[pt];
+            hi[t] = sb + t < s1 ? off[pt + 1] : pos[t];   // a row past the block's end: an empty list, not stored
+            more = more || pos[t] < hi[t];
 #pragma unroll
-                    for (int m = 0; m < M; ++m) g[m] = 0.f;
+            for (int p = 0; p < NP; ++p) acc[t][p] = f2{0.f, 0.f};
+        }
+        // lane l takes coefficient l % KP of entry l / KP: one load fetches 64 / KP list entries, a second one their X columns;
+        // the entries reach the scalar side by lane reads.  The next trip's entries are loaded behind this trip's grad_out rows.
+        auto load_slots = [&](int ahead, unsigned (&slot)[NR]) {
+#pragma unroll
+            for (int i = 0; i < NR; ++i) {
+                const int q = i * QPL + lq < T * E ? i * QPL + lq : T * E - 1, u = q % E + ahead;
+                int e = 0;
+                long long eb = 0;
+#pragma unroll
+                for (int t = 0; t < T; ++t)
+                    if (q / E == t) { e = pos[t] + u < hi[t] ? pos[t] + u : 0; eb = ebase[t]; }
+                slot[i] = static_cast<unsigned>(entries[eb + e]);
+            }
+        };
+        unsigned slot[NR], slot_next[NR];
+        if (more) load_slots(0, slot);
+        while (more) {
+            unsigned rr[T * E];   // the entries' rows (fewer than 2^31, checked by the entry point)
+            float xv[NR];
+#pragma unroll
+            for (int i = 0; i < NR; ++i) {
+                const int q = i * QPL + lq < T * E ? i * QPL + lq : T * E - 1;
+                unsigned rb = 0;
+#pragma unroll
+                for (int t = 0; t < T; ++t)
+                    if (q / E == t) rb = rbase[t];
+                xv[i] = x[static_cast<size_t>(rb + slot[i] / K) * (K * K) + lk * K + slot[i] % K];
+#pragma unroll
+                for (int j = 0; j < QPL; ++j) {
+                    const int qj = i * QPL + j;
+                    if (qj < T * E) rr[qj] = rbase[qj / E] + static_cast<unsigned>(__builtin_amdgcn_readlane(static_cast<int>(slot[i]), j * KP)) / K;
                 }
+            }
+            f2 g[T * E][NP][M];
 #pragma unroll
-                for (int k = 0; k < K; ++k) {
-                    float a = 0.f;
+            for (int q = 0; q < T * E; ++q) {
+                const float *gp = grad_out + static_cast<size_t>(rr[q]) * c * M;
+                if constexpr (VEC) {
+                    float flat[NF];
 #pragma unroll
-                    for (int m = 0; m < M; ++m) a = a + g[m] * w[k][m];
-                    gfx[k] = a;
+                    for (int i = 0; i < NF / CHUNK; ++i) {
+                        if constexpr (CHUNK == 4) {
+                            const f4 v = *reinterpret_cast<const f4 *>(gp + cc[0] * M + 4 * i);
+                            flat[4 * i] = v.x; flat[4 * i + 1] = v.y; flat[4 * i + 2] = v.z; flat[4 * i + 3] = v.w;
+                        } else {
+                            const f2 v = *reinterpret_cast<const f2 *>(gp + cc[0] * M + 2 * i);
+                            flat[2 * i] = v.x; flat[2 * i + 1] = v.y;
+                        }
+                    }
+#pragma unroll
+                    for (int p = 0; p < NP; ++p)
+#pragma unroll
+                        for (int m = 0; m < M; ++m) g[q][p][m] = f2{flat[2 * p * M + m], flat[(2 * p + 1) * M + m]};
+                } else {
+#pragma unroll
+                    for (int p = 0; p < NP; ++p)
+#pragma unroll
+                        for (int m = 0; m < M; ++m) g[q][p][m] = f2{gp[cc[2 * p] * M + m], gp[cc[2 * p + 1] * M + m]};
                 }
-                float a = xr[j] * gfx[0];
+            }
+            load_slots(E, slot_next);
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");   // the previous trip's reads are done
+            __builtin_amdgcn_wave_barrier();
 #pragma unroll
-                for (int k = 1; k < K; ++k) a = a + xr[k * K + j] * gfx[k];
-                a4[u] = valid ? a : 0.f;
+            for (int i = 0; i < NR; ++i) xs[wave][i * QPL + lq < T * E ? i * QPL + lq : T * E - 1][lane % KP] = xv[i];
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            more = false;
+#pragma unroll
+            for (int t = 0; t < T; ++t) {
+#pragma unroll
+                for (int u = 0; u < E; ++u) {
+                    const int q = t * E + u;
+                    if (pos[t] + u >= hi[t]) continue;
+                    const float *xr = xs[wave][q];
+#pragma unroll
+                    for (int p = 0; p < NP; ++p) {
+                        f2 gfx[K];
+#pragma unroll
+                        for (int k = 0; k < K; ++k) {
+                            f2 a = f2{0.f, 0.f};
+#pragma unroll
+                            for (int m = 0; m < M; ++m) a = a + g[q][p][m] * w[k][p][m];
+                            gfx[k] = a;
+                        }
+                        f2 a = xr[0] * gfx[0];
+#pragma unroll
+                        for (int k = 1; k < K; ++k) a = a + xr[k] * gfx[k];
+                        acc[t][p] = acc[t][p] + a;
+                    }
+                }
+                pos[t] += E;
+                more = more || pos[t] < hi[t];
             }
 #pragma unroll
-            for (int u = 0; u < 4; ++u) acc += a4[u];
+            for (int i = 0; i < NR; ++i) slot[i] = slot_next[i];
         }
-        if (live) grad_fts[s * c1 + cf] = acc;
+#pragma unroll
+        for (int t = 0; t < T; ++t) {
+            if (sb + t >= s1) break;
+            float *dst = grad_fts + static_cast<size_t>(sb + t) * c1 + cf0;
+            if constexpr (VEC) {
+                if (live[0]) {
+                    if constexpr (NP == 2) *reinterpret_cast<f4 *>(dst) = f4{acc[t][0].x, acc[t][0].y, acc[t][1].x, acc[t][1].y};
+                    else *reinterpret_cast<f2 *>(dst) = acc[t][0];
+                }
+            } else {
+#pragma unroll
+                for (int p = 0; p < NP; ++p) {
+                    if (live[2 * p]) dst[2 * p] = acc[t][p].x;
+                    if (live[2 * p + 1]) dst[2 * p + 1] = acc[t][p].y;
+                }
+            }
+        }
     }
 }
 
@@ -1080,6 +1204,45 @@ HF_API int hf_xconv_depthwise_gather(int b, int n_src, int rows_per_cloud, int k
     return xdw_forward(rows, k, c0 + c1, c0, m, x, f_delta, fts, idx, n_src, rows_per_cloud, wd, out, as_stream(stream));
 }
 
+// Which route computes the feature table's gradient when a workspace is given: true = rebuilt per table row
+// (xconv_dw_bwd_fts_kernel; the staging region of the workspace is never touched), false = staged in the workspace by
+// xconv_dw_bwd_fw_kernel and summed by hf_group_point_grad_gather.  Direct reads k x (rows x c1 x m) floats of grad_out, mostly from
+// the cache; staged writes and reads rows x k x c1.  Measured per shape as xconv_dw_bwd_fw_kernel + the table's kernel, direct
+// against staged, us (scripts/probes/xconv_table_grad_timing.py, profiles/r06_xconv_table_grad_timing.txt):
+//   lists of 8 and more: direct wins at every size -- 8 frames dec5 617 / 895, dec4 598 / 910, dec3 313 / 456, dec2 171 / 220,
+//     dec1 66 / 72, dec0 33 / 38; one frame dec5 94 / 103 ... dec0 25 / 29
+//   short lists (2 .. 4), where a wave has little in flight per table row:
+//     staged block of 8 MiB and less (one frame's encoder, all latency): direct, one launch fewer -- 31 / 33, 27 / 30, 22 / 26
+//     m <= 2 and a block well past the caches: direct -- m = 1: enc1 at 8 frames (268 MB) 183 / 253, the RCNN's second layer at
+//       128 / 512 RoIs (268 MB / 1.07 GB) 190 / 244, 710 / 943, its fourth at 512 RoIs (201 MB) 254 / 310; m = 2: its third
+//       (101 / 403 MB) 157 / 193, 502 / 746
+//     otherwise staged -- m = 1 at 17 .. 50 MB 36 / 33, 48 / 40, 87 / 74; m = 2 at 34 and 67 MB (enc3, enc2) 53 / 46, 82 / 72;
+//       m = 4, where grad_out is four times the block (the RCNN's first layer, k 4, 570 MB / 2.3 GB) 672 / 592, 3010 / 2345
+//   the 80 MiB lies between the largest block where staging won (64 MiB) and the smallest where it lost (96 MiB)
+static bool xdw_fts_direct(long long rows, int n_src, int rows_per_cloud, int k, int c1, int m)
+{
+    if (static_cast<long long>(rows_per_cloud) * k >= 8ll * n_src) return true;
+    const long long staged = rows * k * c1 * static_cast<long long>(sizeof(float));
+    return staged <= (8ll << 20) || (m <= 2 && staged >= (80ll << 20));
+}
+
+// rows = b * rows_per_cloud stays below 2^31 (checked by the entry point): the kernel keeps a list entry's row in 32 bits
+static int xdw_table_grad(long long src_rows, int n_src, int rows_per_cloud, int k, int c, int c0, int m, const float *x, const float *wd,
+                          const float *grad_out, const int *offsets, const int *entries, float *grad_fts, hipStream_t st)
+{
+    const int c1 = c - c0, cpl = 2 * xc_fts_pairs(m);
+    dim3 grid;
+    int rpb;
+    xdw_grid(src_rows, c1, grid, rpb, 8, 64 * cpl);
+    const bool vec = c1 % cpl == 0 && ((reinterpret_cast<uintptr_t>(grad_out) | reinterpret_cast<uintptr_t>(grad_fts)) & 15) == 0;
+#define HF_XDW_FTS_V(KK, MM, V) hipLaunchKernelGGL((xconv_dw_bwd_fts_kernel<KK, MM, V>), grid, dim3(kXcThreads), 0, st, src_rows, n_src, static_cast<long long>(rows_per_cloud), c, c0, rpb, x, wd, grad_out, offsets, entries, grad_fts);
+#define HF_XDW_FTS(KK, MM) if (vec) { HF_XDW_FTS_V(KK, MM, true) } else { HF_XDW_FTS_V(KK, MM, false) }
+    HF_XDW_DISPATCH(HF_XDW_FTS)
+#undef HF_XDW_FTS
+#undef HF_XDW_FTS_V
+    return launch_status();
+}
+
 // [gradient of the gathered block: rows x k x c1][partial depthwise-weight gradients: row chunks x k x (c0+c1) x m]
 static size_t xdw_gathered_bytes(int b, int rows_per_cloud, int k, int c1)
 {
@@ -1108,30 +1271,27 @@ HF_API int hf_xconv_depthwise_gather_grad(int b, int n_src, int rows_per_cloud, 
     if (grad_fts && (!offsets || !entries)) return HF_EINVAL;
     if (workspace && workspace_bytes < hf_xconv_depthwise_gather_grad_workspace(b, rows_per_cloud, k, c0, c1, m)) return HF_EWORKSPACE;
     hipStream_t st = as_stream(stream);
-    const long long rows = static_cast<long long>(b) * rows_per_cloud;
+    const long long rows = static_cast<long long>(b) * rows_per_cloud, src_rows = static_cast<long long>(b) * n_src;
     const int c = c0 + c1;
-    // with a workspace the gathered block's gradient is written once (rows x k x c1) and summed per table row by
-    // hf_group_point_grad_gather (240 us + 230 us of extra writes at the last decoder layer); without one it is rebuilt per
-    // table row from grad_out (no extra memory, 890 us there)
-    float *gathered = (grad_fts && workspace) ? static_cast<float *>(workspace) : nullptr;
+    // The table's gradient is rebuilt per table row from grad_out (xconv_dw_bwd_fts_kernel: nothing but the table is written), or,
+    // where xdw_fts_direct says so and a workspace is there, staged: xconv_dw_bwd_fw_kernel writes the gathered block's gradient
+    // (rows x k x c1) into the workspace and hf_group_point_grad_gather sums it per table row.  The partial weight gradients go
+    // through the workspace on both routes.
+    const bool want_fts = grad_fts && src_rows > 0 && rows > 0;
+    bool direct = want_fts && (!workspace || xdw_fts_direct(rows, n_src, rows_per_cloud, k, c1, m));
+    if (want_fts && workspace && HF_DIAG_INT("HF_XDW_FTS_ROUTE", 0) != 0) direct = HF_DIAG_INT("HF_XDW_FTS_ROUTE", 0) == 2;   // 1: staged, 2: direct
+    float *gathered = (want_fts && !direct) ? static_cast<float *>(workspace) : nullptr;
     float *wd_partial = workspace ? reinterpret_cast<float *>(static_cast<unsigned char *>(workspace) + xdw_gathered_bytes(b, rows_per_cloud, k, c1)) : nullptr;
+    if (grad_fts && src_rows > 0 && rows == 0) {
+        const int rc = hip_status(hipMemsetAsync(grad_fts, 0, sizeof(float) * static_cast<size_t>(src_rows) * c1, st));
+        if (rc != HF_OK) return rc;
+    }
     if (grad_x || grad_f_delta || grad_wd || gathered) {
         const int rc = xdw_backward(rows, k, c, c0, m, x, f_delta, fts, idx, n_src, rows_per_cloud, wd, grad_out, grad_x, grad_f_delta, gathered,
                                     grad_wd, st, wd_partial);
         if (rc != HF_OK) return rc;
     }
-    if (grad_fts) {
-        const long long src_rows = static_cast<long long>(b) * n_src;
-        if (src_rows == 0) return HF_OK;
-        if (rows == 0) return hip_status(hipMemsetAsync(grad_fts, 0, sizeof(float) * static_cast<size_t>(src_rows) * c1, st));
-        if (gathered) return hf_group_point_grad_gather(b, n_src, c1, rows_per_cloud, k, c1, 0, gathered, offsets, entries, grad_fts, stream);
-        dim3 grid;
-        int rpb;
-        xdw_grid(src_rows, c1, grid, rpb);
-#define HF_XDW_FTS(KK, MM) hipLaunchKernelGGL((xconv_dw_bwd_fts_kernel<KK, MM>), grid, dim3(kXcThreads), 0, st, src_rows, n_src, static_cast<long long>(rows_per_cloud), c, c0, rpb, x, wd, grad_out, offsets, entries, grad_fts);
-        HF_XDW_DISPATCH(HF_XDW_FTS)
-#undef HF_XDW_FTS
-        return launch_status();
-    }
+    if (gathered) return hf_group_point_grad_gather(b, n_src, c1, rows_per_cloud, k, c1, 0, gathered, offsets, entries, grad_fts, stream);
+    if (direct) return xdw_table_grad(src_rows, n_src, rows_per_cloud, k, c, c0, m, x, wd, grad_out, offsets, entries, grad_fts, st);
     return HF_OK;
 }
