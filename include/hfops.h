@@ -367,7 +367,8 @@ int hf_linear_elu_bn_bwd(long long rows, int cout, int cin, const float *dz, con
  * while it stages its operand.  w0 (c0, 3), w1 (c1, c0); batch statistics and running estimates of both layers are produced.
  * hf_lift_elu_bn_bwd: from dz1 (rows, c1) = the gradient w.r.t. z1: grad_w1 (c1, c0), dgamma0 / dbeta0 (c0), and grad_w0_t (3, c0) =
  * the TRANSPOSE of the first layer's weight gradient; dy0 = dz1 W1 (w1_t = W1^T as (c0, c1)) is rebuilt in the accumulators of
- * two passes and never written.  c0 <= 160 (a multiple of 4), c1 <= 256. */
+ * two passes and never written.  c0 a multiple of 4, c1 <= 256, w1 16-byte aligned (it is read four floats at a time);
+ * c0 <= 256 for hf_lift_elu_bn_fwd and the two inference forms below, c0 <= 160 for hf_lift_elu_bn_bwd.  Anything else is HF_EINVAL. */
 size_t hf_lift_elu_bn_fwd_workspace(int c0, int c1);
 int hf_lift_elu_bn_fwd(long long rows, int c0, int c1, const float *x3, const float *w0, const float *gamma0, const float *beta0,
                        float eps0, float momentum0, float *running_mean0, float *running_var0, float *mean0, float *invstd0,
@@ -418,7 +419,8 @@ int hf_bn_relu_bwd_dx(long long rows, int c, const float *x, const float *dy, co
  * from (dy, z, gamma, beta, mean, invstd, dgamma, dbeta) while it is staged (and stored to dz_out if given); z == NULL:
  * the first operand is dz itself.  z_prev != NULL: dgamma / dbeta of the layer below (p_*: its parameters and
  * statistics, z_prev (rows, cin) its pre-BN output) are reduced from the accumulators into p_dgamma / p_dbeta.
- * dx may be NULL when only dz_out / the sums are wanted.  cin <= 256, cout <= 256 with z. */
+ * dx may be NULL when only dz_out / the sums are wanted.  cin <= 256; cout <= 256 with z, no limit on cout without z
+ * (hf_linear_elu_bn_bwd takes no z: cin <= 256 only). */
 size_t hf_linear_bn_bwd_workspace(int cin);
 int hf_linear_bn_bwd(long long rows, int cout, int cin, const float *dy_or_dz, const float *z, const float *gamma,
                      const float *beta, const float *mean, const float *invstd, const float *dgamma, const float *dbeta,
