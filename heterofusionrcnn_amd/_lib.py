@@ -84,6 +84,9 @@ _SIGNATURES = {
     "hf_linear_bn_fwd_gather": [ctypes.c_longlong, _i, _i, _vp, _i, ctypes.c_longlong, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp,
                                 _vp, _sz, _vp],
     "hf_linear_wgrad_gather": [ctypes.c_longlong, _i, _i, _vp, _vp, _i, ctypes.c_longlong, _vp, _vp, _vp, _vp, _sz, _vp],
+    "hf_linear_bn_fwd_interp": [ctypes.c_longlong, _i, _i, _i, _vp, _i, ctypes.c_longlong, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp,
+                                _vp, _vp, _sz, _vp],
+    "hf_linear_wgrad_interp": [ctypes.c_longlong, _i, _i, _i, _vp, _vp, _i, ctypes.c_longlong, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
     "hf_adam_chunk": [],
     "hf_adam_multi": [_i, _vp, _vp, _vp, _f, _f, _f, _f, _f, _i, _vp],
     "hf_adam_sqnorm_partials": [_i, _vp, _vp, _f, _vp, _vp],

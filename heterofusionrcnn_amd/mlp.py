@@ -560,6 +560,136 @@ def shared_mlp_grouped(layers, points, idx, grouped_xyz, xyz_first=True, pool=Tr
     return _shared_mlp_eval(layers, z0, k if pool else 0, 0, first_done=True)
 
 
+class _InterpLinear(torch.autograd.Function):
+    """z0 = [three_interpolate(points2, idx, weight3) | points1] W^T + b with the batch statistics of z0, the three_nn rows read
+    IN PLACE (hf_linear_bn_fwd_interp / hf_linear_wgrad_interp): the (B,N,C2+C1) concat of pointnet_fp_module
+    (pointnet_util.py:311-313) is never written, neither for the forward GEMM nor for the weight gradient.  The operand's column
+    order is the concat's own, so the weight is only zero-padded to a multiple of 4 columns.  Returns (z0, mean, invstd); the
+    BatchNorm that consumes them is the head of _SharedMLPChain (first=...).  offsets / entries: three_nn_inverse(idx, M), needed
+    for the gradient of points2 only (gather form: deterministic, in the reference loop's order)."""
+
+    @staticmethod
+    def forward(ctx, points2, points1, idx, weight3, offsets, entries, weight, bias, bn, update_running):
+        L = _lib.lib()
+        b, n, _ = idx.shape
+        m, c2 = points2.shape[1], points2.shape[2]
+        c1 = points1.shape[2] if points1 is not None else 0
+        rows, cout = b * n, weight.shape[0]
+        cin = (c2 + c1 + 3) // 4 * 4
+        dev = idx.device
+        wp = torch.nn.functional.pad(weight.detach(), (0, cin - c2 - c1)) if cin != c2 + c1 else weight.detach().contiguous()
+        z = torch.empty((rows, cout), dtype=torch.float32, device=dev)
+        mean = torch.empty((cout,), dtype=torch.float32, device=dev)
+        invstd = torch.empty((cout,), dtype=torch.float32, device=dev)
+        nbytes = L.hf_linear_bn_fwd_workspace(cout)
+        ws = torch.empty((nbytes // 4,), dtype=torch.float32, device=dev)
+        if update_running:
+            running_stats_written()
+        check(L.hf_linear_bn_fwd_interp(rows, c2, c1, cout, ptr(points2), m, n, ptr(idx), ptr(weight3), ptr(points1), ptr(wp), ptr(bias),
+                                        ptr(z), bn.eps, bn.momentum, ptr(bn.running_mean) if update_running else None,
+                                        ptr(bn.running_var) if update_running else None, ptr(mean), ptr(invstd), ptr(ws), nbytes,
+                                        stream_ptr()), "linear_bn_fwd_interp")
+        ctx.save_for_backward(points2, idx, weight3, wp, *([points1] if points1 is not None else []),
+                              *([offsets, entries] if offsets is not None else []))
+        ctx.dims = (b, n, m, c2, c1, cout, cin, points1 is not None, offsets is not None)
+        ctx.mark_non_differentiable(mean, invstd)
+        return z, mean, invstd
+
+    @staticmethod
+    def backward(ctx, dz, _dmean, _dinvstd):
+        L = _lib.lib()
+        b, n, m, c2, c1, cout, cin, has_skip, has_inverse = ctx.dims
+        points2, idx, weight3, wp, *rest = ctx.saved_tensors
+        points1 = rest.pop(0) if has_skip else None
+        rows = b * n
+        dz = dz.contiguous()
+        dw = None
+        if ctx.needs_input_grad[6]:
+            nbytes = L.hf_linear_wgrad_workspace(rows, cout, cin)
+            ws = torch.empty((nbytes // 4,), dtype=torch.float32, device=dz.device)
+            dwp = torch.empty((cout, cin), dtype=torch.float32, device=dz.device)
+            check(L.hf_linear_wgrad_interp(rows, cout, c2, c1, ptr(dz), ptr(points2), m, n, ptr(idx), ptr(weight3), ptr(points1), ptr(dwp),
+                                           ptr(ws), nbytes, stream_ptr()), "linear_wgrad_interp")
+            dw = dwp[:, :c2 + c1].contiguous() if cin != c2 + c1 else dwp
+        need2, need1 = ctx.needs_input_grad[0], has_skip and ctx.needs_input_grad[1]
+        dp2 = dp1 = None
+        if need2 or need1:
+            # the gradient of the operand, once for both sources: dz0 @ W[:, :c2 + c1], kept at the padded width (the weight's
+            # padding columns are zero) so that the gather below reads it in 16-byte pieces
+            da = dz @ wp
+            if need2:
+                if not has_inverse:
+                    raise RuntimeError("_InterpLinear: the gradient of points2 needs the inverse index (three_nn_inverse)")
+                offsets, entries = rest
+                dp2 = torch.empty((b, m, c2), dtype=torch.float32, device=dz.device)
+                check(L.hf_three_interpolate_concat_grad(b, n, c2, m, da.shape[1], ptr(da), ptr(weight3), ptr(offsets), ptr(entries),
+                                                         ptr(dp2), stream_ptr()), "three_interpolate_concat_grad")
+            if need1:
+                dp1 = da.view(b, n, -1)[:, :, c2:c2 + c1]
+        # the bias feeds a BatchNorm: its gradient is exactly zero (see _SharedMLPChain.backward)
+        dbias = torch.zeros((cout,), dtype=torch.float32, device=dz.device) if ctx.needs_input_grad[7] else None
+        return dp2, dp1, None, None, None, None, dw, dbias, None, None
+
+
+INTERP_MAX_COUT = 256           # accumulator tiles of the MFMA forward kernel
+INTERP_MAX_C = 1024             # each of c2 and c1 (hf_linear_bn_fwd_interp)
+
+
+def interp_route_pays(rows, cin, cout, training):
+    """Where modules.PointnetFPModule takes shared_mlp_interp by default (cin = C2 + C1 of the first layer).  Always: the layer's
+    GEMM already ran on the MFMA forward kernel (_mfma_forward_pays), so only the source of its operand changes.  In training the
+    route also replaces the layer's weight gradient by the MFMA chunk kernel, and that pays only where the materialised route ran
+    that kernel too (_splitk_wgrad: results up to 128 x 128, up to 2^18 rows); wider results go to the library's batched split there,
+    which is faster than the chunk kernel by more than the concat traffic costs.  Measured, forward + backward, B = 8
+    (scripts/probes/fp_interp_timing.py, profiles/fp_interp_timing.json; materialised / in place, us): 131072 rows 257 -> 128:
+    955 / 1090 (forward alone 353 / 303); 32768 rows 320 -> 256: 602 / 695; 32768 rows 608 -> 256: 738 / 892 -- all three lose in
+    training and are excluded here; at inference the finest level (the only one within Cout <= 224) takes the route."""
+    if not _mfma_forward_pays(rows, cin, cout):
+        return False
+    return not training or (rows <= (1 << 18) and cout * ((cin + 3) // 4 * 4) <= 128 * 128)
+
+
+def interp_mlp_fusable(layers, points2, points1, idx):
+    """shared_mlp_interp's conditions: BatchNorm + ReLU on every layer, fp32 tensors on the device, the first layer within the
+    kernels' range (Cout <= 256, 1 <= C2 <= 1024, C1 <= 1024) and sized for the concat [interpolated | points1]"""
+    layers = list(layers)
+    first = layers[0]
+    c2 = points2.shape[2]
+    c1 = points1.shape[2] if points1 is not None else 0
+    tensors = [points2, idx] + ([points1] if points1 is not None else [])
+    return (all(t.is_cuda for t in tensors) and points2.dtype == torch.float32 and (points1 is None or points1.dtype == torch.float32)
+            and idx.dtype == torch.int32 and all(l.bn is not None and l.bn.relu for l in layers)
+            and first.fc.out_features <= INTERP_MAX_COUT and 1 <= c2 <= INTERP_MAX_C and c1 <= INTERP_MAX_C
+            and first.fc.in_features == c2 + c1)
+
+
+def shared_mlp_interp(layers, points2, points1, idx, weight, inverse):
+    """The MLP of a feature-propagation level on three_nn rows read in place (pointnet_util.py:303-329 as one chain):
+    points2 (B,M,C2) sparse features, points1 (B,N,C1) skip features or None, idx / weight (B,N,3) from three_nn and
+    three_nn_weights, inverse = three_nn_inverse(idx, M) (may be None when points2 needs no gradient) -> (B*N, Cout).
+    The first layer interpolates and concatenates while it stages its operand; the rest is shared_mlp's chain."""
+    layers = list(layers)
+    _on_gpu(points2, points1, idx, weight)
+    points2 = points2.contiguous()
+    points1 = points1.contiguous() if points1 is not None else None
+    idx = idx.contiguous()
+    weight = weight.detach().contiguous()
+    offsets, entries = (t.contiguous() for t in inverse) if inverse is not None else (None, None)
+    first = layers[0]
+    if all(l.bn.training for l in layers) and torch.is_grad_enabled():
+        z0, mean0, invstd0 = _InterpLinear.apply(points2, points1, idx, weight, offsets, entries, first.fc.weight, first.fc.bias,
+                                                 first.bn, True)
+        params = []
+        for l in layers:
+            params += [l.fc.weight, l.fc.bias, l.bn.weight, l.bn.bias]
+        return _SharedMLPChain.apply(z0, 0, layers, (mean0, invstd0), *params)
+    assert not any(l.bn.training for l in layers), "shared_mlp_interp: training-mode BatchNorm needs autograd enabled (or call .eval())"
+    # inference: running statistics; the first layer still reads in place (its batch statistics are simply not used)
+    with torch.no_grad():
+        z0, _, _ = _InterpLinear.apply(points2, points1, idx, weight, None, None, first.fc.weight, first.fc.bias, first.bn, False)
+        return _shared_mlp_eval(layers, z0, 0, 0, first_done=True)
+
+
 def shared_mlp(layers, x, pool_k=0):
     """x (R, Cin) through `layers` (SharedMLPLayer-like: .fc, .bn with relu) -> (R, Cout), or (R / pool_k, Cout) with
     the max over each run of pool_k rows.  One fused node in training when every layer has BN+ReLU (each layer on

@@ -23,11 +23,15 @@ from .grouping import group_concat, group_point, knn_point, query_ball_group, qu
 from .interpolate import (INVERSE_MAX_KNOWN, three_interpolate, three_interpolate_concat, three_nn,
                           three_nn_inverse)
 from .sampling import farthest_point_sample, gather_point
-from .mlp import GATHER_MIN_CFEAT, BatchNormReLU, grouped_mlp_fusable, linear_bn_relu, shared_mlp, shared_mlp_grouped
+from .mlp import (GATHER_MIN_CFEAT, BatchNormReLU, grouped_mlp_fusable, interp_mlp_fusable, interp_route_pays, linear_bn_relu, shared_mlp,
+                  shared_mlp_grouped, shared_mlp_interp)
 
 # the first layer of a set-abstraction MLP gathers its operand in place (mlp.shared_mlp_grouped); False keeps the
 # materialised group_concat route (tests compare the two)
 GATHER_ON_LOAD = True
+# the first layer of a feature-propagation MLP interpolates and concatenates its operand in place (mlp.shared_mlp_interp); False
+# keeps the materialised three_interpolate_concat route (tests compare the two)
+INTERP_ON_LOAD = True
 from .bev_iou import compute_bev_iou as _compute_bev_iou, oriented_nms as _oriented_nms
 
 
@@ -284,8 +288,25 @@ class PointnetFPModule(nn.Module):
             inverse = three_nn_inverse(idx, m) if m <= INVERSE_MAX_KNOWN else None
             return idx, three_nn_weights(dist), inverse
 
+    def _interp_on_load(self, points1, points2, idx, inverse):
+        """The in-place route is taken where mlp.interp_route_pays says so (the first layer's GEMM, and in training its weight
+        gradient, already ran on the MFMA kernels: only the source of the operand changes), in training under the condition of
+        the concat route (the inverse index exists), at inference without autograd"""
+        if not (INTERP_ON_LOAD and points2.is_cuda and interp_mlp_fusable(self.mlp, points2, points1, idx)):
+            return False
+        first, rows = self.mlp[0].fc, idx.shape[0] * idx.shape[1]
+        if self.training and torch.is_grad_enabled():
+            return (inverse is not None and all(l.bn.training for l in self.mlp)
+                    and interp_route_pays(rows, first.in_features, first.out_features, True))
+        return (not torch.is_grad_enabled() and not any(l.bn.training for l in self.mlp)
+                and interp_route_pays(rows, first.in_features, first.out_features, False))
+
     def forward(self, xyz1, xyz2, points1, points2, geom=None):
         idx, weight, inverse = geom if geom is not None else self.geometry(xyz1, xyz2)
+        if self._interp_on_load(points1, points2, idx, inverse):
+            # SURVEY 8f rank 2, FP half: three_nn -> interpolate -> concat -> MLP as one chain; the (B,N,C2+C1) tensor of
+            # pointnet_util.py:311-313 is never written (the first layer reads points2 and points1 in place)
+            return shared_mlp_interp(self.mlp, points2, points1, idx, weight, inverse).reshape(idx.shape[0], idx.shape[1], -1)
         if inverse is not None and self.training and torch.is_grad_enabled():
             # [interpolated, skip] rows written once, padded to a multiple of 4 columns (shared_mlp pads the weight)
             new_points = three_interpolate_concat(points2, points1, idx, weight, inverse)

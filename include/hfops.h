@@ -626,6 +626,32 @@ int hf_linear_wgrad_gather(long long rows, int cout, int c_feat, const float *gr
                            long long rows_per_cloud, const int *idx, const float *grouped_xyz, float *grad_weight,
                            void *workspace, size_t workspace_bytes, hf_stream_t stream);
 
+/* The FIRST layer of a feature-propagation MLP on three_nn rows read in place (the FP twin of the block
+ * above): pointnet_fp_module (hf/core/feature_extractors/pointnet_util.py:303-329) materialises [interpolated | points1] (B,N,C2+C1)
+ * and the first tf_util.conv2d reads it back; here the operand rows are assembled from (points2, idx, weight3, skip) while they
+ * are staged for the MFMA tiles, so that tensor never exists -- neither for the forward GEMM nor for the weight gradient.
+ * rows = B*N, rows_per_cloud = N, points2 (B,m,c2), idx / weight3 (rows,3) = three_nn's indices (into the row's own cloud; a
+ * value outside [0, m) is clamped) and the interpolation weights, skip (rows,c1) = points1, NULL when c1 == 0.
+ * Column layout of the assembled operand = the rows of hf_three_interpolate_concat, which `weight` (cout, cin) / `grad_weight`
+ * follow (the layer's own weight, zero-padded to cin columns; the padding columns of grad_weight are written as zero):
+ *   [ interp 0 .. c2-1 | skip 0 .. c1-1 | zeros up to cin = round_up(c2 + c1, 4) ]
+ *   interp j = weight3[r][0] * points2[cloud, idx[r][0], j] + weight3[r][1] * points2[cloud, idx[r][1], j] + weight3[r][2] * ...
+ * summed left to right without contraction: the bits hf_three_interpolate_concat writes.  16-byte loads where c2 % 4 == 0 and
+ * points2 is 16-byte aligned (for the skip part: c1 % 4 == 0 and skip aligned as well), single columns otherwise.
+ * Otherwise as hf_linear_bn_fwd_gather / hf_linear_wgrad_gather: z (rows,cout) = operand weight^T + bias (bias may be NULL) with
+ * the batch statistics of z from the accumulators, running_* may be NULL; grad_weight = grad_z^T operand, chunk partials summed
+ * in a fixed order; workspaces from hf_linear_bn_fwd_workspace(cout) / hf_linear_wgrad_workspace(rows, cout, cin); nothing
+ * allocates or synchronises.  HF_EINVAL, before any device call: rows <= 0, rows % rows_per_cloud != 0, rows >= 2^32,
+ * (rows / rows_per_cloud) * m >= 2^31, m < 1, c2 outside 1..1024, c1 outside 0..1024, cout outside 1..256, c1 > 0 without skip,
+ * any other required pointer NULL, a workspace that is missing or too small. */
+int hf_linear_bn_fwd_interp(long long rows, int c2, int c1, int cout, const float *points2, int m, long long rows_per_cloud,
+                            const int *idx, const float *weight3, const float *skip, const float *weight, const float *bias,
+                            float *z, float eps, float momentum, float *running_mean, float *running_var, float *mean,
+                            float *invstd, void *workspace, size_t workspace_bytes, hf_stream_t stream);
+int hf_linear_wgrad_interp(long long rows, int cout, int c2, int c1, const float *grad_z, const float *points2, int m,
+                           long long rows_per_cloud, const int *idx, const float *weight3, const float *skip,
+                           float *grad_weight, void *workspace, size_t workspace_bytes, hf_stream_t stream);
+
 /* ------------------------------------------------------------------ the optimizer step of the train step */
 
 /* tf.train.AdamOptimizer.apply_gradients over EVERY parameter tensor in one launch (hf/core/trainer.py:71,
