@@ -981,6 +981,12 @@ constexpr long long kBnNtBytes = 200ll << 20;
 static int bn_nt_fwd(long long rows, int c) { return static_cast<long long>(sizeof(float)) * rows * c > kBnNtBytes ? 1 : 0; }
 static int bn_nt_bwd(long long rows, int c) { return 2ll * static_cast<long long>(sizeof(float)) * rows * c > kBnNtBytes ? 1 : 0; }
 
+// channel counts the launch geometry of bn_geom can serve: a workgroup is cv * rpb threads, cv = c / 4 when c % 4 == 0 (<= 1024 threads
+// up to c = 4096) and cv = c otherwise -- above 1024 such channels the launch itself would be refused by the runtime, so the entry
+// points refuse them first (include/hfops.h states both limits)
+constexpr int kBnMaxChannels = 4096, kBnMaxScalarChannels = 1024;
+static bool bn_channels_ok(int c) { return c > 0 && c <= kBnMaxChannels && (c % 4 == 0 || c <= kBnMaxScalarChannels); }
+
 static bool aligned16(const void *p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
 
 }  // namespace hf
@@ -1006,7 +1012,7 @@ HF_API int hf_bn_relu_fwd_train_ld(long long rows, int c, const float *x, const 
                                    float *save_mean, float *save_invstd, void *workspace, size_t workspace_bytes,
                                    hf_stream_t stream)
 {
-    if (rows <= 0 || c <= 0 || c > 4096 || ldy < c || !x || !gamma || !beta || !y || !save_mean || !save_invstd) return HF_EINVAL;
+    if (rows <= 0 || !bn_channels_ok(c) || ldy < c || !x || !gamma || !beta || !y || !save_mean || !save_invstd) return HF_EINVAL;
     if (!workspace || workspace_bytes < hf_bn_workspace(rows, c)) return HF_EWORKSPACE;
     BnGeom g = bn_geom(rows, c);
     if (g.vec == 4 && !(aligned16(x) && aligned16(y) && ld_ok4(ldy))) return HF_EINVAL;
@@ -1039,7 +1045,7 @@ HF_API int hf_bn_stats(long long rows, int c, const float *x, float eps, float m
                        float *running_var, float *save_mean, float *save_invstd, void *workspace, size_t workspace_bytes,
                        hf_stream_t stream)
 {
-    if (rows <= 0 || c <= 0 || c > 4096 || !x || !save_mean || !save_invstd) return HF_EINVAL;
+    if (rows <= 0 || !bn_channels_ok(c) || !x || !save_mean || !save_invstd) return HF_EINVAL;
     if (!workspace || workspace_bytes < hf_bn_workspace(rows, c)) return HF_EWORKSPACE;
     BnGeom g = bn_geom(rows, c);
     if (g.vec == 4 && !aligned16(x)) return HF_EINVAL;
@@ -1053,7 +1059,7 @@ HF_API int hf_bn_stats(long long rows, int c, const float *x, float eps, float m
 HF_API int hf_bn_relu_fwd_eval(long long rows, int c, const float *x, const float *gamma, const float *beta,
                                const float *mean, const float *invstd, int relu, float *y, hf_stream_t stream)
 {
-    if (rows <= 0 || c <= 0 || c > 4096 || !x || !gamma || !beta || !mean || !invstd || !y) return HF_EINVAL;
+    if (rows <= 0 || !bn_channels_ok(c) || !x || !gamma || !beta || !mean || !invstd || !y) return HF_EINVAL;
     BnGeom g = bn_geom(rows, c);
     if (g.vec == 4 && !(aligned16(x) && aligned16(y))) return HF_EINVAL;
     hipStream_t st = as_stream(stream);
@@ -1066,7 +1072,7 @@ HF_API int hf_bn_relu_bwd_ld(long long rows, int c, const float *x, const float 
                              float *dgamma, float *dbeta, float *dx_colsum, void *workspace, size_t workspace_bytes,
                              hf_stream_t stream)
 {
-    if (rows <= 0 || c <= 0 || c > 4096 || lddy < c || !x || !dy || !gamma || !beta || !save_mean || !save_invstd || !dx || !dgamma ||
+    if (rows <= 0 || !bn_channels_ok(c) || lddy < c || !x || !dy || !gamma || !beta || !save_mean || !save_invstd || !dx || !dgamma ||
         !dbeta)
         return HF_EINVAL;
     if (!workspace || workspace_bytes < hf_bn_workspace(rows, c)) return HF_EWORKSPACE;
@@ -1113,7 +1119,7 @@ HF_API int hf_bn_dropout_fwd_train(long long rows, int c, const float *x, const 
                                    unsigned long long *drop_state, unsigned long long *seed_out, float *y, float *save_mean,
                                    float *save_invstd, void *workspace, size_t workspace_bytes, hf_stream_t stream)
 {
-    if (rows <= 0 || c <= 0 || c > 4096 || !x || !gamma || !beta || !y || !save_mean || !save_invstd || !drop_state || !seed_out) return HF_EINVAL;
+    if (rows <= 0 || !bn_channels_ok(c) || !x || !gamma || !beta || !y || !save_mean || !save_invstd || !drop_state || !seed_out) return HF_EINVAL;
     BnDrop d;
     if (!drop_args(rate, d, seed_out)) return HF_EINVAL;
     if (!workspace || workspace_bytes < hf_bn_workspace(rows, c)) return HF_EWORKSPACE;
@@ -1133,7 +1139,7 @@ HF_API int hf_bn_dropout_bwd(long long rows, int c, const float *x, const float 
                              const float *save_mean, const float *save_invstd, int relu, float rate, const unsigned long long *seed,
                              float *dx, float *dgamma, float *dbeta, void *workspace, size_t workspace_bytes, hf_stream_t stream)
 {
-    if (rows <= 0 || c <= 0 || c > 4096 || !x || !dy || !gamma || !beta || !save_mean || !save_invstd || !dx || !dgamma || !dbeta) return HF_EINVAL;
+    if (rows <= 0 || !bn_channels_ok(c) || !x || !dy || !gamma || !beta || !save_mean || !save_invstd || !dx || !dgamma || !dbeta) return HF_EINVAL;
     BnDrop d;
     if (!drop_args(rate, d, seed)) return HF_EINVAL;
     if (!workspace || workspace_bytes < hf_bn_workspace(rows, c)) return HF_EWORKSPACE;
@@ -1150,7 +1156,7 @@ HF_API int hf_bn_dropout_bwd(long long rows, int c, const float *x, const float 
 
 HF_API int hf_narrow_linear_dx(long long rows, int cin, int cout, const float *g, const float *w, float *dx, hf_stream_t stream)
 {
-    if (rows <= 0 || cin <= 0 || cin > 4096 || cout <= 0 || cout > kNarrowMaxOut || !g || !w || !dx) return HF_EINVAL;
+    if (rows <= 0 || !bn_channels_ok(cin) || cout <= 0 || cout > kNarrowMaxOut || !g || !w || !dx) return HF_EINVAL;
     BnGeom gm = bn_geom(rows, cin);
     if (gm.vec == 4 && !aligned16(dx)) return HF_EINVAL;
     hipStream_t st = as_stream(stream);
@@ -1165,7 +1171,7 @@ HF_API int hf_bn_relu_bwd_dx(long long rows, int c, const float *x, const float 
                              const float *save_mean, const float *save_invstd, const float *dgamma, const float *dbeta,
                              int relu, float *dx, hf_stream_t stream)
 {
-    if (rows <= 0 || c <= 0 || c > 4096 || !x || !dy || !gamma || !beta || !save_mean || !save_invstd || !dx || !dgamma ||
+    if (rows <= 0 || !bn_channels_ok(c) || !x || !dy || !gamma || !beta || !save_mean || !save_invstd || !dx || !dgamma ||
         !dbeta)
         return HF_EINVAL;
     BnGeom g = bn_geom(rows, c);
@@ -1180,7 +1186,7 @@ HF_API int hf_bn_relu_maxpool_fwd(long long groups, int k, int c, const float *z
                                   float *mean, float *invstd, float *pooled, unsigned char *argmax, void *workspace,
                                   size_t workspace_bytes, hf_stream_t stream)
 {
-    if (groups <= 0 || k <= 0 || k > 255 || c <= 0 || c > 4096 || !z || !gamma || !beta || !mean || !invstd || !pooled)
+    if (groups <= 0 || k <= 0 || k > 255 || !bn_channels_ok(c) || !z || !gamma || !beta || !mean || !invstd || !pooled)
         return HF_EINVAL;
     const long long rows = groups * k;
     hipStream_t st = as_stream(stream);
@@ -1211,7 +1217,7 @@ HF_API int hf_bn_relu_maxpool_bwd(long long groups, int k, int c, const float *z
                                   float *dbeta, float *dz_colsum, void *workspace, size_t workspace_bytes,
                                   hf_stream_t stream)
 {
-    if (groups <= 0 || k <= 0 || k > 255 || c <= 0 || c > 4096 || !z || !dpooled || !argmax || !gamma || !beta ||
+    if (groups <= 0 || k <= 0 || k > 255 || !bn_channels_ok(c) || !z || !dpooled || !argmax || !gamma || !beta ||
         !save_mean || !save_invstd || !dz || !dgamma || !dbeta)
         return HF_EINVAL;
     const long long rows = groups * k;

@@ -226,7 +226,14 @@ int hf_knn_point(int b, int n, int m, int k, const float *xyz1, const float *xyz
  * `relu` (all BatchNorm entry points that take it): bit 0 = ReLU after the normalisation; bit 1 = ELU applied to x on
  * load, before the statistics and the normalisation (pointfly.dense / conv2d: linear -> ELU -> batch_normalization,
  * hf/core/pointfly.py:371-497): 0 none, 1 BN+ReLU, 2 ELU+BN.
- * workspace: hf_bn_workspace(rows, c) bytes of device scratch. */
+ * workspace: hf_bn_workspace(rows, c) bytes of device scratch.
+ * Channel limit of every hf_bn_* entry point and of hf_narrow_linear_dx (its cin): c <= 4096, and c <= 1024 where c % 4 != 0 (such
+ * rows are accessed one float at a time, one thread per channel of a row, and a workgroup holds 1024 threads); anything beyond is
+ * HF_EINVAL before a launch.  c % 4 == 0 takes 16-byte accesses and needs 16-byte aligned tensors (and row strides).
+ * The batch variance is ONE pass, E[x^2] - mean^2, from per-block fp32 partial sums added in fp64: its absolute error is bounded by
+ * c u E[x^2] (u = 2^-24, c = 3 (fp32 additions into one partial) + 1, a few hundred at most), so relative to the variance it grows with
+ * 1 + (mean / std)^2 -- measured: at most 0.013 of that bound at mean / std = 30, relative variance errors of 1e-6 to 2.9e-4 (profiles/bn_parity.md);
+ * tf.nn.moments, two passes, has no such term.  Feed these entry points roughly centred channels. */
 size_t hf_bn_workspace(long long rows, int c);
 int hf_bn_relu_fwd_train(long long rows, int c, const float *x, const float *gamma, const float *beta, float eps,
                          float momentum, float *running_mean, float *running_var, int relu, float *y,
@@ -407,7 +414,8 @@ int hf_bn_dropout_bwd(long long rows, int c, const float *x, const float *dy, co
                       float *dx, float *dgamma, float *dbeta, void *workspace, size_t workspace_bytes, hf_stream_t stream);
 
 /* Input gradient of a Linear with a handful of outputs (the segmentation head of the RPN, hf/core/models/rpn_model.py: dense to
- * classes + 1 logits): dx (rows, cin) = g (rows, cout) w (cout, cin), cout <= 4, one streaming pass. */
+ * classes + 1 logits): dx (rows, cin) = g (rows, cout) w (cout, cin), 1 <= cout <= 4, cin within the channel limit of the hf_bn_* entry
+ * points (above), one streaming pass. */
 int hf_narrow_linear_dx(long long rows, int cin, int cout, const float *g, const float *w, float *dx, hf_stream_t stream);
 
 /* The second half of hf_bn_relu_bwd alone: dx from dy, x and ALREADY KNOWN dgamma / dbeta (no reduction pass). */

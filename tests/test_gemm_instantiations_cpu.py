@@ -19,10 +19,10 @@ CSRC = os.path.join(ROOT, "heterofusionrcnn_amd", "csrc")
 LDS_PER_CU = 160 * 1024
 
 
-def compile_to_assembly(directory):
-    asm = os.path.join(str(directory), "gemm.s")
+def compile_to_assembly(directory, source="gemm.hip"):
+    asm = os.path.join(str(directory), os.path.splitext(source)[0] + ".s")
     subprocess.run([os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17",
-                    "-I" + os.path.join(ROOT, "include"), "--cuda-device-only", "-S", os.path.join(CSRC, "gemm.hip"), "-o", asm],
+                    "-I" + os.path.join(ROOT, "include"), "--cuda-device-only", "-S", os.path.join(CSRC, source), "-o", asm],
                    check=True, capture_output=True)
     with open(asm) as f:
         return f.read()
