@@ -12,9 +12,10 @@
 //   interp(j) = w[r][0] * P[cloud, idx[r][0], j] + w[r][1] * P[cloud, idx[r][1], j] + w[r][2] * P[cloud, idx[r][2], j]
 // summed left to right without contraction: the bits of three_interpolate_concat_kernel (interpolate.hip).
 //
-// The tile machine is that of gemm.hip (gemm_common.h): v_mfma_f32_32x32x2_f32, 128-row forward tiles of 32 input channels per
-// LDS stage on a persistent grid with the BatchNorm statistics taken from the accumulators; the weight gradient as per-chunk
-// partial tiles summed in a fixed order.  Only the A-operand loader is new.
+// The tile machine is that of gemm.hip, shared through gemm_common.h (fwd_mfma_stage, col_sums_store, wgrad_tile_loop):
+// v_mfma_f32_32x32x2_f32, 128-row forward tiles of 32 input channels per LDS stage on a persistent grid with the BatchNorm
+// statistics taken from the accumulators; the weight gradient as per-chunk partial tiles summed in a fixed order.  This file is
+// the A-operand loader (InterpSrc), the two kernels that hand it to the machine, and their launchers.
 #include <math.h>
 #include <stdint.h>
 
@@ -137,15 +138,10 @@ __global__ __launch_bounds__(kGemmThreads) __attribute__((amdgpu_waves_per_eu(2)
     long long rows, int cin, int cout, long long ntiles, InterpSrc src, const float *__restrict__ W,
     const float *__restrict__ bias, float *__restrict__ Z, float *__restrict__ partial)
 {
-    __shared__ float As[kFwdRows * kFwdLS];
-    __shared__ float Bs[NT * 32 * kFwdLS];
-    __shared__ float red[4][NT * 32][2];
-
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int k4 = (t & 7) * 4, srow = t >> 3;  // staging: 8 threads cover the 32 channels of a row, 32 rows per pass
-    float s1[NT], s2[NT];
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) { s1[nt] = 0.f; s2[nt] = 0.f; }
+    __shared__ FwdLds<NT> lds;
+    const int lane = threadIdx.x & 63;
+    const int k4 = fwd_k4(), srow = fwd_srow();
+    float s[NT][2] = {};
 
     unsigned ridx[4][3];    // source rows of the tile that the NEXT fetch reads
     float rw[4][3];         // weights of the tile whose loads are combined next
@@ -185,10 +181,10 @@ __global__ __launch_bounds__(kGemmThreads) __attribute__((amdgpu_waves_per_eu(2)
             // the multiplies happen here, not at fetch time: the gathered loads stay in flight across the MFMA loop
 #pragma unroll
             for (int p = 0; p < 4; ++p)
-                *reinterpret_cast<float4 *>(&As[(srow + 32 * p) * kFwdLS + k4]) =
+                *reinterpret_cast<float4 *>(&lds.As[(srow + 32 * p) * kFwdLS + k4]) =
                     interp_combine<VEC>(src, rw[p], row0 + srow + 32 * p < rows, kc + k4, ar[p]);
 #pragma unroll
-            for (int p = 0; p < NT; ++p) *reinterpret_cast<float4 *>(&Bs[(srow + 32 * p) * kFwdLS + k4]) = br[p];
+            for (int p = 0; p < NT; ++p) *reinterpret_cast<float4 *>(&lds.Bs[(srow + 32 * p) * kFwdLS + k4]) = br[p];
             __syncthreads();
             // the next stage -- of this tile, or the first one of the workgroup's next tile -- is in flight during
             // the MFMAs and the output stores below
@@ -198,15 +194,7 @@ __global__ __launch_bounds__(kGemmThreads) __attribute__((amdgpu_waves_per_eu(2)
                 load_w((tile + gridDim.x) * kFwdRows);
                 fetch(tile + gridDim.x, 0);
             }
-            const float *ap = As + (32 * wave + (lane & 31)) * kFwdLS + (lane >> 5);
-            const float *bp = Bs + (lane & 31) * kFwdLS + (lane >> 5);
-#pragma unroll 4
-            for (int s = 0; s < kFwdKC / 2; ++s) {
-                const float a = ap[2 * s];
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt)
-                    acc[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, bp[nt * 32 * kFwdLS + 2 * s], acc[nt], 0, 0, 0);
-            }
+            fwd_mfma_stage(lds, acc);
             __syncthreads();
         }
 #pragma unroll
@@ -216,34 +204,17 @@ __global__ __launch_bounds__(kGemmThreads) __attribute__((amdgpu_waves_per_eu(2)
             const float bv = (bias && col_ok) ? bias[col] : 0.f;
 #pragma unroll
             for (int g = 0; g < 16; ++g) {
-                const long long row = row0 + 32 * wave + 8 * (g >> 2) + 4 * (lane >> 5) + (g & 3);
+                const long long row = fwd_d_row(row0, g);
                 const float v = acc[nt][g] + bv;
                 if (col_ok && row < rows) {
                     Z[row * cout + col] = v;
-                    s1[nt] += v;
-                    s2[nt] += v * v;
+                    s[nt][0] += v;
+                    s[nt][1] += v * v;
                 }
             }
         }
     }
-    // per-workgroup column sums: the two row-halves of a wave, then the four waves in a fixed order
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) {
-        s1[nt] += __shfl_xor(s1[nt], 32);
-        s2[nt] += __shfl_xor(s2[nt], 32);
-        if (lane < 32) {
-            red[wave][nt * 32 + lane][0] = s1[nt];
-            red[wave][nt * 32 + lane][1] = s2[nt];
-        }
-    }
-    __syncthreads();
-    for (int col = t; col < cout; col += kGemmThreads) {
-        float a = red[0][col][0], b = red[0][col][1];
-#pragma unroll
-        for (int w = 1; w < 4; ++w) { a += red[w][col][0]; b += red[w][col][1]; }
-        partial[static_cast<size_t>(col) * kBnMaxBlocks + blockIdx.x] = a;
-        partial[static_cast<size_t>(cout + col) * kBnMaxBlocks + blockIdx.x] = b;
-    }
+    col_sums_store(lds, s, cout, partial);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -256,101 +227,34 @@ __global__ __launch_bounds__(kGemmThreads) void interp_wgrad_kernel(long long ro
                                                                     long long rows_per_chunk, const float *__restrict__ G,
                                                                     InterpSrc src, float *__restrict__ partial)
 {
-    constexpr int TM = 64 * WM, TN = 64 * WN;
-    constexpr int GS = TM + 32, XS = TN + 32;  // LDS row strides: the two row-halves of a wave land on disjoint banks
-    constexpr int GC4 = TM / 4, XC4 = TN / 4;  // float4 per staged row
-    constexpr int GPASS = kGemmRowsPerStage * GC4 / kGemmThreads, XPASS = kGemmRowsPerStage * XC4 / kGemmThreads;
-    constexpr int GROWS = kGemmThreads / GC4, XROWS = kGemmThreads / XC4;  // rows covered per pass
-    __shared__ float Gs[kGemmRowsPerStage * GS];
-    __shared__ float Xs[kGemmRowsPerStage * XS];
+    using Q = WgradTile<WM, WN>;
+    __shared__ typename Q::Lds lds;
+    const Q q(rows, mtiles, rows_per_chunk);
 
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int wm = wave & 1, wn = wave >> 1;
-    const int tile_m = blockIdx.x % mtiles, tile_n = blockIdx.x / mtiles;
-    const long long r0 = blockIdx.y * rows_per_chunk;
-    const long long r1 = r0 + rows_per_chunk < rows ? r0 + rows_per_chunk : rows;
-
-    const int gcol = tile_m * TM + (t % GC4) * 4, grow = t / GC4;
-    const int xcol = tile_n * TN + (t % XC4) * 4, xrow = t / XC4;
-
-    f32x16 acc[WM][WN];
-#pragma unroll
-    for (int i = 0; i < WM; ++i)
-#pragma unroll
-        for (int j = 0; j < WN; ++j)
-#pragma unroll
-            for (int g = 0; g < 16; ++g) acc[i][j][g] = 0.f;
-
-    unsigned nidx[XPASS][3];            // source rows and weights of the stage that the next fetch reads
-    float nw[XPASS][3], cw[XPASS][3];   // cw: weights of the stage whose loads are in xr
-    float4 gr[GPASS], xr[XPASS][3];
+    unsigned nidx[Q::XPASS][3];                 // source rows and weights of the stage that the next fetch reads
+    float nw[Q::XPASS][3], cw[Q::XPASS][3];     // cw: weights of the stage whose loads are in xr
+    float4 gr[Q::GPASS], xr[Q::XPASS][3];
     auto load_meta = [&](long long rt) {
 #pragma unroll
-        for (int p = 0; p < XPASS; ++p) {
-            interp_row_idx(src, rt + xrow + p * XROWS, r1, nidx[p]);
-            interp_row_w(src, rt + xrow + p * XROWS, r1, nw[p]);
+        for (int p = 0; p < Q::XPASS; ++p) {
+            interp_row_idx(src, rt + q.xrow + p * Q::XROWS, q.r1, nidx[p]);
+            interp_row_w(src, rt + q.xrow + p * Q::XROWS, q.r1, nw[p]);
         }
     };
     auto fetch = [&](long long rt) {
 #pragma unroll
-        for (int p = 0; p < GPASS; ++p) gr[p] = load4_guarded<VEC>(G, rt + grow + p * GROWS, r1, gcol, cout);
+        for (int p = 0; p < Q::GPASS; ++p) gr[p] = load4_guarded<VEC>(G, rt + q.grow + p * Q::GROWS, q.r1, q.gcol, cout);
 #pragma unroll
-        for (int p = 0; p < XPASS; ++p) {
-            interp_fetch<VEC>(src, nidx[p], rt + xrow + p * XROWS, r1, xcol, xr[p]);
+        for (int p = 0; p < Q::XPASS; ++p) {
+            interp_fetch<VEC>(src, nidx[p], rt + q.xrow + p * Q::XROWS, q.r1, q.xcol, xr[p]);
             cw[p][0] = nw[p][0]; cw[p][1] = nw[p][1]; cw[p][2] = nw[p][2];
         }
         load_meta(rt + kGemmRowsPerStage);
     };
-    load_meta(r0);
-    fetch(r0);
-    for (long long rt = r0; rt < r1; rt += kGemmRowsPerStage) {
-#pragma unroll
-        for (int p = 0; p < GPASS; ++p)
-            *reinterpret_cast<float4 *>(&Gs[(grow + p * GROWS) * GS + (t % GC4) * 4]) = gr[p];
-        // the multiplies happen here, not at fetch time: the gathered loads stay in flight across the MFMA loop
-#pragma unroll
-        for (int p = 0; p < XPASS; ++p)
-            *reinterpret_cast<float4 *>(&Xs[(xrow + p * XROWS) * XS + (t % XC4) * 4]) =
-                interp_combine<VEC>(src, cw[p], rt + xrow + p * XROWS < r1, xcol, xr[p]);
-        __syncthreads();
-        if (rt + kGemmRowsPerStage < r1) fetch(rt + kGemmRowsPerStage);  // in flight during the MFMAs below
-        const float *ga = Gs + (lane >> 5) * GS + wm * 32 * WM + (lane & 31);
-        const float *xb = Xs + (lane >> 5) * XS + wn * 32 * WN + (lane & 31);
-        float a[2][WM], b[2][WN];  // operands of the next row pair are read while this pair's MFMAs run
-#pragma unroll
-        for (int i = 0; i < WM; ++i) a[0][i] = ga[i * 32];
-#pragma unroll
-        for (int j = 0; j < WN; ++j) b[0][j] = xb[j * 32];
-#pragma unroll
-        for (int s = 0; s < kGemmRowsPerStage / 2; ++s) {
-            const int cur = s & 1, nxt = cur ^ 1;
-            if (s + 1 < kGemmRowsPerStage / 2) {
-#pragma unroll
-                for (int i = 0; i < WM; ++i) a[nxt][i] = ga[2 * (s + 1) * GS + i * 32];
-#pragma unroll
-                for (int j = 0; j < WN; ++j) b[nxt][j] = xb[2 * (s + 1) * XS + j * 32];
-            }
-#pragma unroll
-            for (int i = 0; i < WM; ++i)
-#pragma unroll
-                for (int j = 0; j < WN; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[cur][i], b[cur][j], acc[i][j], 0, 0, 0);
-        }
-        __syncthreads();
-    }
-
-    float *out = partial + static_cast<size_t>(blockIdx.y) * cout * cin;
-#pragma unroll
-    for (int i = 0; i < WM; ++i)
-#pragma unroll
-        for (int j = 0; j < WN; ++j) {
-            const int k = tile_n * TN + wn * 32 * WN + j * 32 + (lane & 31);
-#pragma unroll
-            for (int g = 0; g < 16; ++g) {
-                const int n = tile_m * TM + wm * 32 * WM + i * 32 + 8 * (g >> 2) + 4 * (lane >> 5) + (g & 3);
-                if (n < cout && k < cin) out[static_cast<size_t>(n) * cin + k] = acc[i][j][g];
-            }
-        }
+    // the multiplies happen when the stage is stored, not at fetch time: the gathered loads stay in flight across the MFMA loop
+    auto stage_x = [&](int p, long long rt) { return interp_combine<VEC>(src, cw[p], rt + q.xrow + p * Q::XROWS < q.r1, q.xcol, xr[p]); };
+    load_meta(q.r0);
+    wgrad_tile_loop<WM, WN>(lds, q, cout, cin, partial, gr, fetch, stage_x);
 }
 
 }  // namespace hf

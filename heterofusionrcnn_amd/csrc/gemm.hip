@@ -5,8 +5,10 @@
 // channels, and so are its two gradients.  All three are built on v_mfma_f32_32x32x2_f32: f32 in, f32
 // accumulate, bit-for-bit a k-ordered fmaf chain, so the arithmetic type of the path stays fp32.
 //
-// Lane maps of the 32x32x2 form (lane l): A[i = l&31][k = l>>5], B[k = l>>5][j = l&31];
-// D register g holds row i = 8*(g>>2) + 4*(l>>5) + (g&3), column j = l&31.
+// The tile machine -- the lane maps of the 32x32x2 form, the forward form's LDS layout, MFMA stage and column-sum epilogue, and the
+// wgrad-form chunk loop -- is in gemm_common.h.  A wgrad kernel here is the operand source it hands to that loop; a forward-form
+// kernel is its own walk over tiles and stages (the loads of a stage, what is stored in LDS from them, what happens to the
+// accumulators) around the shared MFMA stage.
 //
 //   wgrad   dW (Cout, Cin) = G^T X, the reduction runs over rows.  Both operands are read in their row-major
 //           global layout and staged in LDS as they are: lane (l&31) walks channels, (l>>5) picks the row of a
@@ -118,89 +120,22 @@ __global__ __launch_bounds__(kGemmThreads) void wgrad_kernel(long long rows, int
                                                              const float *__restrict__ in_invstd,
                                                              float *__restrict__ partial, GatherSrc gs)
 {
-    constexpr int TM = 64 * WM, TN = 64 * WN;
-    constexpr int GS = TM + 32, XS = TN + 32;  // LDS row strides: the two row-halves of a wave land on disjoint banks
-    constexpr int GC4 = TM / 4, XC4 = TN / 4;  // float4 per staged row
-    constexpr int GPASS = kGemmRowsPerStage * GC4 / kGemmThreads, XPASS = kGemmRowsPerStage * XC4 / kGemmThreads;
-    constexpr int GROWS = kGemmThreads / GC4, XROWS = kGemmThreads / XC4;  // rows covered per pass
-    __shared__ float Gs[kGemmRowsPerStage * GS];
-    __shared__ float Xs[kGemmRowsPerStage * XS];
+    using Q = WgradTile<WM, WN>;
+    __shared__ typename Q::Lds lds;
+    const Q q(rows, mtiles, rows_per_chunk);
+    const ColAct act = make_col_act(q.xcol, cin, in_gamma, in_beta, in_mean, in_invstd);
 
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int wm = wave & 1, wn = wave >> 1;
-    const int tile_m = blockIdx.x % mtiles, tile_n = blockIdx.x / mtiles;
-    const long long r0 = blockIdx.y * rows_per_chunk;
-    const long long r1 = r0 + rows_per_chunk < rows ? r0 + rows_per_chunk : rows;
-
-    const int gcol = tile_m * TM + (t % GC4) * 4, grow = t / GC4;
-    const int xcol = tile_n * TN + (t % XC4) * 4, xrow = t / XC4;
-    const ColAct act = make_col_act(xcol, cin, in_gamma, in_beta, in_mean, in_invstd);
-
-    f32x16 acc[WM][WN];
-#pragma unroll
-    for (int i = 0; i < WM; ++i)
-#pragma unroll
-        for (int j = 0; j < WN; ++j)
-#pragma unroll
-            for (int g = 0; g < 16; ++g) acc[i][j][g] = 0.f;
-
-    float4 gr[GPASS], xr[XPASS];
+    float4 gr[Q::GPASS], xr[Q::XPASS];
     auto fetch = [&](long long rt) {
 #pragma unroll
-        for (int p = 0; p < GPASS; ++p) gr[p] = load4_guarded<VEC>(G, rt + grow + p * GROWS, r1, gcol, cout);
+        for (int p = 0; p < Q::GPASS; ++p) gr[p] = load4_guarded<VEC>(G, rt + q.grow + p * Q::GROWS, q.r1, q.gcol, cout);
 #pragma unroll
-        for (int p = 0; p < XPASS; ++p)
-            xr[p] = GATHER ? load4_gathered(gs, rt + xrow + p * XROWS, r1, xcol) : load4_guarded<VEC>(X, rt + xrow + p * XROWS, r1, xcol, cin);
+        for (int p = 0; p < Q::XPASS; ++p)
+            xr[p] = GATHER ? load4_gathered(gs, rt + q.xrow + p * Q::XROWS, q.r1, q.xcol) : load4_guarded<VEC>(X, rt + q.xrow + p * Q::XROWS, q.r1, q.xcol, cin);
     };
-    fetch(r0);
-    for (long long rt = r0; rt < r1; rt += kGemmRowsPerStage) {
-#pragma unroll
-        for (int p = 0; p < GPASS; ++p)
-            *reinterpret_cast<float4 *>(&Gs[(grow + p * GROWS) * GS + (t % GC4) * 4]) = gr[p];
-        // the activation is applied here, not at fetch time: the loads stay in flight across the MFMA loop
-#pragma unroll
-        for (int p = 0; p < XPASS; ++p)
-            *reinterpret_cast<float4 *>(&Xs[(xrow + p * XROWS) * XS + (t % XC4) * 4]) =
-                apply_col_act(act, xr[p], rt + xrow + p * XROWS < r1);
-        __syncthreads();
-        if (rt + kGemmRowsPerStage < r1) fetch(rt + kGemmRowsPerStage);  // in flight during the MFMAs below
-        const float *ga = Gs + (lane >> 5) * GS + wm * 32 * WM + (lane & 31);
-        const float *xb = Xs + (lane >> 5) * XS + wn * 32 * WN + (lane & 31);
-        float a[2][WM], b[2][WN];  // operands of the next row pair are read while this pair's MFMAs run
-#pragma unroll
-        for (int i = 0; i < WM; ++i) a[0][i] = ga[i * 32];
-#pragma unroll
-        for (int j = 0; j < WN; ++j) b[0][j] = xb[j * 32];
-#pragma unroll
-        for (int s = 0; s < kGemmRowsPerStage / 2; ++s) {
-            const int cur = s & 1, nxt = cur ^ 1;
-            if (s + 1 < kGemmRowsPerStage / 2) {
-#pragma unroll
-                for (int i = 0; i < WM; ++i) a[nxt][i] = ga[2 * (s + 1) * GS + i * 32];
-#pragma unroll
-                for (int j = 0; j < WN; ++j) b[nxt][j] = xb[2 * (s + 1) * XS + j * 32];
-            }
-#pragma unroll
-            for (int i = 0; i < WM; ++i)
-#pragma unroll
-                for (int j = 0; j < WN; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[cur][i], b[cur][j], acc[i][j], 0, 0, 0);
-        }
-        __syncthreads();
-    }
-
-    float *out = partial + static_cast<size_t>(blockIdx.y) * cout * cin;
-#pragma unroll
-    for (int i = 0; i < WM; ++i)
-#pragma unroll
-        for (int j = 0; j < WN; ++j) {
-            const int k = tile_n * TN + wn * 32 * WN + j * 32 + (lane & 31);
-#pragma unroll
-            for (int g = 0; g < 16; ++g) {
-                const int n = tile_m * TM + wm * 32 * WM + i * 32 + 8 * (g >> 2) + 4 * (lane >> 5) + (g & 3);
-                if (n < cout && k < cin) out[static_cast<size_t>(n) * cin + k] = acc[i][j][g];
-            }
-        }
+    // the activation is applied when the stage is stored, not at fetch time: the loads stay in flight across the MFMA loop
+    auto stage_x = [&](int p, long long rt) { return apply_col_act(act, xr[p], rt + q.xrow + p * Q::XROWS < q.r1); };
+    wgrad_tile_loop<WM, WN>(lds, q, cout, cin, partial, gr, fetch, stage_x);
 }
 
 // dW[e] = sum over chunks in a fixed order: 64 consecutive elements x 16 chunk groups per workgroup
@@ -254,12 +189,10 @@ __global__ __launch_bounds__(kGemmThreads) __attribute__((amdgpu_waves_per_eu(2)
 {
     // elu: the layer order of PointCNN's dense (pointfly.py:480-497), linear -> ELU -> BatchNorm: the activation on load is
     // a (elu(x) - mu) + beta (no clamp) and the statistics in the epilogue are those of elu(z)
-    __shared__ float As[kFwdRows * kFwdLS];
-    __shared__ float Bs[NT * 32 * kFwdLS];
-    __shared__ float red[4][NT * 32][2];
+    __shared__ FwdLds<NT> lds;
     __shared__ float sc[kFwdMaxCin], sh[kFwdMaxCin], smu[kFwdMaxCin];   // scale, beta, mean
 
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int t = threadIdx.x, lane = t & 63;
     const bool act = in_gamma != nullptr;
     if (act) {
         for (int k = t; k < cin; k += kGemmThreads) {
@@ -271,10 +204,8 @@ __global__ __launch_bounds__(kGemmThreads) __attribute__((amdgpu_waves_per_eu(2)
     }
     __syncthreads();
 
-    const int k4 = (t & 7) * 4, srow = t >> 3;  // staging: 8 threads cover the 32 channels of a row, 32 rows per pass
-    float s1[NT], s2[NT];
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) { s1[nt] = 0.f; s2[nt] = 0.f; }
+    const int k4 = fwd_k4(), srow = fwd_srow();
+    float s[NT][2] = {};
 
     float4 ar[4], br[NT];
     auto fetch = [&](long long r0, int kc) {
@@ -323,24 +254,16 @@ __global__ __launch_bounds__(kGemmThreads) __attribute__((amdgpu_waves_per_eu(2)
                         }
                     }
                 }
-                *reinterpret_cast<float4 *>(&As[(srow + 32 * p) * kFwdLS + k4]) = v;
+                *reinterpret_cast<float4 *>(&lds.As[(srow + 32 * p) * kFwdLS + k4]) = v;
             }
 #pragma unroll
-            for (int p = 0; p < NT; ++p) *reinterpret_cast<float4 *>(&Bs[(srow + 32 * p) * kFwdLS + k4]) = br[p];
+            for (int p = 0; p < NT; ++p) *reinterpret_cast<float4 *>(&lds.Bs[(srow + 32 * p) * kFwdLS + k4]) = br[p];
             __syncthreads();
             // the next stage -- of this tile, or the first one of the workgroup's next tile -- is in flight during
             // the MFMAs and the output stores below
             if (kc + kFwdKC < cin) fetch(row0, kc + kFwdKC);
             else if (tile + gridDim.x < ntiles) fetch((tile + gridDim.x) * kFwdRows, 0);
-            const float *ap = As + (32 * wave + (lane & 31)) * kFwdLS + (lane >> 5);
-            const float *bp = Bs + (lane & 31) * kFwdLS + (lane >> 5);
-#pragma unroll 4
-            for (int s = 0; s < kFwdKC / 2; ++s) {
-                const float a = ap[2 * s];
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt)
-                    acc[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, bp[nt * 32 * kFwdLS + 2 * s], acc[nt], 0, 0, 0);
-            }
+            fwd_mfma_stage(lds, acc);
             __syncthreads();
         }
 #pragma unroll
@@ -350,35 +273,18 @@ __global__ __launch_bounds__(kGemmThreads) __attribute__((amdgpu_waves_per_eu(2)
             const float bv = (bias && cin_range) ? bias[col] : 0.f;
 #pragma unroll
             for (int g = 0; g < 16; ++g) {
-                const long long row = row0 + 32 * wave + 8 * (g >> 2) + 4 * (lane >> 5) + (g & 3);
+                const long long row = fwd_d_row(row0, g);
                 const float v = acc[nt][g] + bv;
                 if (cin_range && row < rows) {
                     Z[row * cout + col] = v;
                     const float sv = elu ? elu_fwd(v) : v;
-                    s1[nt] += sv;
-                    s2[nt] += sv * sv;
+                    s[nt][0] += sv;
+                    s[nt][1] += sv * sv;
                 }
             }
         }
     }
-    // per-workgroup column sums: the two row-halves of a wave, then the four waves in a fixed order
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) {
-        s1[nt] += __shfl_xor(s1[nt], 32);
-        s2[nt] += __shfl_xor(s2[nt], 32);
-        if (lane < 32) {
-            red[wave][nt * 32 + lane][0] = s1[nt];
-            red[wave][nt * 32 + lane][1] = s2[nt];
-        }
-    }
-    __syncthreads();
-    for (int col = t; col < cout; col += kGemmThreads) {
-        float a = red[0][col][0], b = red[0][col][1];
-#pragma unroll
-        for (int w = 1; w < 4; ++w) { a += red[w][col][0]; b += red[w][col][1]; }
-        partial[static_cast<size_t>(col) * kBnMaxBlocks + blockIdx.x] = a;
-        partial[static_cast<size_t>(cout + col) * kBnMaxBlocks + blockIdx.x] = b;
-    }
+    col_sums_store(lds, s, cout, partial);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -406,13 +312,11 @@ __global__ __launch_bounds__(kGemmThreads) __attribute__((amdgpu_waves_per_eu(2)
 {
     // elu (without FROM_DY): the layer below is linear -> ELU -> BatchNorm; DX is the gradient w.r.t. its normalised output, so
     // its BN-backward sums are sum DX and sum DX * xhat with xhat from elu(z_prev), no mask
-    __shared__ float As[kFwdRows * kFwdLS];
-    __shared__ float Bs[NT * 32 * kFwdLS];
-    __shared__ float red[4][NT * 32][2];
+    __shared__ FwdLds<NT> lds;
     __shared__ float ta[FROM_DY ? kBwdMaxK : 1], tsh[FROM_DY ? kBwdMaxK : 1], tmu[FROM_DY ? kBwdMaxK : 1],
         tis[FROM_DY ? kBwdMaxK : 1], tc1[FROM_DY ? kBwdMaxK : 1], tc2[FROM_DY ? kBwdMaxK : 1];
 
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int t = threadIdx.x, lane = t & 63;
     if (FROM_DY) {
         const float inv_r = 1.0f / static_cast<float>(rows);
         for (int k = t; k < kdim; k += kGemmThreads) {
@@ -428,11 +332,11 @@ __global__ __launch_bounds__(kGemmThreads) __attribute__((amdgpu_waves_per_eu(2)
     __syncthreads();
     const bool sums = Zprev != nullptr;
     // BN constants of the layer below for this lane's output columns
-    float pa[NT], psh[NT], pmu[NT], pis[NT], s1[NT], s2[NT];
+    float pa[NT], psh[NT], pmu[NT], pis[NT], s[NT][2] = {};
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) {
         const int col = nt * 32 + (lane & 31);
-        pa[nt] = 0.f; psh[nt] = 0.f; pmu[nt] = 0.f; pis[nt] = 0.f; s1[nt] = 0.f; s2[nt] = 0.f;
+        pa[nt] = 0.f; psh[nt] = 0.f; pmu[nt] = 0.f; pis[nt] = 0.f;
         if (sums && col < ncols) {
             pa[nt] = p_gamma[col] * p_invstd[col];
             psh[nt] = p_beta[col];
@@ -441,7 +345,7 @@ __global__ __launch_bounds__(kGemmThreads) __attribute__((amdgpu_waves_per_eu(2)
         }
     }
 
-    const int k4 = (t & 7) * 4, srow = t >> 3;
+    const int k4 = fwd_k4(), srow = fwd_srow();
     float4 ar[4], zr[4], br[NT];
     auto fetch = [&](long long r0, int kc) {
 #pragma unroll
@@ -494,22 +398,14 @@ __global__ __launch_bounds__(kGemmThreads) __attribute__((amdgpu_waves_per_eu(2)
                         }
                     }
                 }
-                *reinterpret_cast<float4 *>(&As[(srow + 32 * p) * kFwdLS + k4]) = v;
+                *reinterpret_cast<float4 *>(&lds.As[(srow + 32 * p) * kFwdLS + k4]) = v;
             }
 #pragma unroll
-            for (int p = 0; p < NT; ++p) *reinterpret_cast<float4 *>(&Bs[(srow + 32 * p) * kFwdLS + k4]) = br[p];
+            for (int p = 0; p < NT; ++p) *reinterpret_cast<float4 *>(&lds.Bs[(srow + 32 * p) * kFwdLS + k4]) = br[p];
             __syncthreads();
             if (kc + kFwdKC < kdim) fetch(row0, kc + kFwdKC);
             else if (tile + gridDim.x < ntiles) fetch((tile + gridDim.x) * kFwdRows, 0);
-            const float *ap = As + (32 * wave + (lane & 31)) * kFwdLS + (lane >> 5);
-            const float *bp = Bs + (lane & 31) * kFwdLS + (lane >> 5);
-#pragma unroll 4
-            for (int s = 0; s < kFwdKC / 2; ++s) {
-                const float a = ap[2 * s];
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt)
-                    acc[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, bp[nt * 32 * kFwdLS + 2 * s], acc[nt], 0, 0, 0);
-            }
+            fwd_mfma_stage(lds, acc);
             __syncthreads();
         }
 #pragma unroll
@@ -518,42 +414,25 @@ __global__ __launch_bounds__(kGemmThreads) __attribute__((amdgpu_waves_per_eu(2)
             if (col >= ncols) continue;
 #pragma unroll
             for (int g = 0; g < 16; ++g) {
-                const long long row = row0 + 32 * wave + 8 * (g >> 2) + 4 * (lane >> 5) + (g & 3);
+                const long long row = fwd_d_row(row0, g);
                 if (row >= rows) continue;
                 const float v = acc[nt][g];
                 if (DX) DX[row * ncols + col] = v;
                 if (sums) {
                     const float zp = Zprev[row * ncols + col];
                     if (elu) {
-                        s1[nt] += v;
-                        s2[nt] += v * ((elu_fwd(zp) - pmu[nt]) * pis[nt]);
+                        s[nt][0] += v;
+                        s[nt][1] += v * ((elu_fwd(zp) - pmu[nt]) * pis[nt]);
                     } else {
                         const float dh = (pa[nt] * (zp - pmu[nt]) + psh[nt] > 0.0f) ? v : 0.0f;
-                        s1[nt] += dh;
-                        s2[nt] += dh * ((zp - pmu[nt]) * pis[nt]);
+                        s[nt][0] += dh;
+                        s[nt][1] += dh * ((zp - pmu[nt]) * pis[nt]);
                     }
                 }
             }
         }
     }
-    if (!sums) return;
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) {
-        s1[nt] += __shfl_xor(s1[nt], 32);
-        s2[nt] += __shfl_xor(s2[nt], 32);
-        if (lane < 32) {
-            red[wave][nt * 32 + lane][0] = s1[nt];
-            red[wave][nt * 32 + lane][1] = s2[nt];
-        }
-    }
-    __syncthreads();
-    for (int col = t; col < ncols; col += kGemmThreads) {
-        float a = red[0][col][0], b = red[0][col][1];
-#pragma unroll
-        for (int w = 1; w < 4; ++w) { a += red[w][col][0]; b += red[w][col][1]; }
-        partial[static_cast<size_t>(col) * kBnMaxBlocks + blockIdx.x] = a;
-        partial[static_cast<size_t>(ncols + col) * kBnMaxBlocks + blockIdx.x] = b;
-    }
+    if (sums) col_sums_store(lds, s, ncols, partial);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -584,13 +463,28 @@ __device__ __forceinline__ void lift_tab_load(LiftTab &T, int c, const float *__
 }
 __device__ __forceinline__ float lift_z(float wx, float wy, float wz, float x0, float x1, float x2) { return (x0 * wx + x1 * wy) + x2 * wz; }
 // the first layer's ELU is evaluated five times per element instead of once, and expm1f (~30 instructions) made the lift
-// kernels VALU-bound (the forward wrote its 268 MB in 119 us); exp(x) - 1 on the hardware exponential is TensorFlow's own
-// formula for tf.nn.elu (Eigen: x < 0 ? exp(x) - 1 : x) and two instructions
-__device__ __forceinline__ float lift_elu(float x) { return x > 0.0f ? x : __expf(x) - 1.0f; }
-__device__ __forceinline__ float lift_elu_slope(float x) { return x > 0.0f ? 1.0f : __expf(x); }
+// kernels VALU-bound (the forward wrote its 268 MB in 119 us): elu_hw, exp(x) - 1 on the hardware exponential
 __device__ __forceinline__ float lift_y(const LiftTab &T, int k, float x0, float x1, float x2)
 {
-    return T.a[k] * (lift_elu(lift_z(T.wx[k], T.wy[k], T.wz[k], x0, x1, x2)) - T.mu[k]) + T.be[k];
+    return T.a[k] * (elu_hw(lift_z(T.wx[k], T.wy[k], T.wz[k], x0, x1, x2)) - T.mu[k]) + T.be[k];
+}
+// the three coordinates of row `row`, zero outside [0, row_end)
+__device__ __forceinline__ void lift_load_x(const float *__restrict__ x3, long long row, long long row_end, float (&x)[3])
+{
+    const bool ok = row < row_end;
+    const float *px = x3 + (ok ? row : 0) * 3;
+    const float a = px[0], b = px[1], c = px[2];
+    x[0] = ok ? a : 0.f; x[1] = ok ? b : 0.f; x[2] = ok ? c : 0.f;
+}
+// y0 of channels k .. k+3 of a row with coordinates x; zero outside the matrix
+__device__ __forceinline__ float4 lift_y4(const LiftTab &T, int k, int c0, bool rin, const float (&x)[3])
+{
+    float4 v;
+    v.x = (rin && k < c0) ? lift_y(T, k, x[0], x[1], x[2]) : 0.f;
+    v.y = (rin && k + 1 < c0) ? lift_y(T, k + 1, x[0], x[1], x[2]) : 0.f;
+    v.z = (rin && k + 2 < c0) ? lift_y(T, k + 2, x[0], x[1], x[2]) : 0.f;
+    v.w = (rin && k + 3 < c0) ? lift_y(T, k + 3, x[0], x[1], x[2]) : 0.f;
+    return v;
 }
 
 // batch statistics of elu(W0 x): a lane owns a channel, the waves of a block walk a chunk of rows (x is wave-uniform)
@@ -607,7 +501,7 @@ __global__ __launch_bounds__(256) void lift_stats_kernel(long long rows, int c, 
     const long long r1 = r0 + rows_per_block < rows ? r0 + rows_per_block : rows;
     float s = 0.f, q = 0.f;
     for (long long r = r0 + wave; r < r1; r += 4) {
-        const float e = lift_elu(lift_z(wx, wy, wz, x3[3 * r], x3[3 * r + 1], x3[3 * r + 2]));
+        const float e = elu_hw(lift_z(wx, wy, wz, x3[3 * r], x3[3 * r + 1], x3[3 * r + 2]));
         s += e;
         q += e * e;
     }
@@ -631,9 +525,7 @@ __global__ __launch_bounds__(kGemmThreads) __attribute__((amdgpu_waves_per_eu(2)
     const float *__restrict__ invstd0, const float *__restrict__ W, float *__restrict__ Z, float *__restrict__ partial,
     const float *__restrict__ gamma1, const float *__restrict__ beta1, const float *__restrict__ mean1, const float *__restrict__ invstd1)
 {
-    __shared__ float As[kFwdRows * kFwdLS];
-    __shared__ float Bs[NT * 32 * kFwdLS];
-    __shared__ float red[4][NT * 32][2];
+    __shared__ FwdLds<NT> lds;
     __shared__ LiftTab T;
     // inference with the second layer's running statistics given (hf_lift_elu_fwd_eval_bn): the epilogue stores
     // gamma1 * invstd1 * (elu(z1) - mean1) + beta1 instead of z1 -- the normalisation pass of that layer (a read and a write of the
@@ -648,14 +540,12 @@ __global__ __launch_bounds__(kGemmThreads) __attribute__((amdgpu_waves_per_eu(2)
         ob[nt] = okc ? beta1[col] : 0.f;
         om[nt] = okc ? mean1[col] : 0.f;
     }
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int t = threadIdx.x, lane = t & 63;
     lift_tab_load(T, c0, w0, gamma0, beta0, mean0, invstd0);
     __syncthreads();
 
-    const int k4 = (t & 7) * 4, srow = t >> 3;
-    float s1[NT], s2[NT];
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) { s1[nt] = 0.f; s2[nt] = 0.f; }
+    const int k4 = fwd_k4(), srow = fwd_srow();
+    float s[NT][2] = {};
     float xr[4][3], xn[4][3];
     float4 br[NT];
     auto fetch_x = [&](long long r0, float (&dst)[4][3]) {
@@ -690,22 +580,14 @@ __global__ __launch_bounds__(kGemmThreads) __attribute__((amdgpu_waves_per_eu(2)
                 v.y = (rin && k + 1 < c0) ? lift_y(T, k + 1, xr[p][0], xr[p][1], xr[p][2]) : 0.f;
                 v.z = (rin && k + 2 < c0) ? lift_y(T, k + 2, xr[p][0], xr[p][1], xr[p][2]) : 0.f;
                 v.w = (rin && k + 3 < c0) ? lift_y(T, k + 3, xr[p][0], xr[p][1], xr[p][2]) : 0.f;
-                *reinterpret_cast<float4 *>(&As[(srow + 32 * p) * kFwdLS + k4]) = v;
+                *reinterpret_cast<float4 *>(&lds.As[(srow + 32 * p) * kFwdLS + k4]) = v;
             }
 #pragma unroll
-            for (int p = 0; p < NT; ++p) *reinterpret_cast<float4 *>(&Bs[(srow + 32 * p) * kFwdLS + k4]) = br[p];
+            for (int p = 0; p < NT; ++p) *reinterpret_cast<float4 *>(&lds.Bs[(srow + 32 * p) * kFwdLS + k4]) = br[p];
             __syncthreads();
             if (kc + kFwdKC < c0) fetch_b(kc + kFwdKC);
             else if (tile + gridDim.x < ntiles) { fetch_x((tile + gridDim.x) * kFwdRows, xn); fetch_b(0); }
-            const float *ap = As + (32 * wave + (lane & 31)) * kFwdLS + (lane >> 5);
-            const float *bp = Bs + (lane & 31) * kFwdLS + (lane >> 5);
-#pragma unroll 4
-            for (int s = 0; s < kFwdKC / 2; ++s) {
-                const float a = ap[2 * s];
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt)
-                    acc[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, bp[nt * 32 * kFwdLS + 2 * s], acc[nt], 0, 0, 0);
-            }
+            fwd_mfma_stage(lds, acc);
             __syncthreads();
         }
 #pragma unroll
@@ -717,34 +599,18 @@ __global__ __launch_bounds__(kGemmThreads) __attribute__((amdgpu_waves_per_eu(2)
             const int col = nt * 32 + (lane & 31);
 #pragma unroll
             for (int g = 0; g < 16; ++g) {
-                const long long row = row0 + 32 * wave + 8 * (g >> 2) + 4 * (lane >> 5) + (g & 3);
+                const long long row = fwd_d_row(row0, g);
                 const float v = acc[nt][g];
                 if (col < cout && row < rows) {
-                    const float sv = lift_elu(v);   // 32 expm1f per lane and tile cost as much as the tile's MFMAs; |difference| <= 6e-8
+                    const float sv = elu_hw(v);   // 32 expm1f per lane and tile cost as much as the tile's MFMAs; |difference| <= 6e-8
                     Z[row * cout + col] = out_bn ? oa[nt] * (sv - om[nt]) + ob[nt] : v;   // the apply pass's own expression
-                    s1[nt] += sv;
-                    s2[nt] += sv * sv;
+                    s[nt][0] += sv;
+                    s[nt][1] += sv * sv;
                 }
             }
         }
     }
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) {
-        s1[nt] += __shfl_xor(s1[nt], 32);
-        s2[nt] += __shfl_xor(s2[nt], 32);
-        if (lane < 32) {
-            red[wave][nt * 32 + lane][0] = s1[nt];
-            red[wave][nt * 32 + lane][1] = s2[nt];
-        }
-    }
-    __syncthreads();
-    for (int col = t; col < cout; col += kGemmThreads) {
-        float a = red[0][col][0], b = red[0][col][1];
-#pragma unroll
-        for (int w = 1; w < 4; ++w) { a += red[w][col][0]; b += red[w][col][1]; }
-        partial[static_cast<size_t>(col) * kBnMaxBlocks + blockIdx.x] = a;
-        partial[static_cast<size_t>(cout + col) * kBnMaxBlocks + blockIdx.x] = b;
-    }
+    col_sums_store(lds, s, cout, partial);
 }
 
 // dW1 partial tiles = dz1^T y0 with y0 generated from x while it is staged (the wgrad_kernel above with its X operand rebuilt)
@@ -756,103 +622,25 @@ __global__ __launch_bounds__(kGemmThreads) void lift_wgrad_kernel(long long rows
                                                                   const float *__restrict__ mean0, const float *__restrict__ invstd0,
                                                                   float *__restrict__ partial)
 {
-    constexpr int TM = 64 * WM, TN = 64 * WN;
-    constexpr int GS = TM + 32, XS = TN + 32;
-    constexpr int GC4 = TM / 4, XC4 = TN / 4;
-    constexpr int GPASS = kGemmRowsPerStage * GC4 / kGemmThreads, XPASS = kGemmRowsPerStage * XC4 / kGemmThreads;
-    constexpr int GROWS = kGemmThreads / GC4, XROWS = kGemmThreads / XC4;
-    __shared__ float Gs[kGemmRowsPerStage * GS];
-    __shared__ float Xs[kGemmRowsPerStage * XS];
+    using Q = WgradTile<WM, WN>;
+    __shared__ typename Q::Lds lds;
     __shared__ LiftTab T;
-
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int wm = wave & 1, wn = wave >> 1;
-    const int tile_m = blockIdx.x % mtiles, tile_n = blockIdx.x / mtiles;
-    const long long r0 = blockIdx.y * rows_per_chunk;
-    const long long r1 = r0 + rows_per_chunk < rows ? r0 + rows_per_chunk : rows;
+    const Q q(rows, mtiles, rows_per_chunk);
     lift_tab_load(T, c0, w0, gamma0, beta0, mean0, invstd0);
     __syncthreads();
-
-    const int gcol = tile_m * TM + (t % GC4) * 4, grow = t / GC4;
-    const int xcol = tile_n * TN + (t % XC4) * 4, xrow = t / XC4;
     const bool vec = cout % 4 == 0 && reinterpret_cast<uintptr_t>(G) % 16 == 0;
 
-    f32x16 acc[WM][WN];
-#pragma unroll
-    for (int i = 0; i < WM; ++i)
-#pragma unroll
-        for (int j = 0; j < WN; ++j)
-#pragma unroll
-            for (int g = 0; g < 16; ++g) acc[i][j][g] = 0.f;
-
-    float4 gr[GPASS];
-    float xr[XPASS][3];
+    float4 gr[Q::GPASS];
+    float xr[Q::XPASS][3];
     auto fetch = [&](long long rt) {
 #pragma unroll
-        for (int p = 0; p < GPASS; ++p)
-            gr[p] = vec ? load4_guarded<true>(G, rt + grow + p * GROWS, r1, gcol, cout) : load4_guarded<false>(G, rt + grow + p * GROWS, r1, gcol, cout);
+        for (int p = 0; p < Q::GPASS; ++p)
+            gr[p] = vec ? load4_guarded<true>(G, rt + q.grow + p * Q::GROWS, q.r1, q.gcol, cout) : load4_guarded<false>(G, rt + q.grow + p * Q::GROWS, q.r1, q.gcol, cout);
 #pragma unroll
-        for (int p = 0; p < XPASS; ++p) {
-            const long long row = rt + xrow + p * XROWS;
-            const bool ok = row < r1;
-            const float *px = x3 + (ok ? row : 0) * 3;
-            const float a = px[0], b = px[1], c = px[2];
-            xr[p][0] = ok ? a : 0.f; xr[p][1] = ok ? b : 0.f; xr[p][2] = ok ? c : 0.f;
-        }
+        for (int p = 0; p < Q::XPASS; ++p) lift_load_x(x3, rt + q.xrow + p * Q::XROWS, q.r1, xr[p]);
     };
-    fetch(r0);
-    for (long long rt = r0; rt < r1; rt += kGemmRowsPerStage) {
-#pragma unroll
-        for (int p = 0; p < GPASS; ++p)
-            *reinterpret_cast<float4 *>(&Gs[(grow + p * GROWS) * GS + (t % GC4) * 4]) = gr[p];
-#pragma unroll
-        for (int p = 0; p < XPASS; ++p) {
-            const bool rin = rt + xrow + p * XROWS < r1;
-            float4 v;
-            v.x = (rin && xcol < c0) ? lift_y(T, xcol, xr[p][0], xr[p][1], xr[p][2]) : 0.f;
-            v.y = (rin && xcol + 1 < c0) ? lift_y(T, xcol + 1, xr[p][0], xr[p][1], xr[p][2]) : 0.f;
-            v.z = (rin && xcol + 2 < c0) ? lift_y(T, xcol + 2, xr[p][0], xr[p][1], xr[p][2]) : 0.f;
-            v.w = (rin && xcol + 3 < c0) ? lift_y(T, xcol + 3, xr[p][0], xr[p][1], xr[p][2]) : 0.f;
-            *reinterpret_cast<float4 *>(&Xs[(xrow + p * XROWS) * XS + (t % XC4) * 4]) = v;
-        }
-        __syncthreads();
-        if (rt + kGemmRowsPerStage < r1) fetch(rt + kGemmRowsPerStage);
-        const float *ga = Gs + (lane >> 5) * GS + wm * 32 * WM + (lane & 31);
-        const float *xb = Xs + (lane >> 5) * XS + wn * 32 * WN + (lane & 31);
-        float a[2][WM], b[2][WN];
-#pragma unroll
-        for (int i = 0; i < WM; ++i) a[0][i] = ga[i * 32];
-#pragma unroll
-        for (int j = 0; j < WN; ++j) b[0][j] = xb[j * 32];
-#pragma unroll
-        for (int s = 0; s < kGemmRowsPerStage / 2; ++s) {
-            const int cur = s & 1, nxt = cur ^ 1;
-            if (s + 1 < kGemmRowsPerStage / 2) {
-#pragma unroll
-                for (int i = 0; i < WM; ++i) a[nxt][i] = ga[2 * (s + 1) * GS + i * 32];
-#pragma unroll
-                for (int j = 0; j < WN; ++j) b[nxt][j] = xb[2 * (s + 1) * XS + j * 32];
-            }
-#pragma unroll
-            for (int i = 0; i < WM; ++i)
-#pragma unroll
-                for (int j = 0; j < WN; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[cur][i], b[cur][j], acc[i][j], 0, 0, 0);
-        }
-        __syncthreads();
-    }
-    float *out = partial + static_cast<size_t>(blockIdx.y) * cout * c0;
-#pragma unroll
-    for (int i = 0; i < WM; ++i)
-#pragma unroll
-        for (int j = 0; j < WN; ++j) {
-            const int k = tile_n * TN + wn * 32 * WN + j * 32 + (lane & 31);
-#pragma unroll
-            for (int g = 0; g < 16; ++g) {
-                const int n = tile_m * TM + wm * 32 * WM + i * 32 + 8 * (g >> 2) + 4 * (lane >> 5) + (g & 3);
-                if (n < cout && k < c0) out[static_cast<size_t>(n) * c0 + k] = acc[i][j][g];
-            }
-        }
+    auto stage_x = [&](int p, long long rt) { return lift_y4(T, q.xcol, c0, rt + q.xrow + p * Q::XROWS < q.r1, xr[p]); };
+    wgrad_tile_loop<WM, WN>(lds, q, cout, c0, partial, gr, fetch, stage_x);
 }
 
 // dy0 = dz1 W1 is formed in the accumulators and never written.  PASS 0: the BatchNorm-backward sums of the first layer
@@ -867,10 +655,8 @@ __global__ __launch_bounds__(kGemmThreads) __attribute__((amdgpu_waves_per_eu(2)
     float *__restrict__ partial)
 {
     constexpr int NV = PASS == 0 ? 2 : 3;
-    __shared__ float As[kFwdRows * kFwdLS];
-    __shared__ float Bs[NT * 32 * kFwdLS];
-    __shared__ float red[4][NT * 32][NV];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    __shared__ FwdLds<NT, NV> lds;
+    const int t = threadIdx.x, lane = t & 63;
     // constants of this lane's output columns (channels of the first layer)
     float wx[NT], wy[NT], wz[NT], pa[NT], pmu[NT], pis[NT], c1[NT], c2[NT], acc_s[NT][NV];
     const float inv_r = 1.0f / static_cast<float>(rows);
@@ -887,7 +673,7 @@ __global__ __launch_bounds__(kGemmThreads) __attribute__((amdgpu_waves_per_eu(2)
         for (int v = 0; v < NV; ++v) acc_s[nt][v] = 0.f;
     }
     const bool vec = kdim % 4 == 0 && reinterpret_cast<uintptr_t>(DZ) % 16 == 0 && reinterpret_cast<uintptr_t>(WT) % 16 == 0;
-    const int k4 = (t & 7) * 4, srow = t >> 3;
+    const int k4 = fwd_k4(), srow = fwd_srow();
     float4 ar[4], br[NT];
     auto fetch = [&](long long r0, int kc) {
 #pragma unroll
@@ -907,26 +693,18 @@ __global__ __launch_bounds__(kGemmThreads) __attribute__((amdgpu_waves_per_eu(2)
             for (int g = 0; g < 16; ++g) acc[nt][g] = 0.f;
         for (int kc = 0; kc < kdim; kc += kFwdKC) {
 #pragma unroll
-            for (int p = 0; p < 4; ++p) *reinterpret_cast<float4 *>(&As[(srow + 32 * p) * kFwdLS + k4]) = ar[p];
+            for (int p = 0; p < 4; ++p) *reinterpret_cast<float4 *>(&lds.As[(srow + 32 * p) * kFwdLS + k4]) = ar[p];
 #pragma unroll
-            for (int p = 0; p < NT; ++p) *reinterpret_cast<float4 *>(&Bs[(srow + 32 * p) * kFwdLS + k4]) = br[p];
+            for (int p = 0; p < NT; ++p) *reinterpret_cast<float4 *>(&lds.Bs[(srow + 32 * p) * kFwdLS + k4]) = br[p];
             __syncthreads();
             if (kc + kFwdKC < kdim) fetch(row0, kc + kFwdKC);
             else if (tile + gridDim.x < ntiles) fetch((tile + gridDim.x) * kFwdRows, 0);
-            const float *ap = As + (32 * wave + (lane & 31)) * kFwdLS + (lane >> 5);
-            const float *bp = Bs + (lane & 31) * kFwdLS + (lane >> 5);
-#pragma unroll 4
-            for (int s = 0; s < kFwdKC / 2; ++s) {
-                const float a = ap[2 * s];
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt)
-                    acc[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, bp[nt * 32 * kFwdLS + 2 * s], acc[nt], 0, 0, 0);
-            }
+            fwd_mfma_stage(lds, acc);
             __syncthreads();
         }
 #pragma unroll
         for (int g = 0; g < 16; ++g) {
-            const long long row = row0 + 32 * wave + 8 * (g >> 2) + 4 * (lane >> 5) + (g & 3);
+            const long long row = fwd_d_row(row0, g);
             if (row >= rows) continue;
             const float x0 = x3[3 * row], x1 = x3[3 * row + 1], x2 = x3[3 * row + 2];
 #pragma unroll
@@ -934,12 +712,12 @@ __global__ __launch_bounds__(kGemmThreads) __attribute__((amdgpu_waves_per_eu(2)
                 if (nt * 32 + (lane & 31) >= c0) continue;
                 const float v = acc[nt][g];
                 const float z0 = lift_z(wx[nt], wy[nt], wz[nt], x0, x1, x2);
-                const float xhat = (lift_elu(z0) - pmu[nt]) * pis[nt];
+                const float xhat = (elu_hw(z0) - pmu[nt]) * pis[nt];
                 if (PASS == 0) {
                     acc_s[nt][0] += v;
                     acc_s[nt][1] += v * xhat;
                 } else {
-                    const float dz0 = pa[nt] * (v - c1[nt] - xhat * c2[nt]) * lift_elu_slope(z0);
+                    const float dz0 = pa[nt] * (v - c1[nt] - xhat * c2[nt]) * elu_hw_slope(z0);
                     acc_s[nt][0] += dz0 * x0;
                     acc_s[nt][1] += dz0 * x1;
                     acc_s[nt][NV - 1] += dz0 * x2;
@@ -947,23 +725,7 @@ __global__ __launch_bounds__(kGemmThreads) __attribute__((amdgpu_waves_per_eu(2)
             }
         }
     }
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-        for (int v = 0; v < NV; ++v) {
-            acc_s[nt][v] += __shfl_xor(acc_s[nt][v], 32);
-            if (lane < 32) red[wave][nt * 32 + lane][v] = acc_s[nt][v];
-        }
-    __syncthreads();
-    for (int col = t; col < c0; col += kGemmThreads) {
-#pragma unroll
-        for (int v = 0; v < NV; ++v) {
-            float a = red[0][col][v];
-#pragma unroll
-            for (int w = 1; w < 4; ++w) a += red[w][col][v];
-            partial[(static_cast<size_t>(v) * c0 + col) * kBnMaxBlocks + blockIdx.x] = a;
-        }
-    }
+    col_sums_store(lds, acc_s, c0, partial);
 }
 
 // out[row] = sum over blocks of partial[row][blk] (fp64 tree, a workgroup per row)
@@ -1043,9 +805,7 @@ static int linear_wgrad_impl(long long rows, int cout, int cin, const float *gra
     else HF_WGRAD_V(1, 1);
 #undef HF_WGRAD_V
 #undef HF_WGRAD
-    const int total = cout * cin;
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(div_up(total, 64)), dim3(64 * kWredGroups), 0, st, total, p.chunks, partial,
-                       grad_weight);
+    launch_partial_reduce(cout * cin, p.chunks, partial, grad_weight, st);
     return launch_status();
 }
 
@@ -1322,8 +1082,7 @@ HF_API int hf_lift_elu_bn_bwd(long long rows, int c0, int c1, const float *x3, c
     else if (p.wn == 2) HF_LIFT_WG(1, 2);
     else HF_LIFT_WG(1, 1);
 #undef HF_LIFT_WG
-    const int total = c1 * c0;
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(div_up(total, 64)), dim3(64 * kWredGroups), 0, st, total, p.chunks, wpartial, grad_w1);
+    launch_partial_reduce(c1 * c0, p.chunks, wpartial, grad_w1, st);
     // the first layer's BatchNorm-backward sums, then its weight gradient: dy0 = dz1 W1 rebuilt in the accumulators both times
     const long long ntiles = (rows + kFwdRows - 1) / kFwdRows;
     const int nt = div_up(c0, 32);

@@ -135,9 +135,16 @@ __device__ __forceinline__ float ord2f(unsigned o)
     return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
 }
 
-// tf.nn.elu and its slope (pointfly.py:480-497: the activation of every PointCNN layer, applied BEFORE the batch norm)
+// tf.nn.elu and its slope (pointfly.py:480-497: the activation of every PointCNN layer, applied BEFORE the batch norm).  Three
+// forms of it exist, and a layer's forward, statistics and backward all use the same one:
+//   elu_fwd     expm1f (~30 instructions): the fused dense layers of gemm.hip (linear_fwd_kernel / linear_bwd_kernel with `elu`)
+//   elu_hw      exp(x) - 1 on the hardware exponential, TensorFlow's own formula (Eigen: x < 0 ? exp(x) - 1 : x), two instructions:
+//               the lifting chain of gemm.hip and the single-launch BatchNorm kernels for short tensors of mlp.hip
+//   elu_stream  (mlp.hip) the same formula on exp2, branch-free: the streaming BatchNorm passes over the tall tensors
 __device__ __forceinline__ float elu_fwd(float x) { return x > 0.0f ? x : expm1f(x); }
 __device__ __forceinline__ float elu_slope(float x) { return x > 0.0f ? 1.0f : expf(x); }
+__device__ __forceinline__ float elu_hw(float x) { return x > 0.0f ? x : __expf(x) - 1.0f; }
+__device__ __forceinline__ float elu_hw_slope(float x) { return x > 0.0f ? 1.0f : __expf(x); }
 
 // exclusive prefix sum of one int per thread over a 1024-thread workgroup; `wsum` = 16 ints of LDS
 __device__ __forceinline__ int block_exclusive_scan(int v, int *wsum, int *total)

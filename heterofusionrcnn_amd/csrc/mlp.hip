@@ -488,9 +488,8 @@ __global__ __launch_bounds__(256) void bn_colsum_finalize_kernel(int c, int nblk
 // No inter-workgroup traffic, no partials in memory.
 // ------------------------------------------------------------------------------------------
 // the single-launch kernels run ~4 waves per CU on a handful of CUs, so the activation's instruction count shows: exp(x) - 1 on
-// the hardware exponential (TensorFlow's own formula for tf.nn.elu, relu_op_functor.h; the lifting kernels of gemm.hip use it
-// too) and its gradient from the OUTPUT, (y + 1) dy for y <= 0, as TensorFlow's EluGrad does -- one v_exp_f32 per element
-__device__ __forceinline__ float elu_hw(float x) { return x > 0.0f ? x : __expf(x) - 1.0f; }
+// the hardware exponential (elu_hw of hf_common.h) and its gradient from the OUTPUT, (y + 1) dy for y <= 0, as TensorFlow's EluGrad
+// does -- one v_exp_f32 per element
 __device__ __forceinline__ float elu_slope_from_output(float y) { return y > 0.0f ? 1.0f : y + 1.0f; }
 
 constexpr int kBnSmallRowsPerThread = 8;

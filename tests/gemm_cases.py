@@ -18,7 +18,7 @@ product library; a diagnostic build reads HF_GEMM_ROUNDS, which the GPU tests th
 Rounding bounds.  u = 2^-24.  Every bound below has the form  c * u * M (+ propagated input error), M being the same formula
 evaluated in fp64 with every operand replaced by its magnitude, and c the number of fp32 roundings on the longest path to the
 element; each reference function derives its c in its docstring.  The two transcendental paths whose rounding cannot be read
-from the code (expm1f of elu_fwd, exp(x) - 1 on the hardware exponential of lift_elu) are given 4 x the error that a plain fp32
+from the code (expm1f of elu_fwd, exp(x) - 1 on the hardware exponential of elu_hw) are given 4 x the error that a plain fp32
 torch evaluation of the same formula makes against fp64 on the same inputs (ELU_FACTOR; measured at run time on the host by
 elu_abs_error; at the N(0,1)-scale inputs of the cases that measurement is 3.0e-8 .. 6.0e-8 for both formulas, i.e. about u)."""
 import torch
@@ -352,7 +352,7 @@ def relu_margin(z, gamma, beta, mean, invstd):
 
 def elu_abs_error(x32, lift):
     """max |fp32 torch evaluation - fp64| of the ELU formula the kernel uses, on the same inputs, on the host: expm1 (elu_fwd) or
-    exp(x) - 1 (lift_elu); the kernels get ELU_FACTOR times this"""
+    exp(x) - 1 (elu_hw); the kernels get ELU_FACTOR times this"""
     x32 = x32.detach().float().cpu()
     neg = x32[x32 <= 0]
     if neg.numel() == 0:

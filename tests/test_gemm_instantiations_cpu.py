@@ -106,12 +106,15 @@ def test_two_workgroups_fit_a_compute_unit(table):
             assert f["lds"] <= LDS_PER_CU // 2, (name, args, f["lds"])
 
 
-def render(table):
-    lines = ["# Template instantiations of csrc/gemm.hip", "",
-             "Compiled for gfx950 with the Makefile's flags (`-O3 -ffp-contract=off`); produced by",
-             "`python tests/test_gemm_instantiations_cpu.py`.  NT >= 5 spills: the evidence behind the routing thresholds",
-             "`FUSED_FWD_MAX_COUT = 224` and `cin <= 160` of `heterofusionrcnn_amd/mlp.py`.", "",
-             "| kernel | template arguments | LDS bytes | VGPRs | spilled VGPRs | scratch bytes |", "|---|---|---:|---:|---:|---:|"]
+def render(table, source="gemm.hip"):
+    if source == "gemm.hip":
+        lines = ["# Template instantiations of csrc/gemm.hip", "",
+                 "Compiled for gfx950 with the Makefile's flags (`-O3 -ffp-contract=off`); produced by",
+                 "`python tests/test_gemm_instantiations_cpu.py`.  NT >= 5 spills: the evidence behind the routing thresholds",
+                 "`FUSED_FWD_MAX_COUT = 224` and `cin <= 160` of `heterofusionrcnn_amd/mlp.py`.", ""]
+    else:
+        lines = ["## csrc/%s" % source, ""]
+    lines += ["| kernel | template arguments | LDS bytes | VGPRs | spilled VGPRs | scratch bytes |", "|---|---|---:|---:|---:|---:|"]
     for name, args, f in table:
         lines.append("| `%s` | %s | %d | %d | %d | %d |" % (name, ", ".join(str(a).lower() for a in args) or "-", f["lds"], f["vgpr"],
                                                            f["spill"], f["scratch"]))
@@ -122,3 +125,5 @@ def render(table):
 if __name__ == "__main__":
     with tempfile.TemporaryDirectory() as d:
         print(render(kernel_table(compile_to_assembly(d))))
+        print()
+        print(render(kernel_table(compile_to_assembly(d, "fp_linear.hip")), "fp_linear.hip"))
