@@ -138,6 +138,7 @@ _SIGNATURES = {
     "hf_kitti_eval_overlaps": [_i, _vp, _vp, _vp, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, _i, _i, _vp, _vp, _vp, _vp],
     "hf_kitti_eval": [_i, _vp, _vp, _vp, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, _i, _i] + [_vp] * 6 + [_i, _i]
                      + [_vp] * 7 + [_sz, _vp],
+    "hf_kitti_result_boxes": [_i, ctypes.c_longlong] + [_vp] * 5 + [_f, _vp, _vp, _vp],
     "hf_rpn_batch_points_workspace": [_i, ctypes.c_longlong, ctypes.c_longlong],
     "hf_rpn_batch_points": [_i, _i, ctypes.c_longlong, ctypes.c_longlong] + [_vp] * 12 + [_sz, _vp],
     "hf_rpn_point_labels": [_i, _i, _i] + [_vp] * 4 + [_f, _vp, _vp, _vp],

@@ -1,0 +1,186 @@
+"""Detect from KITTI files with both trained models: python -m heterofusionrcnn_amd.detect DATASET_DIR RPN.pt RCNN.pt OUT_DIR
+[--split val] [--config rpn_multiclass] [--batch 8] [--seed 0] [--workers 8] [--score-threshold 0.1] [--handoff-rounding]
+[--host-rows] [--eval]
+
+The reference's `run_inference.py` over both stages (hf/core/evaluator.py:934-1065 for the first, :300-420 and
+evaluator_utils.py:88-166 for the second), without the hand-off on disk: RPN.pt is what train_rpn --save (or a checkpoint of
+it) holds, RCNN.pt what train_rcnn --save (or a checkpoint of it) holds, each with its own VGG pyramid; OUT_DIR/NAME.txt is a
+KITTI result file for EVERY frame of the split (empty when nothing is kept; frames without labels included).
+
+Per batch, on the device: the front half of export_rpn.export unchanged (read_export_frame one batch ahead, pack_frames,
+upload, hf_rpn_batch_points, geometry, hf_rpn_batch_image, propose: equal --seed and --batch give the point samples an export
+would have written), the in-memory hand-off (rcnn_data.handoff_in_memory; --handoff-rounding hands the proposals over with the
+three decimals of the file route), RcnnWithImageBranch.detect on the SAME resized image (computed once; the file route's val
+loader makes the same one: flip 0, jitter 0), then hf_kitti_result_boxes (inference.result_boxes) and one non-blocking copy
+of the batch's rows to pinned host memory.  Worker threads format and write the files behind an event, so the device waits
+neither for the disk nor for the text.  --host-rows keeps inference.write_frame_results (host projection, box by box) as
+the writer: the parity anchor, byte-identical to rcnn_data.run_rcnn_from_handoff on an export with the same seed and batch.
+"""
+import argparse
+import concurrent.futures
+import os
+import sys
+
+import numpy as np
+import torch
+
+from . import checkpoint as ckpt_mod
+from . import kitti_data as KD
+from .export_rpn import read_export_frame
+from .inference import CLASSES, RESULT_ROW_COLUMNS, result_boxes, result_rows, write_frame_results, write_result_rows
+from .rcnn_data import handoff_in_memory
+from .rcnn_train import RcnnTrainer
+from .train_rcnn import make_trainer
+from .train_rpn import CONFIGS, make_model
+
+
+def _state(src):
+    sd = torch.load(src, map_location="cpu") if isinstance(src, (str, os.PathLike)) else src
+    return ckpt_mod.model_state(sd)
+
+
+def rpn_fts_channels(rpn):
+    """the width of RpnModel.propose's rpn_fts: the backbone's output, plus the image channels under concat fusion"""
+    return rpn.backbone.out_channel + (rpn.cfg.img_channels if rpn.cfg.fusion == "concat" else 0)
+
+
+def load_models(rpn, rcnn, config="rpn_multiclass", img_conv=None):
+    """rpn: a train_rpn --save file, a checkpoint of it, a state_dict or a built model (RpnModel / RpnWithImageBranch);
+    rcnn: a train_rcnn --save file (the RcnnTrainer's state_dict), a checkpoint of it, a state_dict, an RcnnTrainer or an
+    RcnnWithImageBranch.  Files and state_dicts load with strict=True; the RCNN is sized from the loaded RPN.
+    -> (the RPN module, the RcnnWithImageBranch)"""
+    if isinstance(rpn, torch.nn.Module):
+        net = rpn
+    else:
+        net, _ = make_model(config, img_conv)
+        net.load_state_dict(_state(rpn), strict=True)
+    if isinstance(rcnn, torch.nn.Module):
+        second = rcnn.model if isinstance(rcnn, RcnnTrainer) else rcnn
+    else:
+        trainer = make_trainer(rpn_fts_channels(net.rpn if hasattr(net, "img_net") else net), img_conv)
+        trainer.load_state_dict(_state(rcnn), strict=True)
+        second = trainer.model
+    return net, second
+
+
+def _write_rows(out_dir, names, counts, host, event, classes):
+    """worker thread: wait for the batch's copy, write its files from the device rows -> {name: rows written}"""
+    event.synchronize()
+    rows = host.numpy()
+    out, at = {}, 0
+    for name, n in zip(names, counts):
+        out[name] = write_result_rows(os.path.join(out_dir, name + ".txt"), rows[at:at + n], classes)
+        at += n
+    return out
+
+
+@torch.no_grad()
+def detect(dataset_dir, rpn, rcnn, out_dir, split="val", config="rpn_multiclass", batch=8, seed=0, workers=8, score_threshold=0.1,
+           handoff_rounding=False, host_rows=False, img_conv=None, num_points=16384, img_hw=(360, 1200), pre_nms_size=9000,
+           nms_thresh=0.8, post_nms_size=100, classes=CLASSES):
+    """rpn / rcnn: see load_models.  -> {name: rows written} for every frame of the split"""
+    net, second = load_models(rpn, rcnn, config, img_conv)
+    modes = (net.training, second.training)
+    net.eval()
+    second.eval()
+    with_image = hasattr(net, "img_net")
+    first = net.rpn if with_image else net
+    names = KD.read_split(dataset_dir, split)
+    os.makedirs(out_dir, exist_ok=True)
+    device = next(net.parameters()).device
+    rng_state = torch.tensor([int(seed), 0], dtype=torch.int64, device=device)
+    # a points-only RPN's export never calls hf_rpn_batch_image; the image the RCNN needs then counts its calls apart, so that
+    # the point samples stay the export's (without jitter the image draws nothing)
+    img_rng = rng_state if with_image else torch.tensor([int(seed), 0], dtype=torch.int64, device=device)
+    pool = concurrent.futures.ThreadPoolExecutor(max_workers=max(1, int(workers)))
+    ahead = concurrent.futures.ThreadPoolExecutor(max_workers=1)
+    writer = concurrent.futures.ThreadPoolExecutor(max_workers=2)
+    chunks = [names[i:i + batch] for i in range(0, len(names), batch)]
+    read = lambda ch: list(pool.map(lambda n: read_export_frame(dataset_dir, n, list(classes), img_hw), ch))
+    staging = [KD._Staging(), KD._Staging()]
+    host_bufs = [None, None]
+    writes = [None, None]
+    pending = ahead.submit(read, chunks[0]) if chunks else None
+    written = {}
+    try:
+        for bi, chunk in enumerate(chunks):
+            frames = pending.result()
+            st = staging[bi % 2]
+            if st.event is not None:
+                st.event.synchronize()
+            packed = KD.pack_frames(frames, st)
+            points, images, meta = KD.upload(packed, device)
+            st.event = torch.cuda.Event()
+            st.event.record()
+            pending = ahead.submit(read, chunks[bi + 1]) if bi + 1 < len(chunks) else None
+            xyz, inten, _, _ = KD.batch_points(points, meta["offsets"], meta["velo_to_rect"], meta["p2"], meta["wh"], meta["flip"],
+                                               rng_state, num_points, packed["max_frame_points"])
+            geo = first.geometry(xyz)
+            image, _ = KD.batch_image(images, meta["img_offsets"], meta["wh"], meta["flip"], meta["jitter"], img_rng, img_hw,
+                                      packed["max_pixels"])
+            if with_image:
+                out = first.propose(xyz, inten, geo, net.img_net(image), meta["calib"], pre_nms_size, nms_thresh, post_nms_size)
+            else:
+                out = first.propose(xyz, inten, geo, None, None, pre_nms_size, nms_thresh, post_nms_size)
+            h = handoff_in_memory(out, xyz, inten, handoff_rounding)
+            dets, _ = second.detect(h["xyz"], h["rpn_fts"], h["intensity"], h["fg_mask"], h["proposals"], image, meta["calib"])
+            fnames = [f["name"] for f in frames]
+            if host_rows:
+                for f, det in zip(frames, dets):
+                    written[f["name"]] = write_frame_results(os.path.join(out_dir, f["name"] + ".txt"), det,
+                                                             np.asarray(f["p2"], np.float32), f["wh"], score_threshold, classes)
+                continue
+            res = result_boxes(dets, meta["p2"], meta["wh"], score_threshold)
+            rows = result_rows(res)
+            # the pinned buffer of this parity is free once its last writer has finished
+            if writes[bi % 2] is not None:
+                written.update(writes[bi % 2].result())
+            if host_bufs[bi % 2] is None or host_bufs[bi % 2].numel() < rows.numel():
+                host_bufs[bi % 2] = torch.empty((rows.numel() * 5 // 4 + RESULT_ROW_COLUMNS,), dtype=torch.float64).pin_memory()
+            host = host_bufs[bi % 2][:rows.numel()].view(rows.shape)
+            host.copy_(rows, non_blocking=True)
+            done = torch.cuda.Event()
+            done.record()
+            writes[bi % 2] = writer.submit(_write_rows, out_dir, fnames, res["counts"], host, done, classes)
+        for w in writes:
+            if w is not None:
+                written.update(w.result())
+    finally:
+        ahead.shutdown(wait=True)
+        pool.shutdown(wait=True)
+        writer.shutdown(wait=True)
+        net.train(modes[0])
+        second.train(modes[1])
+    return written
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(prog="python -m heterofusionrcnn_amd.detect",
+                                 description="Run a trained RPN (train_rpn --save) and a trained RCNN (train_rcnn --save) over a "
+                                             "split and write one KITTI result file per frame to OUT_DIR.")
+    ap.add_argument("dataset_dir")
+    ap.add_argument("rpn", help="the state_dict saved by train_rpn --save, or a checkpoint file (ckpt-NNNNNNNN.pt)")
+    ap.add_argument("rcnn", help="the state_dict saved by train_rcnn --save, or a checkpoint file")
+    ap.add_argument("out_dir")
+    ap.add_argument("--split", default="val", help="a list file, or NAME for NAME.txt next to or inside DATASET_DIR")
+    ap.add_argument("--config", choices=CONFIGS, default="rpn_multiclass", help="the RPN's config")
+    ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--seed", type=int, default=0, help="seed of the point sampling")
+    ap.add_argument("--workers", type=int, default=8, help="host threads that read and decode the files")
+    ap.add_argument("--score-threshold", type=float, default=0.1)
+    ap.add_argument("--handoff-rounding", action="store_true",
+                    help="hand the proposals over with three decimals, as the on-disk hand-off does")
+    ap.add_argument("--host-rows", action="store_true", help="project and filter the boxes on the host (write_frame_results)")
+    ap.add_argument("--eval", action="store_true", help="then evaluate OUT_DIR against DATASET_DIR/label_2 (kitti_eval)")
+    args = ap.parse_args(argv)
+    written = detect(args.dataset_dir, args.rpn, args.rcnn, args.out_dir, args.split, args.config, args.batch, args.seed,
+                     args.workers, args.score_threshold, args.handoff_rounding, args.host_rows)
+    print("done: %d frames, %d rows" % (len(written), sum(written.values())))
+    if args.eval:
+        from . import kitti_eval
+        return kitti_eval.main([os.path.join(args.dataset_dir, "label_2"), args.out_dir])
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

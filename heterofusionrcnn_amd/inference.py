@@ -10,6 +10,8 @@ BASELINE config 5 "Two-stage RPN -> tf_cropping -> RCNN inference on KITTI val, 
   result writing    score threshold (eval_config kitti_score_threshold 0.1), 3-D boxes projected into the image, boxes that
                     leave the image or cover more than 80 % of it dropped, the rest truncated, KITTI label lines with alpha
                     -10, three decimals                      hf/core/evaluator_utils.py:18-166, box_3d_projector.py:88-163
+  device result rows  result_boxes: the same decisions and rectangles for every detection of a batch in one launch
+                    (hf_kitti_result_boxes, fp64), write_result_rows formatting the kept rows; detect.py writes with them
 
 Weights are random unless the caller loads its own (no checkpoint ships with the reference): the test checks the plumbing
 (files -> tensors -> detector -> files, frame ids, sharding), not detection quality.
@@ -139,6 +141,67 @@ def write_frame_results(path, det, p2, image_size, score_threshold=0.1, classes=
         b3.append(np.round(bx, 3))
         sc.append(round(float(s_), 3))
     kitti_io.write_kitti_results(path, types, np.asarray(b2).reshape(-1, 4), np.asarray(b3).reshape(-1, 7), sc)
+    return len(types)
+
+
+RESULT_ROW_COLUMNS = 14      # result_rows(): boxes2d (4), boxes3d (7), score, class, keep
+
+
+def result_boxes(dets, p2, image_wh, score_threshold=0.1):
+    """hf_kitti_result_boxes: what write_frame_results decides per box on the host, for every detection of a batch in one launch.
+    dets: the per-frame dicts {boxes (n_i,7), scores (n_i), classes (n_i)} RcnnModel.detect returns (device tensors); p2: the
+    ORIGINAL P2 of each frame, (B,3,4) / (B,12) as a tensor or array (rounded to float32 first, the values write_frame_results
+    receives); image_wh: (B,2) original (w, h); score_threshold as write_frame_results takes it.
+    -> dict: boxes2d (n,4) float64 truncated image rectangles, keep (n) bool (score >= round(threshold, 3) as float32 and the
+    rectangle neither outside the image nor over 80 % of it), boxes3d (n,7), scores (n), classes (n), frame (n) int32, counts
+    [n_i]; n = sum n_i, rows in frame order.  Nothing is read back from the device; the frame ids (4 n bytes), and p2 / image_wh
+    when they come as arrays, are uploaded from pageable host memory, a copy the runtime stages on the host."""
+    from . import _lib
+    from ._lib import check, dev_tensor, ptr, require, stream_ptr
+    b = len(dets)
+    require(b > 0, "result_boxes needs at least one frame")
+    counts = [int(d["boxes"].shape[0]) for d in dets]
+    n = sum(counts)
+    boxes = dev_tensor(torch.cat([d["boxes"].reshape(-1, 7) for d in dets]), torch.float32, "boxes")
+    scores = dev_tensor(torch.cat([d["scores"].reshape(-1) for d in dets]), torch.float32, "scores")
+    classes = torch.cat([d["classes"].reshape(-1) for d in dets])
+    dev = boxes.device
+    frame = torch.from_numpy(np.repeat(np.arange(b, dtype=np.int32), counts)).to(dev, non_blocking=True)
+    if torch.is_tensor(p2):
+        p2d = p2.to(device=dev, dtype=torch.float32).to(torch.float64).reshape(-1).contiguous()
+    else:
+        p2d = torch.from_numpy(np.asarray(p2, dtype=np.float32).astype(np.float64).reshape(-1)).to(dev, non_blocking=True)
+    if torch.is_tensor(image_wh):
+        wh = image_wh.to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
+    else:
+        wh = torch.from_numpy(np.asarray(image_wh, dtype=np.int32).reshape(-1)).to(dev, non_blocking=True)
+    require(p2d.numel() == 12 * b and wh.numel() == 2 * b, "p2 must be (B, 3, 4) and image_wh (B, 2), B = len(dets)")
+    boxes2d = torch.empty((n, 4), dtype=torch.float64, device=dev)
+    keep = torch.empty((n,), dtype=torch.uint8, device=dev)
+    score_min = float(np.float32(round(score_threshold, 3)))      # the float32 NumPy compares a float32 array against
+    check(_lib.lib().hf_kitti_result_boxes(b, n, ptr(boxes), ptr(scores), ptr(frame), ptr(p2d), ptr(wh), score_min, ptr(boxes2d),
+                                           ptr(keep), stream_ptr()), "kitti_result_boxes")
+    return {"boxes2d": boxes2d, "keep": keep.bool(), "boxes3d": boxes, "scores": scores, "classes": classes, "frame": frame,
+            "counts": counts}
+
+
+def result_rows(res):
+    """result_boxes' outputs as ONE (n, RESULT_ROW_COLUMNS) float64 device tensor [boxes2d, boxes3d, score, class, keep] (every
+    float32 is exact in float64): one copy takes a batch to the host"""
+    return torch.cat([res["boxes2d"], res["boxes3d"].double(), res["scores"].double().unsqueeze(1),
+                      res["classes"].double().unsqueeze(1), res["keep"].double().unsqueeze(1)], dim=1)
+
+
+def write_result_rows(path, rows, classes=CLASSES):
+    """one KITTI result file from a frame's rows of result_rows() (a host array): the kept rows, rounded as write_frame_results
+    rounds them (np.round(., 3) of the float64 image box and of the float32 3-D box, round(score, 3)) -> rows written"""
+    rows = np.asarray(rows, dtype=np.float64).reshape(-1, RESULT_ROW_COLUMNS)
+    rows = rows[rows[:, 13] != 0]
+    types = [classes[int(c) - 1] for c in rows[:, 12]]
+    b2 = np.round(rows[:, 0:4], 3)
+    b3 = np.round(rows[:, 4:11].astype(np.float32), 3)
+    sc = [round(float(s), 3) for s in rows[:, 11]]
+    kitti_io.write_kitti_results(path, types, b2, b3, sc)
     return len(types)
 
 

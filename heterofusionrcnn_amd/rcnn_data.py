@@ -95,6 +95,31 @@ def box3d_iou_matrix(proposals, proposal_count, gt, gt_count):
     return iou
 
 
+# ------------------------------------------------------------------------------------------------ the hand-off in memory
+def round_like_handoff_file(x):
+    """float32 tensor (host or device) -> the float32 the second stage reads after the value went through
+    proposals_and_scores/NAME.txt ("%.3f", kitti_io.save_proposals_and_scores) and back (np.loadtxt, then float32):
+    rint(double(x) * 1000.0) / 1000.0 in fp64, cast to float32.  Bit for bit the file route's value, because
+      - a float32 (24 significant bits) times 1000 (10 bits) has at most 34 significant bits: the product is exact in fp64;
+      - rint and glibc's "%.3f" both round that exact value half to even, so both arrive at the same integer k of thousandths;
+      - k / 1000.0 is the correctly rounded double of k/1000 (IEEE division), and so is what loadtxt parses from the decimal
+        string, which denotes k/1000 exactly; the cast to float32 is the same on both routes;
+      - a value that rounds to zero from below, such as -0.0004, is "-0.000" in the file and -0.0 here."""
+    return (torch.round(x.to(torch.float64) * 1000.0) / 1000.0).to(torch.float32)
+
+
+def handoff_in_memory(rpn_out, xyz, intensity, handoff_rounding=False):
+    """What RpnModel.propose returned (proposals, rpn_fts, fg_mask) with the cloud it ran on -> the leading arguments of
+    RcnnModel.detect as a dict (xyz, rpn_fts, intensity, fg_mask, proposals), the tensors used in place: no
+    hf_rpn_handoff_pack / hf_rcnn_batch_inputs round trip and no copy of the (B,P,c) feature tensor.
+    handoff_rounding: the proposals as the file route hands them over, three decimals (round_like_handoff_file); the default
+    is the unrounded boxes, the better input and what two_stage.TwoStageDetector passes."""
+    proposals = rpn_out["proposals"]
+    if handoff_rounding:
+        proposals = round_like_handoff_file(proposals)
+    return {"xyz": xyz, "rpn_fts": rpn_out["rpn_fts"], "intensity": intensity, "fg_mask": rpn_out["fg_mask"], "proposals": proposals}
+
+
 # ------------------------------------------------------------------------------------------------ host reading
 def handoff_paths(handoff_dir, name):
     return {"proposals": os.path.join(handoff_dir, "proposals_and_scores", name + ".txt"),

@@ -761,6 +761,24 @@ int hf_kitti_eval(int n_frames, const long long *gt_off, const long long *det_of
                   int compute_aos, double *thresholds, int *n_thresholds, int *counts, double *precision, double *aos,
                   double *aos_ground, void *workspace, size_t workspace_bytes, hf_stream_t stream);
 
+/* ------------------------------------------------------------------ KITTI result rows (csrc/kitti_result.hip) */
+
+/* The image rectangle and the keep flag of every detection of a batch: the per-box loop of the result writer
+ * (hf/core/evaluator_utils.py:88-166, box_3d_projector.project_to_image_space(truncate=True, discard_before_truncation=True)
+ * :88-163) in one launch, one thread per detection.  All of it is float64, in the host writer's operation order
+ * (inference.project_box3d_to_image, kitti_io.project_to_image).
+ * b frames; n detections, flat: boxes3d (n, 7) float32 [x, y, z, l, w, h, ry], scores (n) float32, frame (n) int32 in [0, b);
+ * p2 (b, 12) fp64, the ORIGINAL P2 of each frame (float32 values promoted, as the host writer receives them); image_wh (b, 2)
+ * int32 the original image size.  Per detection: cos / sin of double(ry), the eight corners of compute_box_corners_3d in its
+ * order, [x y z 1] . P2^T, u / w and v / w, the bounding rectangle (a NaN propagates as in np.min / np.max); rejected when the
+ * rectangle lies outside the image (x1 > w, y1 > h, x2 < 0, y2 < 0) or is wider than 0.8 w or taller than 0.8 h.
+ * Outputs: boxes2d (n, 4) fp64 [x1, y1, x2, y2] truncated to [0, w] x [0, h] (written for every row; zeros for a frame id
+ * outside [0, b)); keep (n) uint8 = score >= score_min (fp32 comparison) and not rejected and the frame id is valid.
+ * b <= 0 or n < 0, or a NULL pointer with n > 0: HF_EINVAL, nothing launched; n == 0: HF_OK, nothing launched.  No allocation,
+ * no synchronisation, no atomics. */
+int hf_kitti_result_boxes(int b, long long n, const float *boxes3d, const float *scores, const int *frame, const double *p2,
+                          const int *image_wh, float score_min, double *boxes2d, unsigned char *keep, hf_stream_t stream);
+
 /* ------------------------------------------------------------------ RPN training batches (csrc/rpn_batch.hip) */
 
 /* The RPN's training sample (hf/datasets/kitti/kitti_dataset.py:291-440, a host NumPy loop in the reference) for b frames
