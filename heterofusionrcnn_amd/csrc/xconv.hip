@@ -248,7 +248,8 @@ constexpr int kNarrowMaxC = 64;
 //
 // `partial` != NULL (hf_depthwise_k_grad_ws): every chunk writes its K*c*M sums to partial[chunk][...] instead and a second
 // kernel adds the chunks in a fixed order -- 512 chunks x 512 atomics on the same 16 cache lines were 50 us of a 60 us call
-// for the X-transform's 8-channel layers, whatever the number of rows; deterministic as a bonus.
+// for the X-transform's 8-channel layers, whatever the number of rows; deterministic as a bonus: the row slots of a block meet in
+// a fixed order too (shuffles, or turns on the LDS slot), and tests/test_xconv_abi.py calls three times and compares the bits.
 template <int K, int M>
 __global__ __launch_bounds__(kXcThreads) void depthwise_dw_kernel(long long rows, int c, int rows_per_chunk,
                                                                  const float *__restrict__ x, const float *__restrict__ grad_y,
@@ -262,10 +263,6 @@ __global__ __launch_bounds__(kXcThreads) void depthwise_dw_kernel(long long rows
     const int t = static_cast<int>(threadIdx.x);
     const int cl = t % cw, ch = blockIdx.x * cw + cl, rs = t / cw;
     const bool live = ch < c && rs < nrs;
-    if (nrs > 1) {
-        for (int i = t; i < K * M * cw; i += kXcThreads) red[i] = 0.f;
-        __syncthreads();
-    }
     const long long r0 = static_cast<long long>(blockIdx.y) * rows_per_chunk + rs;
     const long long r1 = static_cast<long long>(blockIdx.y + 1) * rows_per_chunk < rows ? static_cast<long long>(blockIdx.y + 1) * rows_per_chunk : rows;
     float acc[K][M];
@@ -305,7 +302,6 @@ __global__ __launch_bounds__(kXcThreads) void depthwise_dw_kernel(long long rows
     const bool shuffle = (cw & (cw - 1)) == 0 && cw <= 32;
     if (shuffle) {
         const int lane = t & 63, wave = t >> 6;
-        __syncthreads();   // the zero fill above is not needed on this path, but every thread must be past it
 #pragma unroll
         for (int w = 0; w < K; ++w)
 #pragma unroll
@@ -328,13 +324,20 @@ __global__ __launch_bounds__(kXcThreads) void depthwise_dw_kernel(long long rows
         }
         return;
     }
-    if (live) {
+    // other channel counts: the row slots take turns on the channel's LDS slot, slot 0 first (it holds every channel: cw = c here),
+    // so the adds have a fixed order; LDS atomics did the same adds in whatever order the slots arrived
+    for (int s = 0; s < nrs; ++s) {
+        if (live && rs == s) {
 #pragma unroll
-        for (int w = 0; w < K; ++w)
+            for (int w = 0; w < K; ++w)
 #pragma unroll
-            for (int m = 0; m < M; ++m) atomicAdd(&red[(w * M + m) * cw + cl], acc[w][m]);
+                for (int m = 0; m < M; ++m) {
+                    float *slot = &red[(w * M + m) * cw + cl];
+                    *slot = s == 0 ? acc[w][m] : *slot + acc[w][m];
+                }
+        }
+        __syncthreads();
     }
-    __syncthreads();
     for (int i = t; i < K * M * cw; i += kXcThreads) {
         const int wm = i / cw, c2 = blockIdx.x * cw + i % cw;
         if (c2 < c) {
@@ -623,16 +626,18 @@ __global__ __launch_bounds__(kXcThreads) void xconv_dw_bwd_fw_kernel(long long r
     if (grad_wd) {
         // the waves of a block meet in LDS first: one global atomic per coefficient and BLOCK (per wave it was 8.4 M atomics on
         // 2080 addresses for the first encoder layer: 870 us for 140 us of memory traffic)
+        // The waves take turns, wave 0 first: a fixed order of adds (LDS atomics left it to the order the waves arrived in), so with
+        // wd_partial grad_wd is the same bits on every call.  The slots of dead lanes are neither written nor read.
         __shared__ float red[K * M][64];
-        for (int i = threadIdx.x; i < K * M * 64; i += kXcThreads) (&red[0][0])[i] = 0.f;
-        __syncthreads();
-        if (live) {
+        for (int wv = 0; wv < kXcThreads / 64; ++wv) {
+            if (wave == wv && live) {
 #pragma unroll
-            for (int k = 0; k < K; ++k)
+                for (int k = 0; k < K; ++k)
 #pragma unroll
-                for (int m = 0; m < M; ++m) atomicAdd(&red[k * M + m][lane], gw[k][m]);
+                    for (int m = 0; m < M; ++m) red[k * M + m][lane] = wv == 0 ? gw[k][m] : red[k * M + m][lane] + gw[k][m];
+            }
+            __syncthreads();
         }
-        __syncthreads();
         // wd_partial: the row chunks' sums are written out (wd_partial[row chunk][K*c*M]) and added in a fixed order by a second
         // kernel; else one global atomic per coefficient and block on grad_wd (zero-filled by the entry point)
         float *mine = wd_partial ? wd_partial + static_cast<size_t>(blockIdx.x) * K * c * M : nullptr;

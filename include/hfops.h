@@ -586,8 +586,9 @@ int hf_xconv_depthwise_grad(long long rows, int k, int c, int m, const float *x,
 int hf_depthwise_k_grad(long long rows, int k, int c, int m, const float *x, const float *w, const float *grad_y,
                         float *grad_x, float *grad_w, hf_stream_t stream);
 /* the same with a workspace (hf_depthwise_k_grad_workspace bytes): the row chunks' partial weight gradients are written out and
- * added in a fixed order instead of meeting in atomics on the same k*c*m addresses -- deterministic, and 4x faster for the
- * 8-channel layers of the X-transform where those atomics were the whole cost */
+ * added in a fixed order instead of meeting in atomics on the same k*c*m addresses -- deterministic (the row slots of a block
+ * meet in a fixed order too: the same bits on every call), and 4x faster for the 8-channel layers of the X-transform where those
+ * atomics were the whole cost */
 size_t hf_depthwise_k_grad_workspace(long long rows, int k, int c, int m);
 int hf_depthwise_k_grad_ws(long long rows, int k, int c, int m, const float *x, const float *w, const float *grad_y, float *grad_x,
                            float *grad_w, void *workspace, size_t workspace_bytes, hf_stream_t stream);
@@ -603,7 +604,8 @@ int hf_depthwise_k_grad_ws(long long rows, int k, int c, int m, const float *x, 
  * like hf_group_point_grad_gather; no atomics, no zero fill.  Any gradient may be NULL.  workspace
  * (hf_xconv_depthwise_gather_grad_workspace bytes, may be NULL), laid out as [gathered block's gradient][partial weight
  * gradients]: with it the row chunks' partial depthwise-weight gradients are added in a fixed order instead of meeting in atomics
- * (deterministic grad_wd).  grad_fts is rebuilt per table row from grad_out (nothing but the table is written), except at
+ * (deterministic grad_wd: the waves of a block add in a fixed order as well, so two calls give the same bits).
+ * grad_fts is rebuilt per table row from grad_out (nothing but the table is written), except at
  * the shapes for which xdw_fts_direct (csrc/xconv.hip, a function of the shape alone, with the measurements behind it) picks the
  * staged route: there the gathered block's gradient is written to the first region and summed per table row.  Same values on
  * both routes; on the direct route, and without a workspace, the first region is never touched. */
