@@ -104,6 +104,8 @@ _SIGNATURES = {
     "hf_lift_elu_fwd_eval_bn": [ctypes.c_longlong, _i, _i] + [_vp] * 12 + [_vp, _sz, _vp],
     "hf_lift_elu_bn_bwd_workspace": [ctypes.c_longlong, _i, _i],
     "hf_lift_elu_bn_bwd": [ctypes.c_longlong, _i, _i] + [_vp] * 12 + [_vp, _sz, _vp],
+    "hf_f32_to_bf16": [ctypes.c_longlong, _vp, _vp, _vp],
+    "hf_linear_bf16_fwd_eval": [ctypes.c_longlong, _i, _i] + [_vp] * 7 + [_i, _vp, _vp],
     "hf_project_gather": [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     "hf_project_gather_grad": [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
     "hf_fuse_concat": [ctypes.c_longlong, _i, _i, _vp, _vp, _vp, _vp, _vp],

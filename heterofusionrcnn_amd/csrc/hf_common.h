@@ -140,7 +140,15 @@ __device__ __forceinline__ float ord2f(unsigned o)
 //   elu_fwd     expm1f (~30 instructions): the fused dense layers of gemm.hip (linear_fwd_kernel / linear_bwd_kernel with `elu`)
 //   elu_hw      exp(x) - 1 on the hardware exponential, TensorFlow's own formula (Eigen: x < 0 ? exp(x) - 1 : x), two instructions:
 //               the lifting chain of gemm.hip and the single-launch BatchNorm kernels for short tensors of mlp.hip
-//   elu_stream  (mlp.hip) the same formula on exp2, branch-free: the streaming BatchNorm passes over the tall tensors
+//   elu_stream  the same formula on exp2, branch-free: the streaming BatchNorm passes over the tall tensors (mlp.hip) and the
+//               epilogue of the bf16 inference GEMM (linear_bf16.hip), which stands in for such a pass
+__device__ __forceinline__ float elu_stream(float x) { return x > 0.0f ? x : __builtin_amdgcn_exp2f(x * 1.44269504088896340736f) - 1.0f; }
+__device__ __forceinline__ float elu_stream(float x, float &slope)
+{
+    const float e = __builtin_amdgcn_exp2f(x * 1.44269504088896340736f);
+    slope = x > 0.0f ? 1.0f : e;
+    return x > 0.0f ? x : e - 1.0f;
+}
 __device__ __forceinline__ float elu_fwd(float x) { return x > 0.0f ? x : expm1f(x); }
 __device__ __forceinline__ float elu_slope(float x) { return x > 0.0f ? 1.0f : expf(x); }
 __device__ __forceinline__ float elu_hw(float x) { return x > 0.0f ? x : __expf(x) - 1.0f; }

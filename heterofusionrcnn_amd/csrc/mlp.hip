@@ -105,14 +105,7 @@ constexpr int kBnRelu = 1, kBnEluIn = 2;
 // at 64 channels x 10^6 rows was as long as the memory time itself; its slope is the same exponential (EluGrad: (y + 1) dy).
 constexpr int kBnUnroll = 4;
 
-// elu(x) and, on request, its slope, branch-free (select, no exec masking around the exponential)
-__device__ __forceinline__ float elu_stream(float x) { return x > 0.0f ? x : __builtin_amdgcn_exp2f(x * 1.44269504088896340736f) - 1.0f; }
-__device__ __forceinline__ float elu_stream(float x, float &slope)
-{
-    const float e = __builtin_amdgcn_exp2f(x * 1.44269504088896340736f);
-    slope = x > 0.0f ? 1.0f : e;
-    return x > 0.0f ? x : e - 1.0f;
-}
+// elu_stream (hf_common.h): elu(x) and, on request, its slope, branch-free (select, no exec masking around the exponential)
 
 // Dropout fused into the normalisation (pointfly's dense -> dropout, pointcnn.py:371-384, rpn_model.py:556-568; tf.layers.dropout
 // keeps an element with probability 1 - rate and scales it by 1 / (1 - rate)).  The framework form is a pass of its own in each

@@ -1,6 +1,6 @@
 """Detect from KITTI files with both trained models: python -m heterofusionrcnn_amd.detect DATASET_DIR RPN.pt RCNN.pt OUT_DIR
 [--split val] [--config rpn_multiclass] [--batch 8] [--seed 0] [--workers 8] [--score-threshold 0.1] [--handoff-rounding]
-[--host-rows] [--eval]
+[--host-rows] [--eval] [--precision {fp32,bf16}]
 
 The reference's `run_inference.py` over both stages (hf/core/evaluator.py:934-1065 for the first, :300-420 and
 evaluator_utils.py:88-166 for the second), without the hand-off on disk: RPN.pt is what train_rpn --save (or a checkpoint of
@@ -15,6 +15,8 @@ loader makes the same one: flip 0, jitter 0), then hf_kitti_result_boxes (infere
 of the batch's rows to pinned host memory.  Worker threads format and write the files behind an event, so the device waits
 neither for the disk nor for the text.  --host-rows keeps inference.write_frame_results (host projection, box by box) as
 the writer: the parity anchor, byte-identical to rcnn_data.run_rcnn_from_handoff on an export with the same seed and batch.
+--precision bf16 sends the wide dense layers of both stages to the bf16 matrix-core kernel (mlp.inference_precision; the heads that
+are decoded into scores and boxes stay fp32); the default, fp32, is the route described above, bit for bit.
 """
 import argparse
 import concurrent.futures
@@ -26,6 +28,7 @@ import torch
 
 from . import checkpoint as ckpt_mod
 from . import kitti_data as KD
+from . import mlp
 from .export_rpn import read_export_frame
 from .inference import CLASSES, RESULT_ROW_COLUMNS, result_boxes, result_rows, write_frame_results, write_result_rows
 from .rcnn_data import handoff_in_memory
@@ -77,8 +80,10 @@ def _write_rows(out_dir, names, counts, host, event, classes):
 @torch.no_grad()
 def detect(dataset_dir, rpn, rcnn, out_dir, split="val", config="rpn_multiclass", batch=8, seed=0, workers=8, score_threshold=0.1,
            handoff_rounding=False, host_rows=False, img_conv=None, num_points=16384, img_hw=(360, 1200), pre_nms_size=9000,
-           nms_thresh=0.8, post_nms_size=100, classes=CLASSES):
-    """rpn / rcnn: see load_models.  -> {name: rows written} for every frame of the split"""
+           nms_thresh=0.8, post_nms_size=100, classes=CLASSES, precision="fp32"):
+    """rpn / rcnn: see load_models.  precision: mlp.inference_precision for the duration of the call.
+    -> {name: rows written} for every frame of the split"""
+    scope = mlp.inference_precision(precision)
     net, second = load_models(rpn, rcnn, config, img_conv)
     modes = (net.training, second.training)
     net.eval()
@@ -102,6 +107,7 @@ def detect(dataset_dir, rpn, rcnn, out_dir, split="val", config="rpn_multiclass"
     writes = [None, None]
     pending = ahead.submit(read, chunks[0]) if chunks else None
     written = {}
+    scope.__enter__()
     try:
         for bi, chunk in enumerate(chunks):
             frames = pending.result()
@@ -149,12 +155,13 @@ def detect(dataset_dir, rpn, rcnn, out_dir, split="val", config="rpn_multiclass"
         ahead.shutdown(wait=True)
         pool.shutdown(wait=True)
         writer.shutdown(wait=True)
+        scope.__exit__(None, None, None)
         net.train(modes[0])
         second.train(modes[1])
     return written
 
 
-def main(argv=None):
+def build_parser():
     ap = argparse.ArgumentParser(prog="python -m heterofusionrcnn_amd.detect",
                                  description="Run a trained RPN (train_rpn --save) and a trained RCNN (train_rcnn --save) over a "
                                              "split and write one KITTI result file per frame to OUT_DIR.")
@@ -172,9 +179,15 @@ def main(argv=None):
                     help="hand the proposals over with three decimals, as the on-disk hand-off does")
     ap.add_argument("--host-rows", action="store_true", help="project and filter the boxes on the host (write_frame_results)")
     ap.add_argument("--eval", action="store_true", help="then evaluate OUT_DIR against DATASET_DIR/label_2 (kitti_eval)")
-    args = ap.parse_args(argv)
+    ap.add_argument("--precision", choices=mlp.PRECISIONS, default="fp32",
+                    help="bf16: the wide dense layers of both stages on the bf16 matrix cores (fp32 accumulation, fp32 output heads)")
+    return ap
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
     written = detect(args.dataset_dir, args.rpn, args.rcnn, args.out_dir, args.split, args.config, args.batch, args.seed,
-                     args.workers, args.score_threshold, args.handoff_rounding, args.host_rows)
+                     args.workers, args.score_threshold, args.handoff_rounding, args.host_rows, precision=args.precision)
     print("done: %d frames, %d rows" % (len(written), sum(written.values())))
     if args.eval:
         from . import kitti_eval

@@ -273,6 +273,94 @@ def _mfma_backward_pays(rows, cin, cout):
     return rows >= FUSED_FWD_MIN_ROWS and cin <= 160 and cout <= 256
 
 
+# ------------------------------------------------------------------------------------------------ bf16 inference
+# Inference precision of the wide dense layers, process-wide: "fp32" (default: every layer as before) or "bf16" (operands
+# rounded to bf16, exact products, fp32 accumulation: hf_linear_bf16_fwd_eval of csrc/linear_bf16.hip, with the layer's
+# eval-mode BatchNorm pass in its epilogue).  Consulted only for a layer in eval mode, with autograd off, on the device, whose shape
+# bf16_route_pays accepts: training, and a frozen BatchNorm inside a model that still trains, never see it.
+PRECISIONS = ("fp32", "bf16")
+_INFERENCE_PRECISION = ["fp32"]
+BF16_ROUTED_CALLS = [0]      # launches of the bf16 kernel so far (tests and probes read the difference)
+
+# The shapes the bf16 kernel takes: those where scripts/probes/bf16_linear_timing.py measured it faster than the fp32 library GEMM
+# plus the BatchNorm pass by more than the spread between repeats of the latter (profiles/bf16_inference_timing.json, "kernels" /
+# "routing").  That held for every GEMM shape of the two-stage batch with 2048 rows or more (2048 x 1280 x 1024: 38 us against 53;
+# 409600 x 2688 x 512: 2.1 ms against 7.9) and not for 800 x 11808 x 256 (269 us against 62: seven 128-row tiles, each walking all of
+# cin alone).  Nothing narrower than 228 outputs was measured: below 64 the matrix cores have little to win, so those stay fp32 too.
+# cin < 32 (coordinate branches, lifting chain, the 6-channel local MLP input) stays fp32 whatever was measured.
+BF16_MIN_ROWS = 2048
+BF16_MIN_CIN = 32
+BF16_MIN_COUT = 64
+
+
+def inference_precision_name():
+    return _INFERENCE_PRECISION[0]
+
+
+class inference_precision:
+    """with mlp.inference_precision("bf16"): ... -- the previous setting returns on exit"""
+
+    def __init__(self, precision):
+        if precision not in PRECISIONS:
+            raise ValueError("precision must be one of %s, got %r" % (PRECISIONS, precision))
+        self.precision = precision
+
+    def __enter__(self):
+        self.previous = _INFERENCE_PRECISION[0]
+        _INFERENCE_PRECISION[0] = self.precision
+        return self
+
+    def __exit__(self, *exc):
+        _INFERENCE_PRECISION[0] = self.previous
+        return False
+
+
+def bf16_route_pays(rows, cin, cout):
+    return rows >= BF16_MIN_ROWS and cin >= max(BF16_MIN_CIN, 32) and cout >= BF16_MIN_COUT
+
+
+def bf16_route(x, weight):
+    """does x (.., cin) times weight (cout, cin)^T take the bf16 kernel?  The caller has checked that its layer is in eval mode."""
+    if _INFERENCE_PRECISION[0] != "bf16" or torch.is_grad_enabled() or not x.is_cuda or x.dtype != torch.float32:
+        return False
+    cout, cin = weight.shape
+    return cin % 4 == 0 and cout % 4 == 0 and x.shape[-1] == cin and bf16_route_pays(x.numel() // cin, cin, cout)
+
+
+def _bf16_weight(weight):
+    """the bf16 copy of a weight (hf_f32_to_bf16), kept on the weight tensor between calls like BatchNormReLU.eval_invstd: the key
+    holds the tensor version (in-place writes, load_state_dict), the generation counter of raw-pointer writes, and the storage;
+    nothing is cached while a stream capture is running (the conversion becomes a node of the graph and is replayed)."""
+    capturing = torch.cuda.is_current_stream_capturing()
+    key = (weight._version, _STATS_GENERATION[0], weight.device, weight.data_ptr())
+    held = getattr(weight, "_hf_bf16", None) if not capturing else None
+    if held is not None and held[0] == key:
+        return held[1]
+    w = weight.detach().contiguous()
+    wb = torch.empty(w.shape, dtype=torch.bfloat16, device=w.device)
+    check(_lib.lib().hf_f32_to_bf16(w.numel(), ptr(w), ptr(wb), stream_ptr()), "f32_to_bf16")
+    if not capturing:
+        weight._hf_bf16 = (key, wb)
+    return wb
+
+
+def linear_bf16_eval(x, weight, bias, bn, mode):
+    """inference: x (rows, cin) fp32 -> (rows, cout) fp32 on the bf16 matrix cores.  bn: a BatchNormReLU in eval mode whose pass
+    runs in the GEMM's epilogue (mode = (1: ReLU) | (2: ELU before the normalisation), its own flags), or None (mode 0)."""
+    _on_gpu(x, weight, bias)
+    assert x.dim() == 2 and (bn is not None or mode == 0)
+    x = x.contiguous()
+    rows, cin = x.shape
+    cout = weight.shape[0]
+    wb = _bf16_weight(weight)
+    y = torch.empty((rows, cout), dtype=torch.float32, device=x.device)
+    g, b, m, s = (bn.weight, bn.bias, bn.running_mean, bn.eval_invstd()) if bn is not None else (None, None, None, None)
+    BF16_ROUTED_CALLS[0] += 1
+    check(_lib.lib().hf_linear_bf16_fwd_eval(rows, cin, cout, ptr(x), ptr(wb), ptr(bias), ptr(g), ptr(b), ptr(m), ptr(s), mode, ptr(y),
+                                             stream_ptr()), "linear_bf16_fwd_eval")
+    return y
+
+
 def _bn_apply(z, gamma, beta, mean, invstd):
     y = torch.empty_like(z)
     check(_lib.lib().hf_bn_relu_fwd_eval(z.shape[0], z.shape[1], ptr(z), ptr(gamma), ptr(beta), ptr(mean), ptr(invstd), 1,
@@ -433,8 +521,17 @@ def _shared_mlp_eval(layers, x, pool_k, extra, first_done=False):
             z = linear_bn_fwd(cur, w, layer.fc.bias, bn, in_bn, update_running=False)[0]
         else:
             xin = _bn_apply(cur, *in_bn) if in_bn is not None else cur
-            z = torch.addmm(layer.fc.bias, xin, w.t())
+            if w is layer.fc.weight and bf16_route(xin, w):
+                if pool_k and i == len(layers) - 1:      # the pooling kernel normalises: the GEMM alone
+                    z = linear_bf16_eval(xin, w, layer.fc.bias, None, 0)
+                else:                                    # BatchNorm + ReLU in the epilogue: cur is the layer's output
+                    cur, in_bn = linear_bf16_eval(xin, w, layer.fc.bias, bn, 1), None
+                    continue
+            else:
+                z = torch.addmm(layer.fc.bias, xin, w.t())
         cur, in_bn = z, (bn.weight, bn.bias, bn.running_mean, bn.eval_invstd())
+    if in_bn is None:
+        return cur
     gamma, beta, mean, invstd = in_bn
     if not pool_k:
         return _bn_apply(cur, gamma, beta, mean, invstd)

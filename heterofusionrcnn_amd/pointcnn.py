@@ -33,7 +33,7 @@ from . import _lib
 from ._lib import check, ptr, require, stream_ptr
 from .grouping import INVERSE_MAX_TARGETS, concat_group, group_point, index_inverse, knn_point
 from .sampling import farthest_point_sample, gather_point
-from .mlp import BatchNormReLU, linear_nobias, running_stats_written
+from .mlp import BatchNormReLU, bf16_route, linear_bf16_eval, linear_nobias, running_stats_written
 
 
 class EluBN(nn.Module):
@@ -51,17 +51,28 @@ class EluBN(nn.Module):
         return self.bn(x.reshape(-1, shape[-1]), dropout).reshape(shape)
 
 
+def _linear_elu_bn_bf16(x, weight, post):
+    """linear -> `post` (an EluBN in eval mode) as one launch of the bf16 inference kernel; the caller has asked mlp.bf16_route"""
+    y = linear_bf16_eval(x.reshape(-1, x.shape[-1]), weight, None, post.bn, _bn_mode(post.bn))
+    return y.reshape(*x.shape[:-1], weight.shape[0])
+
+
 class Dense(nn.Module):
     """pf.dense: Linear without bias -> ELU -> BN"""
 
-    def __init__(self, cin, cout, activation=True):
+    def __init__(self, cin, cout, activation=True, allow_bf16=True):
+        """allow_bf16=False: a layer whose output is decoded directly into scores or boxes stays fp32 under
+        mlp.inference_precision("bf16")"""
         super().__init__()
         self.linear = nn.Linear(cin, cout, bias=False)
         nn.init.xavier_normal_(self.linear.weight)
         self.post = EluBN(cout, activation)
+        self.allow_bf16 = allow_bf16
 
     def forward(self, x, dropout=0.0):
         """dropout: the rate of the tf.layers.dropout that follows this layer (training mode: fused into its BatchNorm)"""
+        if self.allow_bf16 and dropout == 0.0 and not self.post.bn.training and bf16_route(x, self.linear.weight):
+            return _linear_elu_bn_bf16(x, self.linear.weight, self.post)
         return self.post(linear_nobias(x, self.linear.weight), dropout)
 
 
@@ -523,7 +534,10 @@ class SeparableK(nn.Module):
         self.post = EluBN(cout, True)
 
     def forward(self, x):                                    # (B,P,K,Cin)
-        return self.post(linear_nobias(depthwise_k(x, self.depthwise), self.pointwise.weight))
+        d = depthwise_k(x, self.depthwise)
+        if not self.post.bn.training and bf16_route(d, self.pointwise.weight):
+            return _linear_elu_bn_bf16(d, self.pointwise.weight, self.post)
+        return self.post(linear_nobias(d, self.pointwise.weight))
 
 
 # The X-transformation branch of an X-Conv (x0 -> x1 -> x2 on (B,P,K*3): rows = P) and its lifting branch (lift0 -> lift1 on
@@ -561,19 +575,21 @@ class XConv(nn.Module):
     def __init__(self, k, dilation, c_prev, c, c_pts_fts, depth_multiplier, with_x=True, with_global=False):
         super().__init__()
         self.k, self.d = k, dilation
-        self.lift0 = Dense(3, c_pts_fts)
-        self.lift1 = Dense(c_pts_fts, c_pts_fts)
+        # the branches that read coordinates only (lifting, X-transformation, global position) stay fp32 under
+        # mlp.inference_precision("bf16"), whatever their widths
+        self.lift0 = Dense(3, c_pts_fts, allow_bf16=False)
+        self.lift1 = Dense(c_pts_fts, c_pts_fts, allow_bf16=False)
         cin = c_pts_fts + c_prev
         self.with_x = with_x
         if with_x:
-            self.x0 = Dense(3 * k, k * k)                    # conv2d (1,K) over the [k][c] window
+            self.x0 = Dense(3 * k, k * k, allow_bf16=False)  # conv2d (1,K) over the [k][c] window
             self.x1 = DepthwiseK(k, k, k)
             self.x2 = DepthwiseK(k, k, k, activation=False)
         self.conv = SeparableK(k, cin, c, depth_multiplier)
         self.with_global = with_global
         if with_global:
-            self.g0 = Dense(3, c // 4)
-            self.g1 = Dense(c // 4, c // 4)
+            self.g0 = Dense(3, c // 4, allow_bf16=False)
+            self.g1 = Dense(c // 4, c // 4, allow_bf16=False)
         self.out_channel = c + (c // 4 if with_global else 0)
 
     def _x_transform(self, local, b, p, k):
@@ -644,8 +660,14 @@ class XConv(nn.Module):
             # F_X <- X x F_*, then the depthwise half of the separable convolution, in one pass
             fx = (xconv_depthwise_gather(x, f, fts, idx, self.conv.depthwise, inverse) if gather
                   else xconv_depthwise(x, f, self.conv.depthwise))
-            zc = linear_nobias(fx, self.conv.pointwise.weight)
             bnc = self.conv.post.bn
+            if not bnc.training and bf16_route(fx, self.conv.pointwise.weight):
+                # inference in bf16: the pointwise half with its ELU and BatchNorm as one launch (SeparableK.forward's route)
+                out = _linear_elu_bn_bf16(fx, self.conv.pointwise.weight, self.conv.post)
+                if self.with_global:
+                    out = torch.cat([self.g1(self.g0(qrs)), out], dim=-1)
+                return out if skip is None else torch.cat([out, skip], dim=-1)
+            zc = linear_nobias(fx, self.conv.pointwise.weight)
             if skip is not None and not self.with_global and _fusable(bnc, zc, zc.shape[-1], zc.shape[-1] + skip.shape[-1]):
                 out = _BNConcatSkip.apply(zc.reshape(-1, zc.shape[-1]), bnc.weight, bnc.bias, bnc.running_mean, bnc.running_var, bnc.eps,
                                           bnc.momentum, _bn_mode(bnc), skip.reshape(-1, skip.shape[-1]).contiguous())

@@ -144,7 +144,7 @@ class RcnnModel(nn.Module):
         nn.init.xavier_normal_(self.cls_logits.weight)
         nn.init.zeros_(self.cls_logits.bias)
         self.reg_fc = _FcStack(fuse_c, cfg.fc)
-        self.reg_out = Dense(self.reg_fc.out_channel, cfg.head_width * cfg.num_classes, activation=False)
+        self.reg_out = Dense(self.reg_fc.out_channel, cfg.head_width * cfg.num_classes, activation=False, allow_bf16=False)
 
     # ------------------------------------------------------------------ RoI pooling
     def roi_pool(self, xyz, rpn_fts, intensity, fg_mask, proposals, img_fts, calib):

@@ -15,15 +15,19 @@ bench (no checkpoint ships with the reference); the image branch's VGG pyramid i
 import torch
 import torch.nn as nn
 
-from . import dp
+from . import dp, mlp
 from .rcnn import RcnnConfig, RcnnModel, canonical_transform, expand_proposals  # noqa: F401  (re-exported)
 from .rpn import RpnModel, rpn_multiclass
 
 
 class TwoStageDetector(nn.Module):
-    def __init__(self, rpn_cfg=None, rcnn_cfg=None, pre_nms_size=9000, rpn_nms_thresh=0.8, rpn_post_nms_size=100):
-        """defaults = rpn_multiclass.config:27-29 (test settings) + rcnn_multiclass.config"""
+    def __init__(self, rpn_cfg=None, rcnn_cfg=None, pre_nms_size=9000, rpn_nms_thresh=0.8, rpn_post_nms_size=100, precision="fp32"):
+        """defaults = rpn_multiclass.config:27-29 (test settings) + rcnn_multiclass.config.  precision "bf16": the two stages run
+        under mlp.inference_precision("bf16") when the detector is in eval mode (wide dense layers on the bf16 matrix cores)"""
         super().__init__()
+        if precision not in mlp.PRECISIONS:
+            raise ValueError("precision must be one of %s, got %r" % (mlp.PRECISIONS, precision))
+        self.precision = precision
         self.rpn_cfg = rpn_cfg or rpn_multiclass(32)
         self.rcnn_cfg = rcnn_cfg or RcnnConfig(img_channels=self.rpn_cfg.img_channels)
         self.pre_nms_size, self.rpn_nms_thresh, self.rpn_post_nms_size = pre_nms_size, rpn_nms_thresh, rpn_post_nms_size
@@ -37,12 +41,14 @@ class TwoStageDetector(nn.Module):
 
     @torch.no_grad()
     def rpn_stage(self, xyz, intensity, img_fts, calib, geometry=None):
-        return self.rpn.propose(xyz, intensity, geometry, img_fts, calib, self.pre_nms_size, self.rpn_nms_thresh,
-                                self.rpn_post_nms_size)
+        with mlp.inference_precision(self.precision):
+            return self.rpn.propose(xyz, intensity, geometry, img_fts, calib, self.pre_nms_size, self.rpn_nms_thresh,
+                                    self.rpn_post_nms_size)
 
     @torch.no_grad()
     def rcnn_stage(self, xyz, intensity, img_fts, calib, rpn_out):
-        return self.rcnn.detect(xyz, rpn_out["rpn_fts"], intensity, rpn_out["fg_mask"], rpn_out["proposals"], img_fts, calib)
+        with mlp.inference_precision(self.precision):
+            return self.rcnn.detect(xyz, rpn_out["rpn_fts"], intensity, rpn_out["fg_mask"], rpn_out["proposals"], img_fts, calib)
 
     @torch.no_grad()
     def forward(self, xyz, intensity, img_fts, calib, geometry=None, return_debug=False):

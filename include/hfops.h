@@ -397,6 +397,23 @@ int hf_lift_elu_bn_bwd(long long rows, int c0, int c1, const float *x3, const fl
                        const float *mean0, const float *invstd0, const float *dz1, const float *w1_t, float *grad_w0_t,
                        float *grad_w1, float *dgamma0, float *dbeta0, void *workspace, size_t workspace_bytes, hf_stream_t stream);
 
+/* Reduced-precision inference of the wide dense layers (csrc/linear_bf16.hip): the only entry points of the library that do not
+ * compute in fp32 end to end.  bf16 values travel as uint16_t (the upper half of the fp32 bit pattern).
+ * fp32 -> bf16, round to nearest even; the same device function the GEMM applies to x while staging.  n >= 1.  A value whose
+ * magnitude rounds past the largest finite bf16 becomes Inf; NaN stays NaN.  Inputs below the fp32 normal range (subnormals) are
+ * outside the contract of both entry points: the hardware conversion may flush them. */
+int hf_f32_to_bf16(long long n, const float *src, uint16_t *dst, hf_stream_t stream);
+
+/* inference only: z = bf16(x) (rows, cin) . w_bf16^T (cout, cin), products exact, accumulated in fp32, + bias (may be NULL);
+ * with gamma/beta/mean/invstd given (all four or none): y = relu?(gamma * invstd * (elu?(z) - mean) + beta), the convention of
+ * hf_bn_relu_fwd_eval / hf_lift_elu_fwd_eval_bn; mode = (1: ReLU) | (2: ELU on z), 0 when the four are NULL.  y is fp32.
+ * rows >= 1 (rows / 128 row blocks times the column tiles must fit a 31-bit grid), cin % 4 == 0, cout % 4 == 0, x, w_bf16 and y
+ * 16-byte aligned; anything else is HF_EINVAL before a launch.  The ELU is the exp2 form of the streaming BatchNorm passes, the
+ * affine is evaluated in their order (difference first), so this call and GEMM + hf_bn_relu_fwd_eval differ only through z. */
+int hf_linear_bf16_fwd_eval(long long rows, int cin, int cout, const float *x, const uint16_t *w_bf16, const float *bias,
+                            const float *gamma, const float *beta, const float *mean, const float *invstd, int mode,
+                            float *y, hf_stream_t stream);
+
 /* BatchNorm (training mode) with the DROPOUT that follows it fused in -- pointfly's dense -> dropout of the PointCNN fc layers and of
  * the RPN box head (hf/core/feature_extractors/pointcnn.py:371-384, hf/core/models/rpn_model.py:556-568: tf.layers.dropout keeps an
  * element with probability 1 - rate and scales it by 1 / (1 - rate)).  y = dropout(bn(act(x))).  The keep decision of an element
