@@ -106,6 +106,9 @@ _SIGNATURES = {
     "hf_lift_elu_bn_bwd": [ctypes.c_longlong, _i, _i] + [_vp] * 12 + [_vp, _sz, _vp],
     "hf_f32_to_bf16": [ctypes.c_longlong, _vp, _vp, _vp],
     "hf_linear_bf16_fwd_eval": [ctypes.c_longlong, _i, _i] + [_vp] * 7 + [_i, _vp, _vp],
+    "hf_f32_to_bf16_transpose": [_i, _i, _vp, _vp, _vp],
+    "hf_linear_bf16_wgrad_workspace": [ctypes.c_longlong, _i, _i],
+    "hf_linear_bf16_wgrad": [ctypes.c_longlong, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp],
     "hf_project_gather": [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     "hf_project_gather_grad": [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
     "hf_fuse_concat": [ctypes.c_longlong, _i, _i, _vp, _vp, _vp, _vp, _vp],
@@ -163,6 +166,7 @@ _RESTYPES = {
     "hf_three_nn_workspace": _sz,
     "hf_knn_workspace": _sz,
     "hf_linear_wgrad_workspace": _sz,
+    "hf_linear_bf16_wgrad_workspace": _sz,
     "hf_linear_bn_fwd_workspace": _sz,
     "hf_linear_bn_bwd_workspace": _sz,
     "hf_xconv_depthwise_gather_grad_workspace": _sz,

@@ -96,10 +96,14 @@ def reference_train_op(world=1):
     return {"lr": 0.001 * world, "lr_decay": (20000, 0.8, True), "clip_norm": 1.0, "tf_epsilon": True, "check_numerics": True}
 
 
-def train_op_settings(lr, lr_decay, clip_norm, tf_epsilon):
-    """what a checkpoint records of the train op (resume refuses other values)"""
-    return {"lr": float(lr), "lr_decay": None if lr_decay is None else tuple(lr_decay), "clip_norm": float(clip_norm),
-            "tf_epsilon": bool(tf_epsilon)}
+def train_op_settings(lr, lr_decay, clip_norm, tf_epsilon, precision="fp32"):
+    """what a checkpoint records of the train op (resume refuses other values).  "precision" is recorded only when it is not fp32:
+    fp32 checkpoints keep their format, and a checkpoint resumes only at the precision it was written at"""
+    settings = {"lr": float(lr), "lr_decay": None if lr_decay is None else tuple(lr_decay), "clip_norm": float(clip_norm),
+                "tf_epsilon": bool(tf_epsilon)}
+    if precision != "fp32":
+        settings["precision"] = str(precision)
+    return settings
 
 
 class Checkpointer:
@@ -155,6 +159,9 @@ def add_train_op_arguments(ap, config_file):
     ap.add_argument("--max-checkpoints", type=int, default=None, help="keep only the newest K checkpoints")
     ap.add_argument("--resume", action="store_true",
                     help="continue from the newest checkpoint in --checkpoint-dir; --steps is then the final global step")
+    ap.add_argument("--precision", choices=("fp32", "bf16"), default="fp32",
+                    help="bf16: the wide dense layers train on the bf16 matrix cores (fp32 accumulation, tensors, master weights and "
+                         "Adam; a checkpoint resumes only at the precision it was written at)")
 
 
 def train_op_kwargs(args, world=1):
@@ -165,7 +172,7 @@ def train_op_kwargs(args, world=1):
         raise SystemExit("--resume needs --checkpoint-dir")
     kw = reference_train_op(world) if args.reference_train_op else {"lr": args.lr}
     kw.update(checkpoint_dir=args.checkpoint_dir, checkpoint_every=args.checkpoint_every, max_checkpoints=args.max_checkpoints,
-              resume=args.resume)
+              resume=args.resume, precision=args.precision)
     return kw
 
 

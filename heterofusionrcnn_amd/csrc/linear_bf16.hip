@@ -21,27 +21,16 @@
 // epilogue in 2.1 ms (525-540 TFLOP/s) against 7.9 ms for the fp32 library GEMM plus its BatchNorm pass and 2.55 ms for the library's
 // bf16 GEMM with its cast and BatchNorm passes.  One workgroup walks all of cin for its tile: a short, deep product (800 x 11808)
 // launches seven workgroups and loses to the library; mlp.bf16_route_pays keeps such shapes away.
+#include "bf16_common.h"
 #include "gemm_common.h"
 #include "hf_common.h"
 
 namespace hf {
 
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int kBfRows = 128;          // rows per workgroup tile
 constexpr int kBfKC = 64;             // channels per LDS stage: two MFMA k-steps
 constexpr int kBfLS = kBfKC + 16;     // LDS row stride in bf16 elements (see above)
 constexpr int kBfRelu = 1, kBfElu = 2;  // `mode`, the bits of the BatchNorm entry points' `relu`
-
-// two floats -> two bf16 (round to nearest even) in one register, `lo` in the low half: v_cvt_pk_bf16_f32
-__device__ __forceinline__ unsigned pack_bf16x2(float lo, float hi)
-{
-    const f32x2 v = { lo, hi };
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
-}
 
 // n floats; `vec`: src 16-byte and dst 8-byte aligned, whole quads take one 16-byte load and one 8-byte store
 __global__ __launch_bounds__(256) void f32_to_bf16_kernel(long long n, int vec, const float *__restrict__ src, uint16_t *__restrict__ dst)
@@ -188,8 +177,6 @@ static int launch_linear_bf16(long long rows, int cin, int cout, const float *x,
                        cout, col_tiles, x, w, bias, gamma, beta, mean, invstd, mode, y);
     return launch_status();
 }
-
-static inline bool bf_aligned16(const void *p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
 
 }  // namespace hf
 

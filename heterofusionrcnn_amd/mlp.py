@@ -3,6 +3,9 @@ level (tf_util.conv2d's batch_norm + relu, hf/core/feature_extractors/tf_util.py
 
 HIP kernels in csrc/mlp.hip behind hf_bn_relu_* (include/hfops.h); no framework fallback on the GPU
 path: CUDA tensors always take the HIP kernels."""
+import functools
+import inspect
+
 import torch
 import torch.nn as nn
 
@@ -204,10 +207,15 @@ def linear_narrow(x, weight, bias):
     return torch.nn.functional.linear(x, weight, bias)
 
 
-def linear_nobias(x, weight):
+def linear_nobias(x, weight, allow_bf16=False):
     """x (.., Cin) @ weight (Cout, Cin)^T; tall inputs on the device take the split-K weight gradient (from 2048 rows: the
     library's plain weight-gradient GEMM is one workgroup per output tile walking every row -- 115 us for 16384 rows x 64 x 24,
-    the per-layer cost of the one-frame-per-GPU step)"""
+    the per-layer cost of the one-frame-per-GPU step).  allow_bf16: the caller is a wide layer in training mode whose three products
+    may run on the bf16 matrix cores under training_precision("bf16") (bf16_train_route decides)"""
+    if allow_bf16 and bf16_train_route(x, weight):
+        x2 = x.reshape(-1, x.shape[-1]).contiguous()
+        y = _LinearBf16Train.apply(x2 if x2.data_ptr() % 16 == 0 else x2.clone(), weight)
+        return y.reshape(*x.shape[:-1], weight.shape[0])
     if x.is_cuda and x.dtype == torch.float32 and x.numel() // x.shape[-1] >= 2048:
         y = _LinearSplitK.apply(x.reshape(-1, x.shape[-1]).contiguous(), weight)
         return y.reshape(*x.shape[:-1], weight.shape[0])
@@ -359,6 +367,140 @@ def linear_bf16_eval(x, weight, bias, bn, mode):
     check(_lib.lib().hf_linear_bf16_fwd_eval(rows, cin, cout, ptr(x), ptr(wb), ptr(bias), ptr(g), ptr(b), ptr(m), ptr(s), mode, ptr(y),
                                              stream_ptr()), "linear_bf16_fwd_eval")
     return y
+
+
+# ------------------------------------------------------------------------------------------------ bf16 training
+# Training precision of the wide dense layers, process-wide and separate from the inference switch: "fp32" (default: every layer as
+# before) or "bf16" -- the three products of a layer (z = x W^T, dx = g W, dW = g^T x) with their operands rounded to bf16, exact
+# products and fp32 accumulation (csrc/linear_bf16.hip, csrc/linear_bf16_train.hip).  Tensors, master weights and the optimiser stay
+# fp32; the BatchNorm passes read the fp32 z as before.  Consulted only by linear_nobias, with autograd on, for a caller that allows it.
+_TRAINING_PRECISION = ["fp32"]
+BF16_TRAIN_ROUTED_CALLS = [0]    # forward launches of the bf16 training route so far (tests and probes read the difference)
+
+# The shapes the training route takes: those where scripts/probes/bf16_train_linear_timing.py measured the summed trio (forward with its
+# two weight conversions, input gradient, weight gradient) faster than the fp32 trio of linear_nobias by more than the spread between
+# repeats of the latter (profiles/bf16_training_timing.json, "layers" / "routing"; one MI355X, medians in us, bf16 against fp32).
+# All 23 permitted shapes of the rpn_multiclass step (batch 8 and one frame) and of the RCNN step with 2048 rows or more won, by 1.09x
+# to 2.74x: 2048 x 1280 x 1024 136 against 149 (spread 6), 2048 x 2048 x 1024 169 against 205, 4096 x 320 x 256 55 against 75,
+# 131072 x 512 x 256 370 against 784, 65536 x 2688 x 512 1377 against 3768.  Every shape with 1024 rows or fewer lost -- 1024 x 640 x 512
+# 68 against 62, 1024 x 1280 x 1024 123 against 83, 512 x 2304 x 1024 169 against 86 (few 128-row tiles, each walking all of cin alone,
+# and three launches of conversions and reduction that the library does not need), the short, deep 128 x 11808 x 256 304 against 72 --
+# except 128 x 256 x 256 (49 against 107), which a threshold on rows cannot tell from its losing neighbours and which stays fp32.
+# No permitted layer of those steps is narrower than 256 inputs or 256 outputs, so nothing narrower was measured and nothing narrower
+# is routed.
+BF16_TRAIN_MIN_ROWS = 2048
+BF16_TRAIN_MIN_CIN = 256
+BF16_TRAIN_MIN_COUT = 256
+
+
+def training_precision_name():
+    return _TRAINING_PRECISION[0]
+
+
+class training_precision:
+    """with mlp.training_precision("bf16"): ... -- the previous setting returns on exit"""
+
+    def __init__(self, precision):
+        if precision not in PRECISIONS:
+            raise ValueError("precision must be one of %s, got %r" % (PRECISIONS, precision))
+        self.precision = precision
+
+    def __enter__(self):
+        self.previous = _TRAINING_PRECISION[0]
+        _TRAINING_PRECISION[0] = self.precision
+        return self
+
+    def __exit__(self, *exc):
+        _TRAINING_PRECISION[0] = self.previous
+        return False
+
+
+def under_training_precision(fn):
+    """decorator of a train(..., precision="fp32"): the whole call -- the capture and every step, eager ones included -- runs under
+    training_precision(precision)"""
+    sig = inspect.signature(fn)
+
+    @functools.wraps(fn)
+    def run(*args, **kwargs):
+        bound = sig.bind(*args, **kwargs)
+        bound.apply_defaults()
+        with training_precision(bound.arguments["precision"]):
+            return fn(*args, **kwargs)
+    return run
+
+
+def bf16_train_route_pays(rows, cin, cout):
+    # neither kernel needs cin >= 32 (they take cin >= 4): the floor keeps the narrow layers (coordinate branches, lifting chain) fp32
+    # whatever BF16_TRAIN_MIN_CIN is set to, as bf16_route_pays does for inference
+    return rows >= BF16_TRAIN_MIN_ROWS and cin >= max(BF16_TRAIN_MIN_CIN, 32) and cout >= BF16_TRAIN_MIN_COUT
+
+
+def bf16_train_route(x, weight):
+    """does x (.., cin) times weight (cout, cin)^T, with its two gradients, take the bf16 kernels?  The caller has checked that its
+    layer is in training mode and may leave fp32."""
+    if _TRAINING_PRECISION[0] != "bf16" or not torch.is_grad_enabled() or not x.is_cuda or x.dtype != torch.float32:
+        return False
+    if not weight.is_cuda or weight.dtype != torch.float32:
+        return False
+    cout, cin = weight.shape
+    if max(cin, cout) > 32768:           # the weight-gradient kernel's limit
+        return False
+    return cin % 4 == 0 and cout % 4 == 0 and x.shape[-1] == cin and bf16_train_route_pays(x.numel() // cin, cin, cout)
+
+
+def _bf16_gemm(rows, cin, cout, x, wb):
+    """(rows, cin) fp32 times wb (cout, cin) bf16, transposed -> (rows, cout) fp32: hf_linear_bf16_fwd_eval without an epilogue"""
+    y = torch.empty((rows, cout), dtype=torch.float32, device=x.device)
+    check(_lib.lib().hf_linear_bf16_fwd_eval(rows, cin, cout, ptr(x), ptr(wb), None, None, None, None, None, 0, ptr(y), stream_ptr()),
+          "linear_bf16_fwd_eval")
+    return y
+
+
+def linear_bf16_wgrad(grad_z, x):
+    """dW (cout, cin) = bf16(grad_z)^T bf16(x), fp32 accumulation (csrc/linear_bf16_train.hip): rows cut into chunks, partial tiles summed
+    in a fixed order"""
+    _on_gpu(grad_z, x)
+    rows, cout = grad_z.shape
+    cin = x.shape[1]
+    L = _lib.lib()
+    nbytes = L.hf_linear_bf16_wgrad_workspace(rows, cout, cin)
+    ws = torch.empty((max(nbytes, 16) // 4,), dtype=torch.float32, device=x.device)
+    dw = torch.empty((cout, cin), dtype=torch.float32, device=x.device)
+    check(L.hf_linear_bf16_wgrad(rows, cout, cin, ptr(grad_z), ptr(x), ptr(dw), ptr(ws), nbytes, stream_ptr()), "linear_bf16_wgrad")
+    return dw
+
+
+class _LinearBf16Train(torch.autograd.Function):
+    """y = x W^T (no bias) and its two gradients on the bf16 matrix cores.  The weight changes at every step, so nothing is cached on
+    it (the _hf_bf16 copy of the inference route is neither read nor written): W and W^T are converted in every forward -- inside a
+    stream capture the conversions are nodes of the graph -- and the transposed copy is saved for the backward."""
+
+    @staticmethod
+    def forward(ctx, x, weight):
+        rows, cin = x.shape
+        cout = weight.shape[0]
+        w = weight.detach().contiguous()
+        L = _lib.lib()
+        wb = torch.empty((cout, cin), dtype=torch.bfloat16, device=w.device)
+        check(L.hf_f32_to_bf16(w.numel(), ptr(w), ptr(wb), stream_ptr()), "f32_to_bf16")
+        wtb = None
+        if ctx.needs_input_grad[0]:
+            wtb = torch.empty((cin, cout), dtype=torch.bfloat16, device=w.device)
+            check(L.hf_f32_to_bf16_transpose(cout, cin, ptr(w), ptr(wtb), stream_ptr()), "f32_to_bf16_transpose")
+        BF16_TRAIN_ROUTED_CALLS[0] += 1
+        ctx.save_for_backward(x, wtb)
+        return _bf16_gemm(rows, cin, cout, x, wb)
+
+    @staticmethod
+    def backward(ctx, g):
+        x, wtb = ctx.saved_tensors
+        g = g.contiguous()
+        if g.data_ptr() % 16:
+            g = g.clone()                # a view into a larger gradient: the kernels read sixteen bytes at a time
+        rows, cin = x.shape
+        dx = _bf16_gemm(rows, g.shape[1], cin, g, wtb) if ctx.needs_input_grad[0] else None
+        dw = linear_bf16_wgrad(g, x) if ctx.needs_input_grad[1] else None
+        return dx, dw
 
 
 def _bn_apply(z, gamma, beta, mean, invstd):

@@ -62,7 +62,7 @@ class Dense(nn.Module):
 
     def __init__(self, cin, cout, activation=True, allow_bf16=True):
         """allow_bf16=False: a layer whose output is decoded directly into scores or boxes stays fp32 under
-        mlp.inference_precision("bf16")"""
+        mlp.inference_precision("bf16") and mlp.training_precision("bf16")"""
         super().__init__()
         self.linear = nn.Linear(cin, cout, bias=False)
         nn.init.xavier_normal_(self.linear.weight)
@@ -73,7 +73,7 @@ class Dense(nn.Module):
         """dropout: the rate of the tf.layers.dropout that follows this layer (training mode: fused into its BatchNorm)"""
         if self.allow_bf16 and dropout == 0.0 and not self.post.bn.training and bf16_route(x, self.linear.weight):
             return _linear_elu_bn_bf16(x, self.linear.weight, self.post)
-        return self.post(linear_nobias(x, self.linear.weight), dropout)
+        return self.post(linear_nobias(x, self.linear.weight, allow_bf16=self.allow_bf16 and self.post.bn.training), dropout)
 
 
 class _DenseChainElu(torch.autograd.Function):
@@ -537,7 +537,7 @@ class SeparableK(nn.Module):
         d = depthwise_k(x, self.depthwise)
         if not self.post.bn.training and bf16_route(d, self.pointwise.weight):
             return _linear_elu_bn_bf16(d, self.pointwise.weight, self.post)
-        return self.post(linear_nobias(d, self.pointwise.weight))
+        return self.post(linear_nobias(d, self.pointwise.weight, allow_bf16=self.post.bn.training))
 
 
 # The X-transformation branch of an X-Conv (x0 -> x1 -> x2 on (B,P,K*3): rows = P) and its lifting branch (lift0 -> lift1 on
@@ -667,7 +667,7 @@ class XConv(nn.Module):
                 if self.with_global:
                     out = torch.cat([self.g1(self.g0(qrs)), out], dim=-1)
                 return out if skip is None else torch.cat([out, skip], dim=-1)
-            zc = linear_nobias(fx, self.conv.pointwise.weight)
+            zc = linear_nobias(fx, self.conv.pointwise.weight, allow_bf16=bnc.training)
             if skip is not None and not self.with_global and _fusable(bnc, zc, zc.shape[-1], zc.shape[-1] + skip.shape[-1]):
                 out = _BNConcatSkip.apply(zc.reshape(-1, zc.shape[-1]), bnc.weight, bnc.bias, bnc.running_mean, bnc.running_var, bnc.eps,
                                           bnc.momentum, _bn_mode(bnc), skip.reshape(-1, skip.shape[-1]).contiguous())

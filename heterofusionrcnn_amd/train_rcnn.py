@@ -20,6 +20,7 @@ import torch
 from . import checkpoint as ckpt_mod
 from .graph_step import TrainStep
 from .inference import ImgVggPyr
+from .mlp import under_training_precision
 from .optim import MultiTensorAdam
 from .rcnn import RcnnConfig, RcnnModel
 from .rcnn_data import KittiRcnnBatches
@@ -36,13 +37,15 @@ def make_trainer(rpn_fts_channels, img_conv=None, seed=0, path_drop=(0.9, 0.9)):
 CONFIG = "rcnn_multiclass"
 
 
+@under_training_precision
 def train(dataset_dir, handoff_dir, split="train", steps=100, batch=2, seed=0, save=None, log_every=10, workers=8, lr=1e-3,
           graph=True, img_conv=None, aug_list=None, log=print, clip_norm=0.0, lr_decay=None, tf_epsilon=False, check_numerics=False,
-          checkpoint_dir=None, checkpoint_every=ckpt_mod.CHECKPOINT_INTERVAL, max_checkpoints=None, resume=False):
+          checkpoint_dir=None, checkpoint_every=ckpt_mod.CHECKPOINT_INTERVAL, max_checkpoints=None, resume=False,
+          precision="fp32"):
     """-> (list of the per-step losses of this run, read at the end; the trainer)
 
-    The train-op, checkpoint and resume keywords are train_rpn.train's (`steps` is the final global step when resuming)."""
-    settings = ckpt_mod.train_op_settings(lr, lr_decay, clip_norm, tf_epsilon)
+    The train-op, checkpoint, resume and precision keywords are train_rpn.train's (`steps` is the final global step when resuming)."""
+    settings = ckpt_mod.train_op_settings(lr, lr_decay, clip_norm, tf_epsilon, precision)
     ck = None
     if resume:
         ck, path = ckpt_mod.resume_state(checkpoint_dir, CONFIG, settings)
@@ -103,7 +106,7 @@ def train(dataset_dir, handoff_dir, split="train", steps=100, batch=2, seed=0, s
     return out, trainer
 
 
-def main(argv=None):
+def build_parser():
     ap = argparse.ArgumentParser(prog="python -m heterofusionrcnn_amd.train_rcnn",
                                  description="Train the RCNN (with its VGG image branch) on KITTI frames (calib/, label_2/, image_2/ "
                                              "under DATASET_DIR) and the RPN hand-off that export_rpn wrote to HANDOFF_DIR.")
@@ -119,7 +122,11 @@ def main(argv=None):
     ap.add_argument("--lr", type=float, default=1e-3)
     ap.add_argument("--no-graph", action="store_true", help="eager steps instead of the captured hipGraph")
     ckpt_mod.add_train_op_arguments(ap, "rcnn_multiclass.config")
-    args = ap.parse_args(argv)
+    return ap
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
     losses, _ = train(args.dataset_dir, args.handoff_dir, args.split, args.steps, args.batch, args.seed, args.save, args.log_every,
                       args.workers, graph=not args.no_graph, **ckpt_mod.train_op_kwargs(args))
     if losses:

@@ -22,6 +22,7 @@ from . import rpn as rpn_mod
 from .graph_step import TrainStep
 from .inference import CLASSES, ImgVggPyr
 from .kitti_data import KittiRpnBatches
+from .mlp import under_training_precision
 from .optim import MultiTensorAdam
 from .pipeline import GeometryPrefetcher
 
@@ -39,16 +40,19 @@ def make_model(config, img_conv=None):
     raise ValueError("config must be one of %s" % (CONFIGS,))
 
 
+@under_training_precision
 def train(dataset_dir, split="train", steps=100, batch=8, config="rpn_multiclass", seed=0, save=None, log_every=10, workers=8,
           lr=1e-3, graph=True, img_conv=None, num_points=16384, log=print, clip_norm=0.0, lr_decay=None, tf_epsilon=False,
-          check_numerics=False, checkpoint_dir=None, checkpoint_every=ckpt_mod.CHECKPOINT_INTERVAL, max_checkpoints=None, resume=False):
+          check_numerics=False, checkpoint_dir=None, checkpoint_every=ckpt_mod.CHECKPOINT_INTERVAL, max_checkpoints=None, resume=False,
+          precision="fp32"):
     """-> (list of the per-step losses of this run, floats read at the end; the loader status)
 
     clip_norm / lr_decay / tf_epsilon: optim.MultiTensorAdam's (ckpt_mod.reference_train_op() holds the reference's values);
     check_numerics: a NaN / Inf loss raises FloatingPointError at the next log point (always before a checkpoint is written);
     checkpoint_dir: a checkpoint every checkpoint_every global steps, the newest max_checkpoints kept; resume: continue from the
-    newest checkpoint there, `steps` then being the final global step."""
-    settings = ckpt_mod.train_op_settings(lr, lr_decay, clip_norm, tf_epsilon)
+    newest checkpoint there, `steps` then being the final global step.  precision "bf16": the wide dense layers train on the bf16
+    matrix cores (the whole call runs under mlp.training_precision); a checkpoint resumes only at the precision it was written at."""
+    settings = ckpt_mod.train_op_settings(lr, lr_decay, clip_norm, tf_epsilon, precision)
     ck = None
     if resume:
         ck, path = ckpt_mod.resume_state(checkpoint_dir, config, settings)
@@ -121,7 +125,7 @@ def train(dataset_dir, split="train", steps=100, batch=8, config="rpn_multiclass
     return out, st
 
 
-def main(argv=None):
+def build_parser():
     ap = argparse.ArgumentParser(prog="python -m heterofusionrcnn_amd.train_rpn",
                                  description="Train the RPN on KITTI frames (velodyne/, calib/, label_2/, image_2/ under DATASET_DIR).")
     ap.add_argument("dataset_dir")
@@ -136,7 +140,11 @@ def main(argv=None):
     ap.add_argument("--lr", type=float, default=1e-3)
     ap.add_argument("--no-graph", action="store_true", help="eager steps instead of the captured hipGraph")
     ckpt_mod.add_train_op_arguments(ap, "rpn_multiclass.config")
-    args = ap.parse_args(argv)
+    return ap
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
     losses, st = train(args.dataset_dir, args.split, args.steps, args.batch, args.config, args.seed, args.save, args.log_every,
                        args.workers, graph=not args.no_graph, **ckpt_mod.train_op_kwargs(args))
     if losses:

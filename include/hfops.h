@@ -414,6 +414,27 @@ int hf_linear_bf16_fwd_eval(long long rows, int cin, int cout, const float *x, c
                             const float *gamma, const float *beta, const float *mean, const float *invstd, int mode,
                             float *y, hf_stream_t stream);
 
+/* Training of the same layers on the bf16 matrix cores (csrc/linear_bf16_train.hip).  The forward z = bf16(x) bf16(W)^T is
+ * hf_linear_bf16_fwd_eval with mode 0 and no bias; the two entry points below supply the backward products.  Tensors stay fp32 in
+ * memory, accumulation is fp32.
+ * dst (cols, rows) = bf16(src (rows, cols))^T, the rounding of hf_f32_to_bf16 (the same device function), through an LDS tile: reads
+ * and writes are both coalesced.  With src = W (cout, cin) it yields Wt_bf16 (cin, cout), and the input gradient
+ * dx (rows, cin) = bf16(g) (rows, cout) . W is hf_linear_bf16_fwd_eval(rows, cout, cin, g, Wt_bf16, NULL ..., 0, dx): the roles of cin
+ * and cout swapped.  rows, cols >= 1 (the 32 x 32 tiles must fit a 31-bit grid), src 4-byte and dst 2-byte aligned; anything else is
+ * HF_EINVAL before a launch. */
+int hf_f32_to_bf16_transpose(int rows, int cols, const float *src, uint16_t *dst, hf_stream_t stream);
+
+/* grad_weight[o][i] = sum over r of bf16(grad_z[r][o]) * bf16(x[r][i]): both operands are fp32 in memory and rounded (nearest even)
+ * while they are staged, as hf_linear_bf16_fwd_eval rounds x; products exact, accumulated in fp32.  The reduction over rows is cut
+ * into chunks whose partial tiles go to the workspace and are summed in a fixed order (the convention of hf_linear_wgrad; a single
+ * chunk writes grad_weight directly): no floating-point atomics, two calls on the same inputs return the same bits; nothing allocates
+ * or synchronises.  rows >= 1, 4 <= cout, cin <= 32768, cout % 4 == 0, cin % 4 == 0, grad_z, x, grad_weight and workspace 16-byte
+ * aligned, workspace of at least hf_linear_bf16_wgrad_workspace(rows, cout, cin) bytes (0 for a shape outside the contract);
+ * anything else, a missing or short workspace included, is HF_EINVAL before a launch. */
+size_t hf_linear_bf16_wgrad_workspace(long long rows, int cout, int cin);
+int hf_linear_bf16_wgrad(long long rows, int cout, int cin, const float *grad_z, const float *x, float *grad_weight, void *workspace,
+                         size_t workspace_bytes, hf_stream_t stream);
+
 /* BatchNorm (training mode) with the DROPOUT that follows it fused in -- pointfly's dense -> dropout of the PointCNN fc layers and of
  * the RPN box head (hf/core/feature_extractors/pointcnn.py:371-384, hf/core/models/rpn_model.py:556-568: tf.layers.dropout keeps an
  * element with probability 1 - rate and scales it by 1 / (1 - rate)).  y = dropout(bn(act(x))).  The keep decision of an element
