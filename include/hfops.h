@@ -501,8 +501,9 @@ int hf_fuse_concat_grad(long long rows, int c1, int c2, const float *grad_out, c
  * (:733-776).  hf_rpn_loss_fwd -> out5 = [segmentation, bin classification, regression, #foreground, total loss]
  * (focal alpha 0.25 gamma 2 on the clipped softmax, x seg_weight / rows; softmax cross-entropy of the three bin groups and
  * smooth-L1 of the true bin's residuals, y and the sizes over foreground points, / max(#fg, 1)).  hf_rpn_loss_bwd -> the
- * gradients w.r.t. seg_logits and head times *upstream (a device scalar); grad_head is zero-filled here.
- * workspace: hf_rpn_loss_workspace() bytes. */
+ * gradients w.r.t. seg_logits and head times *upstream (a device scalar; out5 as the forward wrote it); grad_head is
+ * zero-filled here.  Limits: k + 1 <= 8, 1 <= nbx, nbt <= 32 (HF_EINVAL beyond).  A label above k and a bin target outside
+ * 0..nbx-1 / 0..nbt-1 are the caller's contract: neither is checked.  workspace: hf_rpn_loss_workspace() bytes. */
 size_t hf_rpn_loss_workspace(void);
 int hf_rpn_loss_fwd(long long rows, int k, int nbx, int nbt, const float *seg_logits, const float *head, const int *label,
                     const int *bin_x, const float *res_x, const int *bin_z, const float *res_z, const int *bin_theta,
@@ -524,7 +525,9 @@ int hf_rpn_loss_bwd(long long rows, int k, int nbx, int nbt, const float *seg_lo
  * cross-entropy summed x cls_weight / #cls; the three bin cross-entropies x cls_weight / #reg; smooth-L1 of the true bin's
  * x / z / theta residuals, y and the three sizes x reg_weight / #reg; a term whose count is 0 is 0.
  * hf_rcnn_loss_bwd -> gradients w.r.t. cls_logits and head times *upstream (a device scalar; out6 as the forward wrote it);
- * grad_head is zero-filled here.  Limits: k + 1 <= 8, nbx, nbt <= 32.  workspace: hf_rcnn_loss_workspace() bytes. */
+ * grad_head is zero-filled here.  Limits: k + 1 <= 8, 1 <= nbx, nbt <= 32 (HF_EINVAL beyond).  non_empty: any non-zero value
+ * is non-empty.  A gt_cls outside 0..k in the cls mask alone is counted in #cls with no term and no gradient; inside the reg
+ * mask it is the caller's contract, and so is a bin target outside its bins.  workspace: hf_rcnn_loss_workspace() bytes. */
 size_t hf_rcnn_loss_workspace(void);
 int hf_rcnn_loss_fwd(long long rows, int k, int nbx, int nbt, const float *cls_logits, const float *head, const float *iou,
                      const int *gt_cls, const int *non_empty, const int *bin_x, const float *res_x, const int *bin_z,

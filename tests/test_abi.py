@@ -108,6 +108,42 @@ def test_c_abi_rejects_bad_arguments_without_a_gpu():
     assert L.hf_group_point(0, 4, 3, 2, 2, one, one, one, None) == _lib.HF_OK
 
 
+def test_loss_entry_points_reject_bad_arguments_without_a_gpu():
+    """hf_rpn_loss_fwd / _bwd and hf_rcnn_loss_fwd / _bwd: the limits of the register arrays (k + 1 <= 8, bins in 1..32), every NULL
+    input one at a time, NULL outputs, and the workspace: all of it returns before any HIP call (fake non-null pointers, never
+    dereferenced).  No call below has a full set of valid arguments"""
+    from heterofusionrcnn_amd import _lib
+    L = _lib.lib()
+    one = ctypes.c_void_p(256)
+    EINVAL, EWS = _lib.HF_EINVAL, _lib.HF_EWORKSPACE
+    for kind, n_in, floats in (("rpn", 11, (100.0, 1.0, 1.0)), ("rcnn", 13, (0.45, 0.6, 0.55, 1.0, 1.0))):
+        need = getattr(L, "hf_%s_loss_workspace" % kind)()
+        assert need == 4 * (4 if kind == "rpn" else 5) * 1024
+        fwd_fn, bwd_fn = getattr(L, "hf_%s_loss_fwd" % kind), getattr(L, "hf_%s_loss_bwd" % kind)
+
+        def fwd(rows=10, k=3, nbx=12, nbt=12, null=None, out=one, ws=one, nbytes=need):
+            ins = [None if i == null else one for i in range(n_in)]
+            return fwd_fn(rows, k, nbx, nbt, *ins, *floats, out, ws, nbytes, None)
+
+        def bwd(rows=10, k=3, nbx=12, nbt=12, null=None, out=one, up=one, g_logits=one, g_head=one):
+            ins = [None if i == null else one for i in range(n_in)]
+            return bwd_fn(rows, k, nbx, nbt, *ins, *floats, out, up, g_logits, g_head, None)
+
+        bad = {}
+        for name, f in (("fwd", fwd), ("bwd", bwd)):
+            bad.update({"%s: rows < 0" % name: f(rows=-1), "%s: k = 0" % name: f(k=0), "%s: k = 8" % name: f(k=8), "%s: nbx = 0" % name: f(nbx=0),
+                        "%s: nbx = 33" % name: f(nbx=33), "%s: nbt = 33" % name: f(nbt=33), "%s: nbt = 0" % name: f(nbt=0), "%s: no out" % name: f(out=None)})
+            bad.update({"%s: input %d is NULL" % (name, i): f(null=i) for i in range(n_in)})
+        bad.update({"bwd: no upstream": bwd(up=None), "bwd: no logit gradient": bwd(g_logits=None), "bwd: no grad_head": bwd(g_head=None),
+                    "fwd: rows = 0, no out": fwd(rows=0, out=None), "bwd: rows = 0, no upstream": bwd(rows=0, up=None)})
+        wrong = {name: got for name, got in bad.items() if got != EINVAL}
+        assert not wrong, (kind, wrong)
+        assert fwd(ws=None) == EWS and fwd(nbytes=need - 1) == EWS and fwd(nbytes=0) == EWS and fwd(rows=0, ws=None) == EWS
+        # the limits themselves pass the argument check: with them only the workspace is left to refuse
+        assert fwd(k=7, nbx=32, nbt=32, ws=None) == EWS and fwd(k=1, nbx=1, nbt=1, nbytes=need - 1) == EWS
+        assert bwd(rows=0) == _lib.HF_OK and bwd(rows=0, g_logits=None, g_head=None) == _lib.HF_OK       # empty: nothing is launched
+
+
 def test_product_library_reads_no_environment_variable():
     """the diagnostic knobs of the kernels (phase exits that leave outputs unwritten, forced tile shapes, kernel overrides) exist
     only in -DHF_DIAG builds: the shipped library neither imports getenv nor carries their names"""
