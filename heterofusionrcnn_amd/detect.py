@@ -19,7 +19,7 @@ the writer: the parity anchor, byte-identical to rcnn_data.run_rcnn_from_handoff
 are decoded into scores and boxes stay fp32); the default, fp32, is the route described above, bit for bit.
 """
 import argparse
-import concurrent.futures
+import contextlib
 import os
 import sys
 
@@ -29,17 +29,12 @@ import torch
 from . import checkpoint as ckpt_mod
 from . import kitti_data as KD
 from . import mlp
-from .export_rpn import read_export_frame
-from .inference import CLASSES, RESULT_ROW_COLUMNS, result_boxes, result_rows, write_frame_results, write_result_rows
+from .export_rpn import WriteBack, load_rpn, proposals_from_files
+from .inference import CLASSES, result_boxes, result_rows, write_frame_results, write_result_rows
 from .rcnn_data import handoff_in_memory
 from .rcnn_train import RcnnTrainer
 from .train_rcnn import make_trainer
-from .train_rpn import CONFIGS, make_model
-
-
-def _state(src):
-    sd = torch.load(src, map_location="cpu") if isinstance(src, (str, os.PathLike)) else src
-    return ckpt_mod.model_state(sd)
+from .train_rpn import CONFIGS
 
 
 def rpn_fts_channels(rpn):
@@ -52,16 +47,13 @@ def load_models(rpn, rcnn, config="rpn_multiclass", img_conv=None):
     rcnn: a train_rcnn --save file (the RcnnTrainer's state_dict), a checkpoint of it, a state_dict, an RcnnTrainer or an
     RcnnWithImageBranch.  Files and state_dicts load with strict=True; the RCNN is sized from the loaded RPN.
     -> (the RPN module, the RcnnWithImageBranch)"""
-    if isinstance(rpn, torch.nn.Module):
-        net = rpn
-    else:
-        net, _ = make_model(config, img_conv)
-        net.load_state_dict(_state(rpn), strict=True)
+    net = load_rpn(rpn, config, img_conv)
     if isinstance(rcnn, torch.nn.Module):
         second = rcnn.model if isinstance(rcnn, RcnnTrainer) else rcnn
     else:
         trainer = make_trainer(rpn_fts_channels(net.rpn if hasattr(net, "img_net") else net), img_conv)
-        trainer.load_state_dict(_state(rcnn), strict=True)
+        sd = torch.load(rcnn, map_location="cpu") if isinstance(rcnn, (str, os.PathLike)) else rcnn
+        trainer.load_state_dict(ckpt_mod.model_state(sd), strict=True)
         second = trainer.model
     return net, second
 
@@ -88,74 +80,25 @@ def detect(dataset_dir, rpn, rcnn, out_dir, split="val", config="rpn_multiclass"
     modes = (net.training, second.training)
     net.eval()
     second.eval()
-    with_image = hasattr(net, "img_net")
-    first = net.rpn if with_image else net
     names = KD.read_split(dataset_dir, split)
     os.makedirs(out_dir, exist_ok=True)
-    device = next(net.parameters()).device
-    rng_state = torch.tensor([int(seed), 0], dtype=torch.int64, device=device)
-    # a points-only RPN's export never calls hf_rpn_batch_image; the image the RCNN needs then counts its calls apart, so that
-    # the point samples stay the export's (without jitter the image draws nothing)
-    img_rng = rng_state if with_image else torch.tensor([int(seed), 0], dtype=torch.int64, device=device)
-    pool = concurrent.futures.ThreadPoolExecutor(max_workers=max(1, int(workers)))
-    ahead = concurrent.futures.ThreadPoolExecutor(max_workers=1)
-    writer = concurrent.futures.ThreadPoolExecutor(max_workers=2)
-    chunks = [names[i:i + batch] for i in range(0, len(names), batch)]
-    read = lambda ch: list(pool.map(lambda n: read_export_frame(dataset_dir, n, list(classes), img_hw), ch))
-    staging = [KD._Staging(), KD._Staging()]
-    host_bufs = [None, None]
-    writes = [None, None]
-    pending = ahead.submit(read, chunks[0]) if chunks else None
+    batches = proposals_from_files(net, dataset_dir, names, batch, workers, seed, num_points, img_hw,
+                                   (pre_nms_size, nms_thresh, post_nms_size), classes, always_image=True)
     written = {}
-    scope.__enter__()
     try:
-        for bi, chunk in enumerate(chunks):
-            frames = pending.result()
-            st = staging[bi % 2]
-            if st.event is not None:
-                st.event.synchronize()
-            packed = KD.pack_frames(frames, st)
-            points, images, meta = KD.upload(packed, device)
-            st.event = torch.cuda.Event()
-            st.event.record()
-            pending = ahead.submit(read, chunks[bi + 1]) if bi + 1 < len(chunks) else None
-            xyz, inten, _, _ = KD.batch_points(points, meta["offsets"], meta["velo_to_rect"], meta["p2"], meta["wh"], meta["flip"],
-                                               rng_state, num_points, packed["max_frame_points"])
-            geo = first.geometry(xyz)
-            image, _ = KD.batch_image(images, meta["img_offsets"], meta["wh"], meta["flip"], meta["jitter"], img_rng, img_hw,
-                                      packed["max_pixels"])
-            if with_image:
-                out = first.propose(xyz, inten, geo, net.img_net(image), meta["calib"], pre_nms_size, nms_thresh, post_nms_size)
-            else:
-                out = first.propose(xyz, inten, geo, None, None, pre_nms_size, nms_thresh, post_nms_size)
-            h = handoff_in_memory(out, xyz, inten, handoff_rounding)
-            dets, _ = second.detect(h["xyz"], h["rpn_fts"], h["intensity"], h["fg_mask"], h["proposals"], image, meta["calib"])
-            fnames = [f["name"] for f in frames]
-            if host_rows:
-                for f, det in zip(frames, dets):
-                    written[f["name"]] = write_frame_results(os.path.join(out_dir, f["name"] + ".txt"), det,
-                                                             np.asarray(f["p2"], np.float32), f["wh"], score_threshold, classes)
-                continue
-            res = result_boxes(dets, meta["p2"], meta["wh"], score_threshold)
-            rows = result_rows(res)
-            # the pinned buffer of this parity is free once its last writer has finished
-            if writes[bi % 2] is not None:
-                written.update(writes[bi % 2].result())
-            if host_bufs[bi % 2] is None or host_bufs[bi % 2].numel() < rows.numel():
-                host_bufs[bi % 2] = torch.empty((rows.numel() * 5 // 4 + RESULT_ROW_COLUMNS,), dtype=torch.float64).pin_memory()
-            host = host_bufs[bi % 2][:rows.numel()].view(rows.shape)
-            host.copy_(rows, non_blocking=True)
-            done = torch.cuda.Event()
-            done.record()
-            writes[bi % 2] = writer.submit(_write_rows, out_dir, fnames, res["counts"], host, done, classes)
-        for w in writes:
-            if w is not None:
-                written.update(w.result())
+        with scope, contextlib.closing(batches), contextlib.closing(WriteBack()) as back:
+            for frames, meta, xyz, inten, image, out in batches:
+                h = handoff_in_memory(out, xyz, inten, handoff_rounding)
+                dets, _ = second.detect(h["xyz"], h["rpn_fts"], h["intensity"], h["fg_mask"], h["proposals"], image, meta["calib"])
+                if host_rows:
+                    for f, det in zip(frames, dets):
+                        written[f["name"]] = write_frame_results(os.path.join(out_dir, f["name"] + ".txt"), det,
+                                                                 np.asarray(f["p2"], np.float32), f["wh"], score_threshold, classes)
+                    continue
+                res = result_boxes(dets, meta["p2"], meta["wh"], score_threshold)
+                back.submit(result_rows(res), _write_rows, (out_dir, [f["name"] for f in frames], res["counts"]), (classes,))
+            written.update(back.drain())
     finally:
-        ahead.shutdown(wait=True)
-        pool.shutdown(wait=True)
-        writer.shutdown(wait=True)
-        scope.__exit__(None, None, None)
         net.train(modes[0])
         second.train(modes[1])
     return written

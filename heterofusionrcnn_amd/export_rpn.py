@@ -15,6 +15,7 @@ Files are written by worker threads from pinned host buffers, so the device neve
 """
 import argparse
 import concurrent.futures
+import contextlib
 import os
 import sys
 
@@ -76,87 +77,119 @@ def _write_batch(out_dir, names, has_label, host, event, gcounts, batch_index, l
     return out
 
 
+class WriteBack:
+    """Results on their way back to files without the device waiting for the disk: two sets of pinned host tensors used in
+    turn (grown on demand), one non-blocking copy per tensor, an event behind the copies, and two writer threads.
+    submit(dev, write, head, tail) copies `dev` (a device tensor, or a dict of them) and runs write(*head, host, event, *tail)
+    -> dict on a writer thread (it waits for the event first); a set is reused only after its previous writer has returned.
+    drain() -> every writer's dict, merged."""
+
+    def __init__(self):
+        self._writer = concurrent.futures.ThreadPoolExecutor(max_workers=2, thread_name_prefix="hf-write")
+        self._sets, self._writes, self._turn, self._results = [{}, {}], [None, None], 0, {}
+
+    def _collect(self, i):
+        if self._writes[i] is not None:
+            self._results.update(self._writes[i].result())
+
+    def submit(self, dev, write, head, tail=()):
+        single = torch.is_tensor(dev)
+        dev = {"": dev} if single else dev
+        i = self._turn
+        self._turn ^= 1
+        self._collect(i)                             # the pinned set of this parity is free once its last writer has finished
+        hs = self._sets[i]
+        for k, t in dev.items():
+            if k not in hs or hs[k].numel() < t.numel():
+                hs[k] = torch.empty((t.numel() * 5 // 4 + 1,), dtype=t.dtype).pin_memory()
+        host = {k: hs[k][:t.numel()].view(t.shape) for k, t in dev.items()}
+        for k, t in dev.items():
+            host[k].copy_(t, non_blocking=True)
+        done = torch.cuda.Event()
+        done.record()
+        self._writes[i] = self._writer.submit(write, *head, host[""] if single else host, done, *tail)
+
+    def drain(self):
+        self._collect(0)
+        self._collect(1)
+        return self._results
+
+    def close(self):
+        self._writer.shutdown(wait=True)
+
+
+def load_rpn(model, config, img_conv):
+    """a path to a saved state_dict or to a checkpoint, a state_dict, or a built model -> the model"""
+    if isinstance(model, torch.nn.Module):
+        return model
+    sd = torch.load(model, map_location="cpu") if isinstance(model, (str, os.PathLike)) else model
+    net, _ = make_model(config, img_conv)
+    net.load_state_dict(ckpt_mod.model_state(sd), strict=True)
+    return net
+
+
+def proposals_from_files(net, dataset_dir, names, batch, workers, seed, num_points, img_hw, nms, classes, always_image=False):
+    """File names -> the RPN's proposals, a generator over the chunks of `batch` names (the last may be short): frames are read
+    one chunk ahead (kitti_data.ReadAhead) and packed on the caller's thread (measured: profiles/read_ahead_ab.md), then
+    upload, hf_rpn_batch_points, geometry, hf_rpn_batch_image and propose(..., *nms) on the current stream; yields (frames,
+    meta, xyz, intensity, image or None, the propose output).
+    The image is drawn when the model has an image branch, from the [seed, call] pair of the points.  always_image: a
+    points-only RPN gets one too (the RCNN needs it), its calls counted on a pair apart, so that the point samples stay those
+    of a run without it (without jitter the image draws nothing).  Close the generator to stop the reader threads."""
+    with_image = hasattr(net, "img_net")
+    rpn = net.rpn if with_image else net
+    device = next(net.parameters()).device
+    rng_state = torch.tensor([int(seed), 0], dtype=torch.int64, device=device)
+    img_rng = rng_state if with_image else torch.tensor([int(seed), 0], dtype=torch.int64, device=device)
+    chunks = [names[i:i + batch] for i in range(0, len(names), batch)]
+
+    def read(chunk, staging, pool):
+        return list(pool.map(lambda n: read_export_frame(dataset_dir, n, list(classes), img_hw), chunk)), staging
+
+    with KD.ReadAhead(read, workers) as feed:
+        feed.submit(chunks[0] if chunks else None)
+        for bi in range(len(chunks)):
+            frames, staging = feed.take()          # the feeder has waited for this staging's event
+            packed = KD.pack_frames(frames, staging)
+            points, images, meta = KD.upload(packed, device)
+            feed.uploaded()
+            feed.submit(chunks[bi + 1] if bi + 1 < len(chunks) else None)
+            xyz, inten, _, _ = KD.batch_points(points, meta["offsets"], meta["velo_to_rect"], meta["p2"], meta["wh"], meta["flip"],
+                                               rng_state, num_points, packed["max_frame_points"])
+            geo = rpn.geometry(xyz)
+            image = KD.batch_image(images, meta["img_offsets"], meta["wh"], meta["flip"], meta["jitter"], img_rng, img_hw,
+                                   packed["max_pixels"])[0] if with_image or always_image else None
+            fts, calib = (net.img_net(image), meta["calib"]) if with_image else (None, None)
+            yield frames, meta, xyz, inten, image, rpn.propose(xyz, inten, geo, fts, calib, *nms)
+
+
 @torch.no_grad()
 def export(dataset_dir, model, out_dir, split="train", config="rpn_multiclass", batch=8, img_conv=None, workers=8, seed=0,
            num_points=16384, img_hw=(360, 1200), pre_nms_size=9000, nms_thresh=0.8, post_nms_size=100, classes=CLASSES, log=print):
     """model: a path to a saved state_dict (train_rpn --save) or to a checkpoint (train_rpn --checkpoint-dir), a state_dict, or a
     built model (RpnModel / RpnWithImageBranch).
     -> {name: {"proposals", "labels", "recall_50", "recall_70"}} for every frame of the split"""
-    if isinstance(model, torch.nn.Module):
-        net = model
-    else:
-        sd = torch.load(model, map_location="cpu") if isinstance(model, (str, os.PathLike)) else model
-        sd = ckpt_mod.model_state(sd)
-        net, _ = make_model(config, img_conv)
-        net.load_state_dict(sd, strict=True)
+    net = load_rpn(model, config, img_conv)
     was_training = net.training
     net.eval()
-    with_image = hasattr(net, "img_net")
-    rpn = net.rpn if with_image else net
     names = KD.read_split(dataset_dir, split)
     for d in HANDOFF_DIRS:
         os.makedirs(os.path.join(out_dir, d), exist_ok=True)
-    device = next(net.parameters()).device
-    rng_state = torch.tensor([int(seed), 0], dtype=torch.int64, device=device)
-    pool = concurrent.futures.ThreadPoolExecutor(max_workers=max(1, int(workers)))
-    ahead = concurrent.futures.ThreadPoolExecutor(max_workers=1)
-    writer = concurrent.futures.ThreadPoolExecutor(max_workers=2)
-    chunks = [names[i:i + batch] for i in range(0, len(names), batch)]
-    read = lambda ch: list(pool.map(lambda n: read_export_frame(dataset_dir, n, list(classes), img_hw), ch))
-    staging = [KD._Staging(), KD._Staging()]
-    host_sets = [{}, {}]
-    writes = [None, None]
-    pending = ahead.submit(read, chunks[0]) if chunks else None
-    totals = {}
+    batches = proposals_from_files(net, dataset_dir, names, batch, workers, seed, num_points, img_hw,
+                                   (pre_nms_size, nms_thresh, post_nms_size), classes)
     try:
-        for bi, chunk in enumerate(chunks):
-            frames = pending.result()
-            st = staging[bi % 2]
-            if st.event is not None:
-                st.event.synchronize()
-            packed = KD.pack_frames(frames, st)
-            points, images, meta = KD.upload(packed, device)
-            st.event = torch.cuda.Event()
-            st.event.record()
-            pending = ahead.submit(read, chunks[bi + 1]) if bi + 1 < len(chunks) else None
-            xyz, inten, _, _ = KD.batch_points(points, meta["offsets"], meta["velo_to_rect"], meta["p2"], meta["wh"], meta["flip"],
-                                               rng_state, num_points, packed["max_frame_points"])
-            geo = rpn.geometry(xyz)
-            if with_image:
-                image, _ = KD.batch_image(images, meta["img_offsets"], meta["wh"], meta["flip"], meta["jitter"], rng_state, img_hw,
-                                          packed["max_pixels"])
-                out = rpn.propose(xyz, inten, geo, net.img_net(image), meta["calib"], pre_nms_size, nms_thresh, post_nms_size)
-            else:
-                out = rpn.propose(xyz, inten, geo, None, None, pre_nms_size, nms_thresh, post_nms_size)
-            rows = handoff_pack(xyz, inten, out["fg_mask"], out["rpn_fts"])
-            b, m = out["proposals"].shape[:2]
-            gt = torch.cat([meta["boxes"], meta["cls"].unsqueeze(-1).float()], dim=-1)
-            iou = box3d_iou_matrix(out["proposals"], torch.full((b,), m, dtype=torch.int32, device=device), gt, meta["gt_count"])
-            # the pinned host set of this parity is free once its last writer has finished
-            if writes[bi % 2] is not None:
-                totals.update(writes[bi % 2].result())
-            hs = host_sets[bi % 2]
-            dev = {"rows": rows, "proposals": out["proposals"], "scores": out["proposal_scores"], "iou": iou}
-            for k, t in dev.items():
-                if k not in hs or hs[k].numel() < t.numel():
-                    hs[k] = torch.empty((t.numel() * 5 // 4 + 1,), dtype=t.dtype).pin_memory()
-            host = {k: hs[k][:t.numel()].view(t.shape) for k, t in dev.items()}
-            for k, t in dev.items():
-                host[k].copy_(t, non_blocking=True)
-            done = torch.cuda.Event()
-            done.record()
-            gcounts = [len(f["cls"]) for f in frames]
-            writes[bi % 2] = writer.submit(_write_batch, out_dir, [f["name"] for f in frames], [f["has_label"] for f in frames], host,
-                                           done, gcounts, bi, log)
-        for w in writes:
-            if w is not None:
-                totals.update(w.result())
+        with contextlib.closing(batches), contextlib.closing(WriteBack()) as back:
+            for bi, (frames, meta, xyz, inten, _, out) in enumerate(batches):
+                rows = handoff_pack(xyz, inten, out["fg_mask"], out["rpn_fts"])
+                b, m = out["proposals"].shape[:2]
+                gt = torch.cat([meta["boxes"], meta["cls"].unsqueeze(-1).float()], dim=-1)
+                iou = box3d_iou_matrix(out["proposals"], torch.full((b,), m, dtype=torch.int32, device=xyz.device), gt, meta["gt_count"])
+                back.submit({"rows": rows, "proposals": out["proposals"], "scores": out["proposal_scores"], "iou": iou}, _write_batch,
+                            (out_dir, [f["name"] for f in frames], [f["has_label"] for f in frames]),
+                            ([len(f["cls"]) for f in frames], bi, log))
+            return back.drain()
     finally:
-        ahead.shutdown(wait=True)
-        pool.shutdown(wait=True)
-        writer.shutdown(wait=True)
         net.train(was_training)
-    return totals
 
 
 def main(argv=None):

@@ -178,6 +178,50 @@ class _Staging:
         return buf[:nbytes]
 
 
+class ReadAhead:
+    """Host work one batch ahead of the device: the reader pool (`workers` threads), the single ahead thread and the two
+    _Staging sets used in turn.  submit(picks) runs prepare(picks, staging, pool) on the ahead thread once the copy that last
+    read that staging's pinned buffers has finished (picks None: nothing is pending); take() returns what prepare returned and
+    raises what it raised (nothing pending: StopIteration); uploaded(), called after the caller has enqueued its host-to-device
+    copies, records the staging's event on the current stream and passes the turn to the other staging.
+    event: the event class (record(), synchronize()), a seam for tests without a device."""
+
+    def __init__(self, prepare, workers, event=torch.cuda.Event):
+        self._prepare, self._event = prepare, event
+        self._pool = concurrent.futures.ThreadPoolExecutor(max_workers=max(1, int(workers)), thread_name_prefix="hf-read-pool")
+        self._ahead = concurrent.futures.ThreadPoolExecutor(max_workers=1, thread_name_prefix="hf-read-ahead")
+        self._staging, self._turn, self._pending = [_Staging(), _Staging()], 0, None
+
+    def _run(self, picks, staging):
+        if staging.event is not None:
+            staging.event.synchronize()        # the copy that last read these pinned buffers has finished
+        return self._prepare(picks, staging, self._pool)
+
+    def submit(self, picks):
+        self._pending = None if picks is None else self._ahead.submit(self._run, picks, self._staging[self._turn])
+
+    def take(self):
+        if self._pending is None:
+            raise StopIteration
+        return self._pending.result()
+
+    def uploaded(self):
+        staging = self._staging[self._turn]
+        staging.event = self._event()
+        staging.event.record()
+        self._turn ^= 1
+
+    def close(self):
+        self._ahead.shutdown(wait=True)
+        self._pool.shutdown(wait=True)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 def _layout(parts):
     """[(name, nbytes)] -> ({name: (offset, nbytes)}, total) with every segment 16-byte aligned"""
     out, off = {}, 0
@@ -185,6 +229,15 @@ def _layout(parts):
         out[name] = (off, n)
         off += (n + 15) & ~15
     return out, off
+
+
+def _torch_dtype(np_dtype):
+    return torch.from_numpy(np.empty(0, np_dtype)).dtype
+
+
+# the fields of the RPN batch's meta buffer; rcnn_data has its own table, and both cut the host and the device bytes by one
+META_DTYPES = {"offsets": np.int64, "velo_to_rect": np.float64, "p2": np.float64, "img_offsets": np.int64, "wh": np.int32,
+               "flip": np.int32, "jitter": np.int32, "boxes": np.float32, "cls": np.int32, "gt_count": np.int32, "calib": np.float32}
 
 
 def pack_frames(frames, staging):
@@ -200,9 +253,7 @@ def pack_frames(frames, staging):
     lay, total = _layout(meta_parts)
     meta = staging.get("meta", total)
     mv = meta.numpy()
-    dtypes = {"offsets": np.int64, "velo_to_rect": np.float64, "p2": np.float64, "img_offsets": np.int64, "wh": np.int32,
-              "flip": np.int32, "jitter": np.int32, "boxes": np.float32, "cls": np.int32, "gt_count": np.int32, "calib": np.float32}
-    view = {k: mv[o:o + n].view(dtypes[k]) for k, (o, n) in lay.items()}
+    view = {k: mv[o:o + n].view(META_DTYPES[k]) for k, (o, n) in lay.items()}
     view["boxes"][:] = 0
     view["cls"][:] = 0
     row, byte = 0, 0
@@ -230,17 +281,18 @@ def pack_frames(frames, staging):
             "host": {"points": staging.get("points", 16 * sum(counts)), "images": staging.get("images", 3 * sum(pix)), "meta": meta}}
 
 
+def upload_buffers(packed, device, dtypes):
+    """one non-blocking copy per pinned buffer -> ({buffer: device bytes}, meta cut into typed views by `dtypes`, a META_DTYPES)"""
+    dev = {k: torch.empty(v.shape, dtype=torch.uint8, device=device) for k, v in packed["host"].items()}
+    for k, v in packed["host"].items():
+        dev[k].copy_(v, non_blocking=True)
+    return dev, {k: dev["meta"][o:o + n].view(_torch_dtype(dtypes[k])) for k, (o, n) in packed["layout"].items()}
+
+
 def upload(packed, device):
-    """one host-to-device copy per buffer (non-blocking from pinned memory) -> device tensors, meta split into typed views"""
-    h = packed["host"]
-    dev = {k: torch.empty(v.shape, dtype=torch.uint8, device=device) for k, v in h.items()}
-    for k in dev:
-        dev[k].copy_(h[k], non_blocking=True)
+    """upload_buffers of an RPN batch (pack_frames) -> points (N, 4), image bytes, meta with boxes, cls and calib in shape"""
+    dev, meta = upload_buffers(packed, device, META_DTYPES)
     b, g = packed["b"], packed["g"]
-    dt = {"offsets": torch.int64, "velo_to_rect": torch.float64, "p2": torch.float64, "img_offsets": torch.int64, "wh": torch.int32,
-          "flip": torch.int32, "jitter": torch.int32, "boxes": torch.float32, "cls": torch.int32, "gt_count": torch.int32,
-          "calib": torch.float32}
-    meta = {k: dev["meta"][o:o + n].view(dt[k]) for k, (o, n) in packed["layout"].items()}
     meta["boxes"] = meta["boxes"].view(b, g, 7)
     meta["cls"] = meta["cls"].view(b, g)
     meta["calib"] = meta["calib"].view(b, 3, 4)
@@ -350,13 +402,10 @@ class KittiRpnBatches:
             self.list.load_state_dict(state["samples"])
             self._rng_host = [int(v) for v in state["rng_state"]]
         self.rng_state = torch.tensor(self._rng_host, dtype=torch.int64, device=self.device)
-        self._pool = concurrent.futures.ThreadPoolExecutor(max_workers=max(1, int(workers)))
-        self._ahead = concurrent.futures.ThreadPoolExecutor(max_workers=1)
-        self._staging = [_Staging(), _Staging()]
-        self._turn = 0
+        self._feed = ReadAhead(self._prepare, workers)
         self._status = []
         self._pending_pos = self.list.position()
-        self._pending = self._ahead.submit(self._prepare, self.list.take(self.batch), self._staging[0])
+        self._feed.submit(self.list.take(self.batch))
 
     def state_dict(self, position=None):
         """the position of the batch the next next() returns, or of a batch (batch.position), as plain host values (no
@@ -367,25 +416,20 @@ class KittiRpnBatches:
     def __len__(self):
         return len(self.samples)
 
-    def _prepare(self, picks, staging):
-        frames = list(self._pool.map(lambda s: read_frame(self.dataset_dir, s[0], s[1], self.classes, self.img_hw), picks))
-        if staging.event is not None:
-            staging.event.synchronize()        # the copy that last read these pinned buffers has finished
+    def _prepare(self, picks, staging, pool):
+        frames = list(pool.map(lambda s: read_frame(self.dataset_dir, s[0], s[1], self.classes, self.img_hw), picks))
         return pack_frames(frames, staging), [f["name"] for f in frames], [f["augs"] for f in frames]
 
     # --------------------------------------------------------------- device side
     def next(self):
-        packed, names, augs = self._pending.result()
+        packed, names, augs = self._feed.take()
         position = (self._pending_pos, tuple(self._rng_host))     # raw: state_dict(position) makes it plain values
         self._rng_host[1] += self.RNG_CALLS_PER_BATCH
-        staging = self._staging[self._turn]
-        self._turn ^= 1
         with torch.cuda.device(self.device):
             points, images, meta = upload(packed, self.device)
-            staging.event = torch.cuda.Event()
-            staging.event.record()
+            self._feed.uploaded()
             self._pending_pos = self.list.position()
-            self._pending = self._ahead.submit(self._prepare, self.list.take(self.batch), self._staging[self._turn])
+            self._feed.submit(self.list.take(self.batch))
             xyz, inten, src, status = batch_points(points, meta["offsets"], meta["velo_to_rect"], meta["p2"], meta["wh"], meta["flip"],
                                                    self.rng_state, self.num_points, packed["max_frame_points"])
             label_cls, label_reg = point_labels(xyz, meta["boxes"], meta["cls"], meta["gt_count"])
@@ -406,5 +450,4 @@ class KittiRpnBatches:
         return {"empty": int(((st & STATUS_EMPTY) != 0).sum()), "too_many_far": int(((st & STATUS_TOO_MANY_FAR) != 0).sum())}
 
     def close(self):
-        self._ahead.shutdown(wait=True)
-        self._pool.shutdown(wait=True)
+        self._feed.close()

@@ -25,7 +25,6 @@ Deviations from the reference:
       captured step); a frame with more is a ValueError naming it.
 Nothing here synchronises with the device except check_status().
 """
-import concurrent.futures
 import os
 
 import numpy as np
@@ -37,6 +36,9 @@ from ._lib import check, dev_tensor, ptr, require, stream_ptr
 from .inference import CLASSES, rescale_p2
 
 STATUS_BAD_FG = 1                                # include/hfops.h HF_RCNN_BATCH_BAD_FG
+# the fields of the RCNN batch's meta buffer (the host views and, through kitti_data.upload_buffers, the device views)
+META_DTYPES = {"img_offsets": np.int64, "wh": np.int32, "flip": np.int32, "jitter": np.int32, "proposals": np.float32,
+               "proposal_count": np.int32, "gt": np.float32, "gt_count": np.int32, "calib": np.float32}
 HANDOFF_DIRS = ("proposals_and_scores", "rpn_feature", "proposals_iou")
 
 
@@ -232,12 +234,9 @@ class KittiRcnnBatches:
         self.channels = w - 5
         self.num_proposals = max(1, len(read_proposals(fpath["proposals"], first)[0]))
         self.rng_state = torch.tensor(self._rng_host, dtype=torch.int64, device=self.device)
-        self._pool = concurrent.futures.ThreadPoolExecutor(max_workers=max(1, int(workers)))
-        self._ahead = concurrent.futures.ThreadPoolExecutor(max_workers=1)
-        self._staging = [KD._Staging(), KD._Staging()]
-        self._turn = 0
+        self._feed = KD.ReadAhead(self._prepare, workers)
         self._status = []
-        self._pending = self._submit()
+        self._feed.submit(self._take())
 
     def __len__(self):
         return len(self.samples)
@@ -254,10 +253,6 @@ class KittiRcnnBatches:
             raise ValueError("a loader position applies to mode='train' only")
         lp, rng = (self._pending_pos, self._rng_host) if position is None else position
         return {"samples": self.list.state_dict(lp), "rng_state": [int(v) for v in rng]}
-
-    def _submit(self):
-        picks = self._take()
-        return None if picks is None else self._ahead.submit(self._prepare, picks, self._staging[self._turn])
 
     # --------------------------------------------------------------- host side
     def _read(self, i, name, augs, rows):
@@ -288,12 +283,10 @@ class KittiRcnnBatches:
                 "boxes": np.asarray(boxes, np.float32).reshape(-1, 7), "cls": cls, "p2": np.asarray(p2, np.float32),
                 "calib": rescale_p2(p2_aug.astype(np.float32), (w0, h0), (self.img_hw[1], self.img_hw[0]))}
 
-    def _prepare(self, picks, staging):
-        if staging.event is not None:
-            staging.event.synchronize()        # the copy that last read these pinned buffers has finished
+    def _prepare(self, picks, staging, pool):
         b, p, w = len(picks), self.num_points, self.channels + 5
         rows = staging.get("rows", 4 * b * p * w).view(torch.float32).numpy().reshape(b, p, w)
-        frames = list(self._pool.map(lambda a: self._read(a[0], a[1][0], a[1][1], rows[a[0]]), enumerate(picks)))
+        frames = list(pool.map(lambda a: self._read(a[0], a[1][0], a[1][1], rows[a[0]]), enumerate(picks)))
         return self._pack(frames, staging, rows), [f["name"] for f in frames], [f["augs"] for f in frames], \
             [f["p2"] for f in frames], [f["wh"] for f in frames]
 
@@ -306,7 +299,7 @@ class KittiRcnnBatches:
         lay, total = KD._layout(parts)
         meta = staging.get("meta", total)
         mv = meta.numpy()
-        view = {k: mv[o:o + n].view(_META_NP[k]) for k, (o, n) in lay.items()}
+        view = {k: mv[o:o + n].view(META_DTYPES[k]) for k, (o, n) in lay.items()}
         view["proposals"][:] = 0
         view["gt"][:] = 0
         byte = 0
@@ -331,23 +324,14 @@ class KittiRcnnBatches:
 
     # --------------------------------------------------------------- device side
     def next(self):
-        if self._pending is None:
-            raise StopIteration
-        packed, names, augs, p2, wh = self._pending.result()
+        packed, names, augs, p2, wh = self._feed.take()
         position = (self._pending_pos, tuple(self._rng_host)) if self.list is not None else None
         self._rng_host[1] += self.RNG_CALLS_PER_BATCH
-        staging = self._staging[self._turn]
-        self._turn ^= 1
         b, m, g = packed["b"], self.num_proposals, self.max_gt
         with torch.cuda.device(self.device):
-            h = packed["host"]
-            dev = {k: torch.empty(v.shape, dtype=torch.uint8, device=self.device) for k, v in h.items()}
-            for k in dev:
-                dev[k].copy_(h[k], non_blocking=True)
-            staging.event = torch.cuda.Event()
-            staging.event.record()
-            self._pending = self._submit()
-            meta = {k: dev["meta"][o:o + n].view(_META_TORCH[k]) for k, (o, n) in packed["layout"].items()}
+            dev, meta = KD.upload_buffers(packed, self.device, META_DTYPES)
+            self._feed.uploaded()
+            self._feed.submit(self._take())
             rows = dev["rows"].view(torch.float32).view(b, self.num_points, self.channels + 5)
             xyz, inten, fg, fts, status = batch_inputs(rows, meta["flip"])
             image, noise = KD.batch_image(dev["images"], meta["img_offsets"], meta["wh"], meta["flip"], meta["jitter"], self.rng_state,
@@ -374,14 +358,7 @@ class KittiRcnnBatches:
         return {"bad_fg": int(((st & STATUS_BAD_FG) != 0).sum())}
 
     def close(self):
-        self._ahead.shutdown(wait=True)
-        self._pool.shutdown(wait=True)
-
-
-_META_NP = {"img_offsets": np.int64, "wh": np.int32, "flip": np.int32, "jitter": np.int32, "proposals": np.float32,
-            "proposal_count": np.int32, "gt": np.float32, "gt_count": np.int32, "calib": np.float32}
-_META_TORCH = {"img_offsets": torch.int64, "wh": torch.int32, "flip": torch.int32, "jitter": torch.int32, "proposals": torch.float32,
-               "proposal_count": torch.int32, "gt": torch.float32, "gt_count": torch.int32, "calib": torch.float32}
+        self._feed.close()
 
 
 # ------------------------------------------------------------------------------------------------ second stage on val

@@ -81,42 +81,44 @@ def train(dataset_dir, split="train", steps=100, batch=8, config="rpn_multiclass
             d.pop("img_fts"), d.pop("calib")
         return d
 
-    steps_per_epoch = max(1, math.ceil(len(data.samples) / batch))
-    cur = data.next()
-    opt = MultiTensorAdam([p for p in model.parameters() if p.requires_grad], lr=lr, tf_epsilon=tf_epsilon, clip_norm=clip_norm,
-                          lr_decay=lr_decay)
-    if ck:
-        opt.load_state_dict(ck["optimizer"])
-    step = TrainStep(model, opt, inputs_of(cur), model.geometry(cur.xyz), graph=graph, loss_fn=loss_fn)
-    if ck:
-        ckpt_mod.load_rng_states(ck["rng"])          # after the capture: its warm-up draws were behind the saved run too
-    keeper = ckpt_mod.Checkpointer(checkpoint_dir, checkpoint_every, max_checkpoints, config, settings, model, opt, data, start, log)
-    prefetch = GeometryPrefetcher(model.geometry, depth=1)
-    prefetch.submit(cur.xyz)
-    losses = []
-    t0 = time.perf_counter()
-    for i in range(n_steps):
-        g = start + i + 1                            # the global step this iteration completes
-        nxt = data.next() if i + 1 < n_steps else None
-        geo = prefetch.get()
-        if nxt is not None:
-            prefetch.submit(nxt.xyz)
-        losses.append(step(geometry=geo, **inputs_of(cur)).clone())
-        if log_every and (i + 1) % log_every == 0:
-            if check_numerics:
-                keeper.check(losses, start + 1)
-            log("step %d loss %.5f seg %.5f bin %.5f reg %.5f fg %d  lr %.3g  %.1f ms/step" % (
-                g, float(losses[-1]), float(parts["segmentation"]), float(parts["bin_classification"]),
-                float(parts["regression"]), int(parts["num_foreground"]), opt.lr_at(g - 1), 1e3 * (time.perf_counter() - t0) / (i + 1)))
-        if keeper.due(g):
-            keeper.write(g, nxt.position if nxt is not None else None, losses, start + 1)
-        if (i + 1) % steps_per_epoch == 0:
-            st = data.check_status()
-            if st["empty"] or st["too_many_far"]:
-                log("status: %d frames with nothing in view, %d with more than P far points" % (st["empty"], st["too_many_far"]))
-        cur = nxt
-    st = data.check_status()
-    data.close()
+    try:
+        steps_per_epoch = max(1, math.ceil(len(data.samples) / batch))
+        cur = data.next()
+        opt = MultiTensorAdam([p for p in model.parameters() if p.requires_grad], lr=lr, tf_epsilon=tf_epsilon, clip_norm=clip_norm,
+                              lr_decay=lr_decay)
+        if ck:
+            opt.load_state_dict(ck["optimizer"])
+        step = TrainStep(model, opt, inputs_of(cur), model.geometry(cur.xyz), graph=graph, loss_fn=loss_fn)
+        if ck:
+            ckpt_mod.load_rng_states(ck["rng"])          # after the capture: its warm-up draws were behind the saved run too
+        keeper = ckpt_mod.Checkpointer(checkpoint_dir, checkpoint_every, max_checkpoints, config, settings, model, opt, data, start, log)
+        prefetch = GeometryPrefetcher(model.geometry, depth=1)
+        prefetch.submit(cur.xyz)
+        losses = []
+        t0 = time.perf_counter()
+        for i in range(n_steps):
+            g = start + i + 1                            # the global step this iteration completes
+            nxt = data.next() if i + 1 < n_steps else None
+            geo = prefetch.get()
+            if nxt is not None:
+                prefetch.submit(nxt.xyz)
+            losses.append(step(geometry=geo, **inputs_of(cur)).clone())
+            if log_every and (i + 1) % log_every == 0:
+                if check_numerics:
+                    keeper.check(losses, start + 1)
+                log("step %d loss %.5f seg %.5f bin %.5f reg %.5f fg %d  lr %.3g  %.1f ms/step" % (
+                    g, float(losses[-1]), float(parts["segmentation"]), float(parts["bin_classification"]),
+                    float(parts["regression"]), int(parts["num_foreground"]), opt.lr_at(g - 1), 1e3 * (time.perf_counter() - t0) / (i + 1)))
+            if keeper.due(g):
+                keeper.write(g, nxt.position if nxt is not None else None, losses, start + 1)
+            if (i + 1) % steps_per_epoch == 0:
+                st = data.check_status()
+                if st["empty"] or st["too_many_far"]:
+                    log("status: %d frames with nothing in view, %d with more than P far points" % (st["empty"], st["too_many_far"]))
+            cur = nxt
+        st = data.check_status()
+    finally:
+        data.close()
     if check_numerics:
         keeper.check(losses, start + 1)
     if save:

@@ -7,6 +7,7 @@ import os
 import shutil
 import subprocess
 import sys
+import threading
 
 import numpy as np
 import pytest
@@ -272,3 +273,34 @@ def test_train_rpn_cli(dataset, tmp_path):
     assert "done: 3 steps" in r.stdout
     sd = torch.load(str(out), map_location="cpu")
     assert any(k.startswith("img_net.") for k in sd) and any(k.startswith("rpn.") for k in sd)
+
+
+def _reader_threads():
+    return [t.name for t in threading.enumerate() if t.name.startswith("hf-read")]
+
+
+def test_close_leaves_no_reader_thread(dataset):
+    data = KD.KittiRpnBatches(dataset, "train", batch=2, workers=2, seed=3)
+    try:
+        data.next()
+        data.next()
+        assert _reader_threads()
+    finally:
+        data.close()
+    assert _reader_threads() == []
+
+
+def test_a_missing_scan_ends_training_with_no_reader_thread_left(dataset, tmp_path):
+    """a fifth labelled frame with calib, label and image but no velodyne file: 12 steps of batch 2 exceed the epoch of 5 frames
+    x 4 augmentation combinations, so the loader's next() meets it whatever the shuffle"""
+    from heterofusionrcnn_amd import train_rpn
+    root = str(tmp_path / "kitti")
+    shutil.copytree(dataset, root)
+    for d, ext in (("calib", ".txt"), ("label_2", ".txt"), ("image_2", ".png")):
+        shutil.copy(os.path.join(root, d, "000000" + ext), os.path.join(root, d, "000004" + ext))
+    with open(os.path.join(root, "train.txt"), "a") as f:
+        f.write("000004\n")
+    with pytest.raises(FileNotFoundError, match="000004"):
+        train_rpn.train(root, "train", steps=12, batch=2, seed=1, log_every=0, workers=2, graph=False,
+                        img_conv=((1, 16), (1, 16), (1, 16), (1, 16)))
+    assert _reader_threads() == []

@@ -6,6 +6,7 @@ import os
 import shutil
 import subprocess
 import sys
+import threading
 
 import numpy as np
 import pytest
@@ -300,3 +301,17 @@ def test_second_stage_from_the_handoff_writes_results(dataset, handoff, tmp_path
         assert len(lines) == written[n] and all(len(l) == 16 for l in lines)
     res = kitti_eval.evaluate_dirs(os.path.join(dataset, "label_2"), res_dir)
     assert res["ap"].shape == (3, 3, 3) and len(res["frames"]) == 4
+
+
+def test_export_and_second_stage_leave_no_worker_thread(dataset, handoff, tmp_path):
+    """the reader threads (hf-read...) and the write-back threads (hf-write...) end with the call that started them"""
+    from heterofusionrcnn_amd import export_rpn, train_rcnn
+    workers = lambda: [t.name for t in threading.enumerate() if t.name.startswith(("hf-read", "hf-write"))]
+    out, _, _ = handoff
+    c = RD.feature_shape(RD.handoff_paths(out, NAMES[0])["features"])[1] - 5
+    written = RD.run_rcnn_from_handoff(train_rcnn.make_trainer(c, IMG_CONV, seed=0), dataset, out, NAMES, str(tmp_path / "results"),
+                                       batch=2, workers=2)
+    assert sorted(written) == NAMES and workers() == []
+    totals = export_rpn.export(dataset, os.path.join(out, "rpn.pt"), str(tmp_path / "handoff"), "train", batch=2, img_conv=IMG_CONV,
+                               workers=2, log=None)
+    assert sorted(totals) == NAMES and workers() == []
