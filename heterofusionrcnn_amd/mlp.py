@@ -1,15 +1,19 @@
-"""Fused training-mode BatchNorm(+ReLU) over channel-last rows -- the MLP half of a set-abstraction
-level (tf_util.conv2d's batch_norm + relu, hf/core/feature_extractors/tf_util.py:190-203,554-581).
+"""The dense half of both stages: the autograd nodes, eval routes and routing decisions of the shared MLPs (tf_util.conv2d's linear +
+batch_norm + relu, hf/core/feature_extractors/tf_util.py:190-203,554-581; pointnet_util.py:156-176), of their first layers on
+neighbourhoods and three_nn rows read in place, of BatchNormReLU (with its fused ELU and dropout), of the tall and narrow linear layers,
+and the bf16 inference and training switches of the wide ones.
 
-HIP kernels in csrc/mlp.hip behind hf_bn_relu_* (include/hfops.h); no framework fallback on the GPU
-path: CUDA tensors always take the HIP kernels."""
+This module decides which kernel a shape takes and keeps the tensors autograd needs; every launch goes through one function of
+_dense_kernels.py.  No framework fallback on the GPU path: a tensor on the host raises."""
 import functools
 import inspect
 
 import torch
 import torch.nn as nn
 
+from . import _dense_kernels as _k
 from . import _lib
+from ._dense_kernels import _STATS_GENERATION, Running, running_stats_written  # noqa: F401  (re-exported: the counter lives there)
 from ._lib import check, ptr, stream_ptr
 
 
@@ -20,19 +24,7 @@ def _on_gpu(*tensors):
             raise RuntimeError("heterofusionrcnn_amd.mlp: tensors must live on the GPU (there is no CPU implementation)")
 
 
-def _workspace(rows, c, device):
-    nbytes = _lib.lib().hf_bn_workspace(rows, c)
-    return torch.empty((nbytes // 4,), dtype=torch.float32, device=device), nbytes
-
-
-# The training kernels update running_mean / running_var through raw pointers, which bumps no tensor version: every launch
-# site that hands those pointers to a kernel calls running_stats_written(), and BatchNormReLU.eval_invstd keys its cache on it.
-_STATS_GENERATION = [0]
-
-
-_DROP_LAYERS = [0]      # BatchNormReLU modules built so far in this process (distinct dropout seeds per layer)
-
-
+_DROP_LAYERS = [0]     # BatchNormReLU modules built so far in this process (distinct dropout seeds per layer)
 DROPOUT_SALT = None     # tests: a fixed salt instead of the rank (to reproduce another rank's masks in one process)
 
 
@@ -44,22 +36,10 @@ def _dropout_salt():
     return dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
 
 
-def running_stats_written():
-    _STATS_GENERATION[0] += 1
-
-
 class _BNReLUTrain(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, gamma, beta, running_mean, running_var, eps, momentum, relu):
-        running_stats_written()          # the kernel below writes the running statistics through raw pointers
-        rows, c = x.shape
-        y = torch.empty_like(x)
-        mean = torch.empty((c,), dtype=torch.float32, device=x.device)
-        invstd = torch.empty((c,), dtype=torch.float32, device=x.device)
-        ws, nbytes = _workspace(rows, c, x.device)
-        check(_lib.lib().hf_bn_relu_fwd_train(rows, c, ptr(x), ptr(gamma), ptr(beta), eps, momentum, ptr(running_mean),
-                                              ptr(running_var), int(relu), ptr(y), ptr(mean), ptr(invstd),
-                                              ptr(ws), nbytes, stream_ptr()), "bn_relu_fwd_train")
+        y, mean, invstd = _k.bn_fwd_train(x, gamma, beta, Running(running_mean, running_var, eps, momentum), int(relu))
         ctx.save_for_backward(x, gamma, beta, mean, invstd)
         ctx.relu = int(relu)   # mode bits: 1 = ReLU after, 2 = ELU before
         return y
@@ -67,15 +47,7 @@ class _BNReLUTrain(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x, gamma, beta, mean, invstd = ctx.saved_tensors
-        rows, c = x.shape
-        dy = dy.contiguous()
-        dx = torch.empty_like(x)
-        dgamma = torch.empty_like(gamma)
-        dbeta = torch.empty_like(beta)
-        ws, nbytes = _workspace(rows, c, x.device)
-        check(_lib.lib().hf_bn_relu_bwd(rows, c, ptr(x), ptr(dy), ptr(gamma), ptr(beta), ptr(mean), ptr(invstd),
-                                        ctx.relu, ptr(dx), ptr(dgamma), ptr(dbeta), None, ptr(ws), nbytes,
-                                        stream_ptr()), "bn_relu_bwd")
+        dx, dgamma, dbeta, _ = _k.bn_bwd(x, dy.contiguous(), gamma, beta, mean, invstd, ctx.relu)
         return dx, dgamma, dbeta, None, None, None, None, None
 
 
@@ -85,16 +57,8 @@ class _BNDropoutTrain(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, gamma, beta, running_mean, running_var, eps, momentum, relu, rate, drop_state, salt):
-        running_stats_written()
-        rows, c = x.shape
-        y = torch.empty_like(x)
-        mean = torch.empty((c,), dtype=torch.float32, device=x.device)
-        invstd = torch.empty((c,), dtype=torch.float32, device=x.device)
-        seed = torch.empty((1,), dtype=torch.int64, device=x.device)
-        ws, nbytes = _workspace(rows, c, x.device)
-        check(_lib.lib().hf_bn_dropout_fwd_train(rows, c, ptr(x), ptr(gamma), ptr(beta), eps, momentum, ptr(running_mean), ptr(running_var),
-                                                 int(relu), float(rate), int(salt), ptr(drop_state), ptr(seed), ptr(y), ptr(mean), ptr(invstd),
-                                                 ptr(ws), nbytes, stream_ptr()), "bn_dropout_fwd_train")
+        y, mean, invstd, seed = _k.bn_dropout_fwd(x, gamma, beta, Running(running_mean, running_var, eps, momentum), int(relu), float(rate),
+                                                  int(salt), drop_state)
         ctx.save_for_backward(x, gamma, beta, mean, invstd, seed)
         ctx.relu, ctx.rate = int(relu), float(rate)
         return y
@@ -102,14 +66,7 @@ class _BNDropoutTrain(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x, gamma, beta, mean, invstd, seed = ctx.saved_tensors
-        rows, c = x.shape
-        dy = dy.contiguous()
-        dx = torch.empty_like(x)
-        dgamma = torch.empty_like(gamma)
-        dbeta = torch.empty_like(beta)
-        ws, nbytes = _workspace(rows, c, x.device)
-        check(_lib.lib().hf_bn_dropout_bwd(rows, c, ptr(x), ptr(dy), ptr(gamma), ptr(beta), ptr(mean), ptr(invstd), ctx.relu, ctx.rate,
-                                           ptr(seed), ptr(dx), ptr(dgamma), ptr(dbeta), ptr(ws), nbytes, stream_ptr()), "bn_dropout_bwd")
+        dx, dgamma, dbeta = _k.bn_dropout_bwd(x, dy.contiguous(), gamma, beta, mean, invstd, ctx.relu, ctx.rate, seed)
         return dx, dgamma, dbeta, None, None, None, None, None, None, None, None
 
 
@@ -160,11 +117,7 @@ class _LinearSplitK(torch.autograd.Function):
         return dx, dw
 
 
-class _NoBN:
-    eps, momentum, running_mean, running_var = 1e-5, 0.0, None, None
-
-
-_NO_BN = _NoBN()
+_NO_BN = Running(None, None, 1e-5, 0.0)     # linear_bn_fwd without a BatchNorm behind it: update_running=False
 _ZEROS = {}
 
 
@@ -189,11 +142,7 @@ class _NarrowLinear(torch.autograd.Function):
     def backward(ctx, g):
         x, weight = ctx.saved_tensors
         g = g.contiguous()
-        dx = None
-        if ctx.needs_input_grad[0]:
-            dx = torch.empty_like(x)
-            check(_lib.lib().hf_narrow_linear_dx(x.shape[0], x.shape[1], weight.shape[0], ptr(g), ptr(weight.contiguous()), ptr(dx),
-                                                 stream_ptr()), "narrow_linear_dx")
+        dx = _k.narrow_linear_dx(g, weight.contiguous(), x.shape[1]) if ctx.needs_input_grad[0] else None
         dw = _splitk_wgrad(g, x) if ctx.needs_input_grad[1] else None
         db = g.sum(0) if ctx.needs_input_grad[2] else None
         return dx, dw, db
@@ -227,16 +176,7 @@ def linear_wgrad(grad_z, x, in_bn=None):
     summed in a fixed order.  in_bn = (gamma, beta, mean, invstd) of the previous layer: x is then that layer's
     pre-BN output and relu(bn(x)) is applied while it is staged."""
     _on_gpu(grad_z, x)
-    rows, cout = grad_z.shape
-    cin = x.shape[1]
-    L = _lib.lib()
-    nbytes = L.hf_linear_wgrad_workspace(rows, cout, cin)
-    ws = torch.empty((nbytes // 4,), dtype=torch.float32, device=x.device)
-    dw = torch.empty((cout, cin), dtype=torch.float32, device=x.device)
-    g, b, m, i = in_bn if in_bn is not None else (None, None, None, None)
-    check(L.hf_linear_wgrad(rows, cout, cin, ptr(grad_z), ptr(x), ptr(g), ptr(b), ptr(m), ptr(i), ptr(dw), ptr(ws), nbytes,
-                            stream_ptr()), "linear_wgrad")
-    return dw
+    return _k.linear_wgrad(grad_z, x, in_bn)
 
 
 def linear_bn_fwd(x, weight, bias, bn, in_bn=None, keep_act=False, update_running=True):
@@ -246,23 +186,7 @@ def linear_bn_fwd(x, weight, bias, bn, in_bn=None, keep_act=False, update_runnin
     applied on load; keep_act also stores that activated input (x_act, else None); update_running=False leaves the
     running estimates alone (inference: the returned batch statistics are then simply not used)."""
     _on_gpu(x, weight, bias)
-    if update_running:
-        running_stats_written()
-    rows, cin = x.shape
-    cout = weight.shape[0]
-    L = _lib.lib()
-    nbytes = L.hf_linear_bn_fwd_workspace(cout)
-    ws = torch.empty((nbytes // 4,), dtype=torch.float32, device=x.device)
-    z = torch.empty((rows, cout), dtype=torch.float32, device=x.device)
-    mean = torch.empty((cout,), dtype=torch.float32, device=x.device)
-    invstd = torch.empty((cout,), dtype=torch.float32, device=x.device)
-    g, b, m, i = in_bn if in_bn is not None else (None, None, None, None)
-    x_act = torch.empty_like(x) if (keep_act and in_bn is not None) else None
-    check(L.hf_linear_bn_fwd(rows, cin, cout, ptr(x), ptr(g), ptr(b), ptr(m), ptr(i), ptr(x_act), ptr(weight), ptr(bias),
-                             ptr(z), bn.eps, bn.momentum, ptr(bn.running_mean) if update_running else None,
-                             ptr(bn.running_var) if update_running else None, ptr(mean),
-                             ptr(invstd), ptr(ws), nbytes, stream_ptr()), "linear_bn_fwd")
-    return z, mean, invstd, x_act
+    return _k.linear_bn_fwd(x, weight, bias, bn, in_bn, keep_act, update_running)
 
 
 # The MFMA forward pays off where the layer is bound by memory traffic: enough 128-row tiles to fill the chip and at
@@ -305,22 +229,31 @@ def inference_precision_name():
     return _INFERENCE_PRECISION[0]
 
 
-class inference_precision:
-    """with mlp.inference_precision("bf16"): ... -- the previous setting returns on exit"""
+class _PrecisionScope:
+    """with mlp.inference_precision("bf16"): ... / with mlp.training_precision("bf16"): ... -- the previous setting returns on exit"""
 
-    def __init__(self, precision):
+    def __init__(self, cell, precision):
         if precision not in PRECISIONS:
             raise ValueError("precision must be one of %s, got %r" % (PRECISIONS, precision))
-        self.precision = precision
+        self.cell, self.precision = cell, precision
 
     def __enter__(self):
-        self.previous = _INFERENCE_PRECISION[0]
-        _INFERENCE_PRECISION[0] = self.precision
+        self.previous = self.cell[0]
+        self.cell[0] = self.precision
         return self
 
     def __exit__(self, *exc):
-        _INFERENCE_PRECISION[0] = self.previous
+        self.cell[0] = self.previous
         return False
+
+
+inference_precision = functools.partial(_PrecisionScope, _INFERENCE_PRECISION)
+
+
+def _bf16_operands(x, weight):
+    """what both bf16 routes ask of their operands: x fp32 on the device with cin columns, cin and cout multiples of 4 (16-byte rows)"""
+    cout, cin = weight.shape
+    return x.is_cuda and x.dtype == torch.float32 and cin % 4 == 0 and cout % 4 == 0 and x.shape[-1] == cin
 
 
 def bf16_route_pays(rows, cin, cout):
@@ -329,10 +262,10 @@ def bf16_route_pays(rows, cin, cout):
 
 def bf16_route(x, weight):
     """does x (.., cin) times weight (cout, cin)^T take the bf16 kernel?  The caller has checked that its layer is in eval mode."""
-    if _INFERENCE_PRECISION[0] != "bf16" or torch.is_grad_enabled() or not x.is_cuda or x.dtype != torch.float32:
+    if _INFERENCE_PRECISION[0] != "bf16" or torch.is_grad_enabled() or not _bf16_operands(x, weight):
         return False
     cout, cin = weight.shape
-    return cin % 4 == 0 and cout % 4 == 0 and x.shape[-1] == cin and bf16_route_pays(x.numel() // cin, cin, cout)
+    return bf16_route_pays(x.numel() // cin, cin, cout)
 
 
 def _bf16_weight(weight):
@@ -344,9 +277,7 @@ def _bf16_weight(weight):
     held = getattr(weight, "_hf_bf16", None) if not capturing else None
     if held is not None and held[0] == key:
         return held[1]
-    w = weight.detach().contiguous()
-    wb = torch.empty(w.shape, dtype=torch.bfloat16, device=w.device)
-    check(_lib.lib().hf_f32_to_bf16(w.numel(), ptr(w), ptr(wb), stream_ptr()), "f32_to_bf16")
+    wb = _k.f32_to_bf16(weight.detach().contiguous())
     if not capturing:
         weight._hf_bf16 = (key, wb)
     return wb
@@ -357,16 +288,10 @@ def linear_bf16_eval(x, weight, bias, bn, mode):
     runs in the GEMM's epilogue (mode = (1: ReLU) | (2: ELU before the normalisation), its own flags), or None (mode 0)."""
     _on_gpu(x, weight, bias)
     assert x.dim() == 2 and (bn is not None or mode == 0)
-    x = x.contiguous()
-    rows, cin = x.shape
-    cout = weight.shape[0]
-    wb = _bf16_weight(weight)
-    y = torch.empty((rows, cout), dtype=torch.float32, device=x.device)
-    g, b, m, s = (bn.weight, bn.bias, bn.running_mean, bn.eval_invstd()) if bn is not None else (None, None, None, None)
+    x, wb = x.contiguous(), _bf16_weight(weight)
     BF16_ROUTED_CALLS[0] += 1
-    check(_lib.lib().hf_linear_bf16_fwd_eval(rows, cin, cout, ptr(x), ptr(wb), ptr(bias), ptr(g), ptr(b), ptr(m), ptr(s), mode, ptr(y),
-                                             stream_ptr()), "linear_bf16_fwd_eval")
-    return y
+    bn4 = (bn.weight, bn.bias, bn.running_mean, bn.eval_invstd()) if bn is not None else (None, None, None, None)
+    return _k.bf16_gemm(x, wb, bias, bn4, mode)
 
 
 # ------------------------------------------------------------------------------------------------ bf16 training
@@ -397,22 +322,7 @@ def training_precision_name():
     return _TRAINING_PRECISION[0]
 
 
-class training_precision:
-    """with mlp.training_precision("bf16"): ... -- the previous setting returns on exit"""
-
-    def __init__(self, precision):
-        if precision not in PRECISIONS:
-            raise ValueError("precision must be one of %s, got %r" % (PRECISIONS, precision))
-        self.precision = precision
-
-    def __enter__(self):
-        self.previous = _TRAINING_PRECISION[0]
-        _TRAINING_PRECISION[0] = self.precision
-        return self
-
-    def __exit__(self, *exc):
-        _TRAINING_PRECISION[0] = self.previous
-        return False
+training_precision = functools.partial(_PrecisionScope, _TRAINING_PRECISION)
 
 
 def under_training_precision(fn):
@@ -438,36 +348,25 @@ def bf16_train_route_pays(rows, cin, cout):
 def bf16_train_route(x, weight):
     """does x (.., cin) times weight (cout, cin)^T, with its two gradients, take the bf16 kernels?  The caller has checked that its
     layer is in training mode and may leave fp32."""
-    if _TRAINING_PRECISION[0] != "bf16" or not torch.is_grad_enabled() or not x.is_cuda or x.dtype != torch.float32:
-        return False
-    if not weight.is_cuda or weight.dtype != torch.float32:
+    if _TRAINING_PRECISION[0] != "bf16" or not torch.is_grad_enabled() or not _bf16_operands(x, weight):
         return False
     cout, cin = weight.shape
-    if max(cin, cout) > 32768:           # the weight-gradient kernel's limit
+    if not weight.is_cuda or weight.dtype != torch.float32 or max(cin, cout) > 32768:    # 32768: the weight-gradient kernel's limit
         return False
-    return cin % 4 == 0 and cout % 4 == 0 and x.shape[-1] == cin and bf16_train_route_pays(x.numel() // cin, cin, cout)
+    return bf16_train_route_pays(x.numel() // cin, cin, cout)
 
 
 def _bf16_gemm(rows, cin, cout, x, wb):
-    """(rows, cin) fp32 times wb (cout, cin) bf16, transposed -> (rows, cout) fp32: hf_linear_bf16_fwd_eval without an epilogue"""
-    y = torch.empty((rows, cout), dtype=torch.float32, device=x.device)
-    check(_lib.lib().hf_linear_bf16_fwd_eval(rows, cin, cout, ptr(x), ptr(wb), None, None, None, None, None, 0, ptr(y), stream_ptr()),
-          "linear_bf16_fwd_eval")
-    return y
+    """(rows, cin) fp32 times wb (cout, cin) bf16, transposed -> (rows, cout) fp32: the inference kernel without an epilogue.  The three
+    sizes are kept for the callers that pass them (scripts/probes/bf16_train_linear_timing.py); they are read off x and wb"""
+    return _k.bf16_gemm(x, wb)
 
 
 def linear_bf16_wgrad(grad_z, x):
     """dW (cout, cin) = bf16(grad_z)^T bf16(x), fp32 accumulation (csrc/linear_bf16_train.hip): rows cut into chunks, partial tiles summed
     in a fixed order"""
     _on_gpu(grad_z, x)
-    rows, cout = grad_z.shape
-    cin = x.shape[1]
-    L = _lib.lib()
-    nbytes = L.hf_linear_bf16_wgrad_workspace(rows, cout, cin)
-    ws = torch.empty((max(nbytes, 16) // 4,), dtype=torch.float32, device=x.device)
-    dw = torch.empty((cout, cin), dtype=torch.float32, device=x.device)
-    check(L.hf_linear_bf16_wgrad(rows, cout, cin, ptr(grad_z), ptr(x), ptr(dw), ptr(ws), nbytes, stream_ptr()), "linear_bf16_wgrad")
-    return dw
+    return _k.linear_bf16_wgrad(grad_z, x)
 
 
 class _LinearBf16Train(torch.autograd.Function):
@@ -480,13 +379,8 @@ class _LinearBf16Train(torch.autograd.Function):
         rows, cin = x.shape
         cout = weight.shape[0]
         w = weight.detach().contiguous()
-        L = _lib.lib()
-        wb = torch.empty((cout, cin), dtype=torch.bfloat16, device=w.device)
-        check(L.hf_f32_to_bf16(w.numel(), ptr(w), ptr(wb), stream_ptr()), "f32_to_bf16")
-        wtb = None
-        if ctx.needs_input_grad[0]:
-            wtb = torch.empty((cin, cout), dtype=torch.bfloat16, device=w.device)
-            check(L.hf_f32_to_bf16_transpose(cout, cin, ptr(w), ptr(wtb), stream_ptr()), "f32_to_bf16_transpose")
+        wb = _k.f32_to_bf16(w)
+        wtb = _k.f32_to_bf16(w, transpose=True) if ctx.needs_input_grad[0] else None
         BF16_TRAIN_ROUTED_CALLS[0] += 1
         ctx.save_for_backward(x, wtb)
         return _bf16_gemm(rows, cin, cout, x, wb)
@@ -503,24 +397,6 @@ class _LinearBf16Train(torch.autograd.Function):
         return dx, dw
 
 
-def _bn_apply(z, gamma, beta, mean, invstd):
-    y = torch.empty_like(z)
-    check(_lib.lib().hf_bn_relu_fwd_eval(z.shape[0], z.shape[1], ptr(z), ptr(gamma), ptr(beta), ptr(mean), ptr(invstd), 1,
-                                         ptr(y), stream_ptr()), "bn_relu_apply")
-    return y
-
-
-def _bn_stats(z, bn):
-    running_stats_written()
-    rows, c = z.shape
-    mean = torch.empty((c,), dtype=torch.float32, device=z.device)
-    invstd = torch.empty((c,), dtype=torch.float32, device=z.device)
-    ws, nbytes = _workspace(rows, c, z.device)
-    check(_lib.lib().hf_bn_stats(rows, c, ptr(z), bn.eps, bn.momentum, ptr(bn.running_mean), ptr(bn.running_var), ptr(mean),
-                                 ptr(invstd), ptr(ws), nbytes, stream_ptr()), "bn_stats")
-    return mean, invstd
-
-
 class _SharedMLPChain(torch.autograd.Function):
     """A whole shared MLP (tf_util.conv2d([1,1], bn=True) x L, pointnet_util.py:156-160) as ONE autograd node,
     optionally ending in the max over the K grouped rows (:163-176).
@@ -535,7 +411,6 @@ class _SharedMLPChain(torch.autograd.Function):
     def forward(ctx, x, pool_k, layers, first, *params):
         """first = (mean0, invstd0): x IS the first layer's pre-BN output (its linear ran in _GatherLinear, on neighbourhoods
         read in place); the node then starts at that layer's BatchNorm and hands dz0 back as the gradient of x"""
-        L = _lib.lib()
         n = len(layers)
         saved, cur, in_bn = [], x, None
         for li, layer in enumerate(layers):
@@ -546,33 +421,21 @@ class _SharedMLPChain(torch.autograd.Function):
                 z, mean, invstd, x_act = linear_bn_fwd(cur, w, b, layer.bn, in_bn, keep_act=True)
                 xin = x_act if x_act is not None else cur
             else:  # library GEMM on the materialised input, statistics in their own pass
-                xin = _bn_apply(cur, *in_bn) if in_bn is not None else cur
+                xin = _k.bn_apply(cur, *in_bn, 1) if in_bn is not None else cur
                 z = torch.addmm(b, xin, w.t())
-                mean, invstd = _bn_stats(z, layer.bn)
+                mean, invstd = _k.bn_stats(z, layer.bn)
             saved.append((xin, z, mean, invstd))
             cur, in_bn = z, (gamma, beta, mean, invstd)
-        gamma, beta, mean, invstd = in_bn
-        rows, cout = cur.shape
         if pool_k:
-            groups = rows // pool_k
-            out = torch.empty((groups, cout), dtype=torch.float32, device=x.device)
-            argmax = torch.empty((groups, cout), dtype=torch.uint8, device=x.device)
-            check(L.hf_bn_relu_maxpool_fwd(groups, pool_k, cout, ptr(cur), ptr(gamma), ptr(beta), 0, 0.0, 0.0, None, None,
-                                           ptr(mean), ptr(invstd), ptr(out), ptr(argmax), None, 0, stream_ptr()),
-                  "bn_relu_maxpool_fwd")
+            out, argmax = _k.bn_maxpool_fwd(cur, pool_k, *in_bn)[:2]
         else:
-            argmax = None
-            out = _bn_apply(cur, gamma, beta, mean, invstd)
-        flat = []
-        for t in saved:
-            flat.extend(t)
-        ctx.save_for_backward(*flat, *params, *([argmax] if argmax is not None else []))
+            out, argmax = _k.bn_apply(cur, *in_bn, 1), None
+        ctx.save_for_backward(*(t for layer_saved in saved for t in layer_saved), *params, *([argmax] if argmax is not None else []))
         ctx.n, ctx.pool_k, ctx.first = n, pool_k, first is not None
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        L = _lib.lib()
         n, pool_k = ctx.n, ctx.pool_k
         tensors = ctx.saved_tensors
         saved = [tensors[4 * i:4 * i + 4] for i in range(n)]
@@ -598,47 +461,22 @@ class _SharedMLPChain(torch.autograd.Function):
             dbias = zero_bias[sum(couts[:li]):sum(couts[:li + 1])]
             dz, from_dy = None, False
             if known is None:  # reduce + dx passes of the BN backward (the pooled tail has its own pair)
-                dz = torch.empty_like(z)
-                dgamma, dbeta = torch.empty_like(gamma), torch.empty_like(beta)
-                ws, nbytes = _workspace(rows, cout, z.device)
                 if li == n - 1 and pool_k:
-                    check(L.hf_bn_relu_maxpool_bwd(rows // pool_k, pool_k, cout, ptr(z), ptr(dy), ptr(argmax), ptr(gamma),
-                                                   ptr(beta), ptr(mean), ptr(invstd), ptr(dz), ptr(dgamma), ptr(dbeta),
-                                                   None, ptr(ws), nbytes, stream_ptr()), "bn_relu_maxpool_bwd")
+                    dz, dgamma, dbeta, _ = _k.bn_maxpool_bwd(z, dy, argmax, pool_k, gamma, beta, mean, invstd)
                 else:
-                    check(L.hf_bn_relu_bwd(rows, cout, ptr(z), ptr(dy), ptr(gamma), ptr(beta), ptr(mean), ptr(invstd), 1,
-                                           ptr(dz), ptr(dgamma), ptr(dbeta), None, ptr(ws), nbytes, stream_ptr()),
-                          "bn_relu_bwd")
+                    dz, dgamma, dbeta, _ = _k.bn_bwd(z, dy, gamma, beta, mean, invstd, 1)
             else:
                 dgamma, dbeta = known
                 if mfma:
                     from_dy = True  # dz is rebuilt inside the input-gradient kernel while its operand is staged
                 else:
-                    dz = torch.empty_like(z)
-                    check(L.hf_bn_relu_bwd_dx(rows, cout, ptr(z), ptr(dy), ptr(gamma), ptr(beta), ptr(mean), ptr(invstd),
-                                              ptr(dgamma), ptr(dbeta), 1, ptr(dz), stream_ptr()), "bn_relu_bwd_dx")
+                    dz = _k.bn_bwd_dx(z, dy, gamma, beta, mean, invstd, dgamma, dbeta, 1)
             known = None
             if mfma:
-                wt = w.t().contiguous()
-                dx = torch.empty((rows, cin), dtype=torch.float32, device=z.device)
-                if from_dy:
-                    dz = torch.empty_like(z)
-                if li > 0:  # the BN-backward sums of the layer below come out of this kernel's accumulators
-                    pz, pmean, pinv = saved[li - 1][1:4]
-                    pgamma, pbeta = params[4 * (li - 1) + 2], params[4 * (li - 1) + 3]
-                    pdg, pdb = torch.empty_like(pgamma), torch.empty_like(pbeta)
-                    nbytes = L.hf_linear_bn_bwd_workspace(cin)
-                    ws = torch.empty((nbytes // 4,), dtype=torch.float32, device=z.device)
-                    known = (pdg, pdb)
-                else:
-                    pz = pmean = pinv = pgamma = pbeta = pdg = pdb = ws = None
-                    nbytes = 0
-                check(L.hf_linear_bn_bwd(rows, cout, cin, ptr(dy if from_dy else dz), ptr(z) if from_dy else None,
-                                         ptr(gamma), ptr(beta), ptr(mean), ptr(invstd), ptr(dgamma), ptr(dbeta),
-                                         ptr(dz) if from_dy else None, ptr(wt), ptr(dx), ptr(pz), ptr(pgamma), ptr(pbeta),
-                                         ptr(pmean), ptr(pinv), ptr(pdg), ptr(pdb), ptr(ws), nbytes, stream_ptr()),
-                      "linear_bn_bwd")
-                dy = dx
+                # the BN-backward sums of the layer below, (z, gamma, beta, mean, invstd), come out of this kernel's accumulators
+                prev = (saved[li - 1][1], *params[4 * li - 2:4 * li], *saved[li - 1][2:4]) if li > 0 else None
+                dy, dz, known = _k.linear_bn_bwd(dy if from_dy else dz, w.t().contiguous(), z, gamma, beta, mean, invstd, dgamma, dbeta,
+                                                 from_dy, prev)
             elif need_dx:
                 dy = dz @ w
             if gathered:
@@ -652,7 +490,6 @@ class _SharedMLPChain(torch.autograd.Function):
 def _shared_mlp_eval(layers, x, pool_k, extra, first_done=False):
     """inference twin of _SharedMLPChain.forward: running statistics instead of batch statistics, nothing saved.
     first_done: x is already the first layer's pre-BN output (shared_mlp_grouped)"""
-    L = _lib.lib()
     cur, in_bn = x, None
     for i, layer in enumerate(layers):
         w = layer.fc.weight if (i or not extra) else torch.nn.functional.pad(layer.fc.weight, (0, extra))
@@ -662,7 +499,7 @@ def _shared_mlp_eval(layers, x, pool_k, extra, first_done=False):
         elif _mfma_forward_pays(cur.shape[0], w.shape[1], w.shape[0]):
             z = linear_bn_fwd(cur, w, layer.fc.bias, bn, in_bn, update_running=False)[0]
         else:
-            xin = _bn_apply(cur, *in_bn) if in_bn is not None else cur
+            xin = _k.bn_apply(cur, *in_bn, 1) if in_bn is not None else cur
             if w is layer.fc.weight and bf16_route(xin, w):
                 if pool_k and i == len(layers) - 1:      # the pooling kernel normalises: the GEMM alone
                     z = linear_bf16_eval(xin, w, layer.fc.bias, None, 0)
@@ -674,14 +511,9 @@ def _shared_mlp_eval(layers, x, pool_k, extra, first_done=False):
         cur, in_bn = z, (bn.weight, bn.bias, bn.running_mean, bn.eval_invstd())
     if in_bn is None:
         return cur
-    gamma, beta, mean, invstd = in_bn
     if not pool_k:
-        return _bn_apply(cur, gamma, beta, mean, invstd)
-    rows, cout = cur.shape
-    out = torch.empty((rows // pool_k, cout), dtype=torch.float32, device=x.device)
-    check(L.hf_bn_relu_maxpool_fwd(rows // pool_k, pool_k, cout, ptr(cur), ptr(gamma), ptr(beta), 0, 0.0, 0.0, None, None,
-                                   ptr(mean), ptr(invstd), ptr(out), None, None, 0, stream_ptr()), "bn_relu_maxpool_fwd")
-    return out
+        return _k.bn_apply(cur, *in_bn, 1)
+    return _k.bn_maxpool_fwd(cur, pool_k, *in_bn, want_argmax=False)[0]
 
 
 def _gather_weight(w, c, xyz_first):
@@ -709,27 +541,11 @@ class _GatherLinear(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, points, idx, gxyz, weight, bias, bn, xyz_first, update_running):
-        L = _lib.lib()
         b, m, k = idx.shape
-        rows = b * m * k
-        c = points.shape[2] if points is not None else 0
-        n_src = points.shape[1] if points is not None else 1
-        cout = weight.shape[0]
-        dev = idx.device
-        wi = _gather_weight(weight, c, xyz_first)
-        z = torch.empty((rows, cout), dtype=torch.float32, device=dev)
-        mean = torch.empty((cout,), dtype=torch.float32, device=dev)
-        invstd = torch.empty((cout,), dtype=torch.float32, device=dev)
-        nbytes = L.hf_linear_bn_fwd_workspace(cout)
-        ws = torch.empty((nbytes // 4,), dtype=torch.float32, device=dev)
-        if update_running:
-            running_stats_written()
-        check(L.hf_linear_bn_fwd_gather(rows, c, cout, ptr(points), n_src, m * k, ptr(idx), ptr(gxyz), ptr(wi), ptr(bias), ptr(z),
-                                        bn.eps, bn.momentum, ptr(bn.running_mean) if update_running else None,
-                                        ptr(bn.running_var) if update_running else None, ptr(mean), ptr(invstd), ptr(ws), nbytes,
-                                        stream_ptr()), "linear_bn_fwd_gather")
+        c, n_src = (points.shape[2], points.shape[1]) if points is not None else (0, 1)
+        z, mean, invstd = _k.linear_bn_fwd_gather(points, idx, gxyz, _gather_weight(weight, c, xyz_first), bias, bn, update_running)
         ctx.save_for_backward(idx, gxyz, weight, *([points] if points is not None else []))
-        ctx.dims = (b, m, k, c, n_src, cout, xyz_first)
+        ctx.dims = (b, m, k, c, n_src, weight.shape[0], xyz_first)
         ctx.mark_non_differentiable(mean, invstd)
         return z, mean, invstd
 
@@ -739,15 +555,8 @@ class _GatherLinear(torch.autograd.Function):
         idx, gxyz, weight, *rest = ctx.saved_tensors
         points = rest[0] if rest else None
         b, m, k, c, n_src, cout, xyz_first = ctx.dims
-        rows = b * m * k
         dz = dz.contiguous()
-        cin = (c + 3) // 4 * 4 + 4
-        nbytes = L.hf_linear_wgrad_workspace(rows, cout, cin)
-        ws = torch.empty((nbytes // 4,), dtype=torch.float32, device=dz.device)
-        dwi = torch.empty((cout, cin), dtype=torch.float32, device=dz.device)
-        check(L.hf_linear_wgrad_gather(rows, cout, c, ptr(dz), ptr(points), n_src, m * k, ptr(idx), ptr(gxyz), ptr(dwi), ptr(ws),
-                                       nbytes, stream_ptr()), "linear_wgrad_gather")
-        dw = _ungather_weight(dwi, c, xyz_first)
+        dw = _ungather_weight(_k.linear_wgrad_gather(dz, points, idx, gxyz, c, n_src), c, xyz_first)
         dpoints = None
         if points is not None and ctx.needs_input_grad[0]:
             wf = (weight[:, 3:3 + c] if xyz_first else weight[:, :c]).contiguous()
@@ -781,22 +590,9 @@ def shared_mlp_grouped(layers, points, idx, grouped_xyz, xyz_first=True, pool=Tr
     neighbours (pool) or (B*M*K, Cout).  The first layer gathers while it stages its operand; the rest is shared_mlp's chain.
     xyz_first: the reference's column order of the first weight, [xyz | features] (single-scale module) or [features | xyz]."""
     layers = list(layers)
-    b, m, k = idx.shape
-    training = all(l.bn.training for l in layers)
-    first = layers[0]
-    if training and torch.is_grad_enabled():
-        z0, mean0, invstd0 = _GatherLinear.apply(points, idx, grouped_xyz.detach().contiguous(), first.fc.weight, first.fc.bias, first.bn,
-                                                 xyz_first, True)
-        params = []
-        for l in layers:
-            params += [l.fc.weight, l.fc.bias, l.bn.weight, l.bn.bias]
-        return _SharedMLPChain.apply(z0, k if pool else 0, layers, (mean0, invstd0), *params)
-    require_eval = not any(l.bn.training for l in layers)
-    assert require_eval, "shared_mlp_grouped: training-mode BatchNorm needs autograd enabled (or call .eval())"
-    # inference: running statistics; the first layer still gathers in place (its batch statistics are simply not used)
-    with torch.no_grad():
-        z0, _, _ = _GatherLinear.apply(points, idx, grouped_xyz.contiguous(), first.fc.weight, first.fc.bias, first.bn, xyz_first, False)
-    return _shared_mlp_eval(layers, z0, k if pool else 0, 0, first_done=True)
+    first, gxyz = layers[0], grouped_xyz.detach().contiguous()
+    return _first_layer_then_chain("shared_mlp_grouped", layers, idx.shape[2] if pool else 0, lambda update_running: _GatherLinear.apply(
+        points, idx, gxyz, first.fc.weight, first.fc.bias, first.bn, xyz_first, update_running))
 
 
 class _InterpLinear(torch.autograd.Function):
@@ -809,25 +605,13 @@ class _InterpLinear(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, points2, points1, idx, weight3, offsets, entries, weight, bias, bn, update_running):
-        L = _lib.lib()
         b, n, _ = idx.shape
         m, c2 = points2.shape[1], points2.shape[2]
         c1 = points1.shape[2] if points1 is not None else 0
-        rows, cout = b * n, weight.shape[0]
+        cout = weight.shape[0]
         cin = (c2 + c1 + 3) // 4 * 4
-        dev = idx.device
         wp = torch.nn.functional.pad(weight.detach(), (0, cin - c2 - c1)) if cin != c2 + c1 else weight.detach().contiguous()
-        z = torch.empty((rows, cout), dtype=torch.float32, device=dev)
-        mean = torch.empty((cout,), dtype=torch.float32, device=dev)
-        invstd = torch.empty((cout,), dtype=torch.float32, device=dev)
-        nbytes = L.hf_linear_bn_fwd_workspace(cout)
-        ws = torch.empty((nbytes // 4,), dtype=torch.float32, device=dev)
-        if update_running:
-            running_stats_written()
-        check(L.hf_linear_bn_fwd_interp(rows, c2, c1, cout, ptr(points2), m, n, ptr(idx), ptr(weight3), ptr(points1), ptr(wp), ptr(bias),
-                                        ptr(z), bn.eps, bn.momentum, ptr(bn.running_mean) if update_running else None,
-                                        ptr(bn.running_var) if update_running else None, ptr(mean), ptr(invstd), ptr(ws), nbytes,
-                                        stream_ptr()), "linear_bn_fwd_interp")
+        z, mean, invstd = _k.linear_bn_fwd_interp(points2, points1, idx, weight3, wp, bias, bn, update_running)
         ctx.save_for_backward(points2, idx, weight3, wp, *([points1] if points1 is not None else []),
                               *([offsets, entries] if offsets is not None else []))
         ctx.dims = (b, n, m, c2, c1, cout, cin, points1 is not None, offsets is not None)
@@ -840,15 +624,10 @@ class _InterpLinear(torch.autograd.Function):
         b, n, m, c2, c1, cout, cin, has_skip, has_inverse = ctx.dims
         points2, idx, weight3, wp, *rest = ctx.saved_tensors
         points1 = rest.pop(0) if has_skip else None
-        rows = b * n
         dz = dz.contiguous()
         dw = None
         if ctx.needs_input_grad[6]:
-            nbytes = L.hf_linear_wgrad_workspace(rows, cout, cin)
-            ws = torch.empty((nbytes // 4,), dtype=torch.float32, device=dz.device)
-            dwp = torch.empty((cout, cin), dtype=torch.float32, device=dz.device)
-            check(L.hf_linear_wgrad_interp(rows, cout, c2, c1, ptr(dz), ptr(points2), m, n, ptr(idx), ptr(weight3), ptr(points1), ptr(dwp),
-                                           ptr(ws), nbytes, stream_ptr()), "linear_wgrad_interp")
+            dwp = _k.linear_wgrad_interp(dz, points2, points1, idx, weight3, c1, cin)
             dw = dwp[:, :c2 + c1].contiguous() if cin != c2 + c1 else dwp
         need2, need1 = ctx.needs_input_grad[0], has_skip and ctx.needs_input_grad[1]
         dp2 = dp1 = None
@@ -913,20 +692,34 @@ def shared_mlp_interp(layers, points2, points1, idx, weight, inverse):
     points1 = points1.contiguous() if points1 is not None else None
     idx = idx.contiguous()
     weight = weight.detach().contiguous()
-    offsets, entries = (t.contiguous() for t in inverse) if inverse is not None else (None, None)
+    inverse = [t.contiguous() for t in inverse] if inverse is not None else [None, None]
     first = layers[0]
+    return _first_layer_then_chain("shared_mlp_interp", layers, 0, lambda update_running: _InterpLinear.apply(
+        points2, points1, idx, weight, *(inverse if update_running else (None, None)), first.fc.weight, first.fc.bias, first.bn,
+        update_running))       # inference runs without the inverse index
+
+
+def _chain_params(layers, extra=0):
+    """[w, b, gamma, beta] of every layer, flattened (the tensor arguments of _SharedMLPChain); extra: zero columns appended to the
+    first weight, for an input the producer padded"""
+    params = []
+    for i, l in enumerate(layers):
+        w = l.fc.weight if (i or not extra) else torch.nn.functional.pad(l.fc.weight, (0, extra))
+        params += [w, l.fc.bias, l.bn.weight, l.bn.bias]
+    return params
+
+
+def _first_layer_then_chain(name, layers, pool_k, first_layer):
+    """the shared tail of shared_mlp_grouped and shared_mlp_interp: first_layer(update_running) runs the node that reads its operand in
+    place and returns (z0, mean0, invstd0); the rest is shared_mlp's chain, started at the first layer's BatchNorm"""
     if all(l.bn.training for l in layers) and torch.is_grad_enabled():
-        z0, mean0, invstd0 = _InterpLinear.apply(points2, points1, idx, weight, offsets, entries, first.fc.weight, first.fc.bias,
-                                                 first.bn, True)
-        params = []
-        for l in layers:
-            params += [l.fc.weight, l.fc.bias, l.bn.weight, l.bn.bias]
-        return _SharedMLPChain.apply(z0, 0, layers, (mean0, invstd0), *params)
-    assert not any(l.bn.training for l in layers), "shared_mlp_interp: training-mode BatchNorm needs autograd enabled (or call .eval())"
+        z0, mean0, invstd0 = first_layer(True)
+        return _SharedMLPChain.apply(z0, pool_k, layers, (mean0, invstd0), *_chain_params(layers))
+    assert not any(l.bn.training for l in layers), "%s: training-mode BatchNorm needs autograd enabled (or call .eval())" % name
     # inference: running statistics; the first layer still reads in place (its batch statistics are simply not used)
     with torch.no_grad():
-        z0, _, _ = _InterpLinear.apply(points2, points1, idx, weight, None, None, first.fc.weight, first.fc.bias, first.bn, False)
-        return _shared_mlp_eval(layers, z0, 0, 0, first_done=True)
+        z0, _, _ = first_layer(False)
+    return _shared_mlp_eval(layers, z0, pool_k, 0, first_done=True)
 
 
 def shared_mlp(layers, x, pool_k=0):
@@ -942,11 +735,7 @@ def shared_mlp(layers, x, pool_k=0):
     extra = x.shape[1] - layers[0].fc.in_features  # zero columns appended by the producer (grouping.group_concat)
     assert extra >= 0
     if fused:
-        params = []
-        for i, l in enumerate(layers):
-            w = l.fc.weight if (i or not extra) else torch.nn.functional.pad(l.fc.weight, (0, extra))
-            params += [w, l.fc.bias, l.bn.weight, l.bn.bias]
-        return _SharedMLPChain.apply(x, pool_k, layers, None, *params)
+        return _SharedMLPChain.apply(x, pool_k, layers, None, *_chain_params(layers, extra))
     if bn_relu and pool_ok and not torch.is_grad_enabled() and not any(l.bn.training for l in layers):
         return _shared_mlp_eval(layers, x, pool_k, extra)
     if extra:
@@ -969,17 +758,8 @@ class _LinearBNReLU(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, gamma, beta, running_mean, running_var, eps, momentum, relu):
-        running_stats_written()          # the kernel below writes the running statistics through raw pointers
-        rows, cout = x.shape[0], weight.shape[0]
         z = torch.addmm(bias, x, weight.t())
-        y = torch.empty_like(z)
-        mean = torch.empty((cout,), dtype=torch.float32, device=x.device)
-        invstd = torch.empty((cout,), dtype=torch.float32, device=x.device)
-        ws, nbytes = _workspace(rows, cout, x.device)
-        check(_lib.lib().hf_bn_relu_fwd_train(rows, cout, ptr(z), ptr(gamma), ptr(beta), eps, momentum,
-                                              ptr(running_mean), ptr(running_var), 1 if relu else 0, ptr(y),
-                                              ptr(mean), ptr(invstd), ptr(ws), nbytes, stream_ptr()),
-              "bn_relu_fwd_train")
+        y, mean, invstd = _k.bn_fwd_train(z, gamma, beta, Running(running_mean, running_var, eps, momentum), 1 if relu else 0)
         ctx.save_for_backward(x, weight, z, gamma, beta, mean, invstd)
         ctx.relu = relu
         return y
@@ -987,16 +767,7 @@ class _LinearBNReLU(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x, weight, z, gamma, beta, mean, invstd = ctx.saved_tensors
-        rows, cout = z.shape
-        dy = dy.contiguous()
-        dz = torch.empty_like(z)
-        dgamma = torch.empty_like(gamma)
-        dbeta = torch.empty_like(beta)
-        dbias = torch.empty_like(beta)
-        ws, nbytes = _workspace(rows, cout, z.device)
-        check(_lib.lib().hf_bn_relu_bwd(rows, cout, ptr(z), ptr(dy), ptr(gamma), ptr(beta), ptr(mean), ptr(invstd),
-                                        1 if ctx.relu else 0, ptr(dz), ptr(dgamma), ptr(dbeta), ptr(dbias), ptr(ws),
-                                        nbytes, stream_ptr()), "bn_relu_bwd")
+        dz, dgamma, dbeta, dbias = _k.bn_bwd(z, dy.contiguous(), gamma, beta, mean, invstd, 1 if ctx.relu else 0, colsum=True)
         dx = dz @ weight if ctx.needs_input_grad[0] else None
         dw = _splitk_wgrad(dz, x)
         return dx, dw, dbias, dgamma, dbeta, None, None, None, None, None
@@ -1032,6 +803,11 @@ class BatchNormReLU(nn.Module):
         base = (torch.initial_seed() * 0x9E3779B97F4A7C15 + _DROP_LAYERS[0] * 0xBF58476D1CE4E5B9) % (1 << 62)
         self.register_buffer("drop_state", torch.tensor([base, 0], dtype=torch.int64), persistent=False)
 
+    @property
+    def mode(self):
+        """the mode bits of every BatchNorm kernel: (1: ReLU after the normalisation) | (2: ELU before it)"""
+        return (1 if self.relu else 0) | (2 if self.elu_in else 0)
+
     def train(self, mode=True):
         self._eval_invstd = None
         return super().train(mode)
@@ -1059,16 +835,10 @@ class BatchNormReLU(nn.Module):
         x = x.contiguous()
         if self.training and dropout > 0.0:
             return _BNDropoutTrain.apply(x, self.weight, self.bias, self.running_mean, self.running_var, self.eps, self.momentum,
-                                         (1 if self.relu else 0) | (2 if self.elu_in else 0), dropout, self.drop_state, _dropout_salt())
+                                         self.mode, dropout, self.drop_state, _dropout_salt())
         if self.training:
-            return _BNReLUTrain.apply(x, self.weight, self.bias, self.running_mean, self.running_var, self.eps,
-                                      self.momentum, (1 if self.relu else 0) | (2 if self.elu_in else 0))
-        y = torch.empty_like(x)
-        invstd = self.eval_invstd()
-        check(_lib.lib().hf_bn_relu_fwd_eval(x.shape[0], x.shape[1], ptr(x), ptr(self.weight), ptr(self.bias),
-                                             ptr(self.running_mean), ptr(invstd),
-                                             (1 if self.relu else 0) | (2 if self.elu_in else 0), ptr(y),
-                                             stream_ptr()), "bn_relu_fwd_eval")
+            return _BNReLUTrain.apply(x, self.weight, self.bias, self.running_mean, self.running_var, self.eps, self.momentum, self.mode)
+        y = _k.bn_apply(x, self.weight, self.bias, self.running_mean, self.eval_invstd(), self.mode)
         return torch.nn.functional.dropout(y, p=dropout, training=True) if dropout > 0.0 else y
 
 
@@ -1079,19 +849,8 @@ class _LinearBNReLUMaxPool(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, gamma, beta, running_mean, running_var, eps, momentum, k):
-        running_stats_written()          # the kernel below writes the running statistics through raw pointers
-        rows, cout = x.shape[0], weight.shape[0]
-        groups = rows // k
         z = torch.addmm(bias, x, weight.t())
-        pooled = torch.empty((groups, cout), dtype=torch.float32, device=x.device)
-        argmax = torch.empty((groups, cout), dtype=torch.uint8, device=x.device)
-        mean = torch.empty((cout,), dtype=torch.float32, device=x.device)
-        invstd = torch.empty((cout,), dtype=torch.float32, device=x.device)
-        ws, nbytes = _workspace(rows, cout, x.device)
-        check(_lib.lib().hf_bn_relu_maxpool_fwd(groups, k, cout, ptr(z), ptr(gamma), ptr(beta), 1, eps, momentum,
-                                                ptr(running_mean), ptr(running_var), ptr(mean), ptr(invstd),
-                                                ptr(pooled), ptr(argmax), ptr(ws), nbytes, stream_ptr()),
-              "bn_relu_maxpool_fwd")
+        pooled, argmax, mean, invstd = _k.bn_maxpool_fwd(z, k, gamma, beta, bn=Running(running_mean, running_var, eps, momentum))
         ctx.save_for_backward(x, weight, z, gamma, beta, mean, invstd, argmax)
         ctx.k = k
         return pooled
@@ -1099,17 +858,7 @@ class _LinearBNReLUMaxPool(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dpooled):
         x, weight, z, gamma, beta, mean, invstd, argmax = ctx.saved_tensors
-        rows, cout = z.shape
-        groups = rows // ctx.k
-        dpooled = dpooled.contiguous()
-        dz = torch.empty_like(z)
-        dgamma = torch.empty_like(gamma)
-        dbeta = torch.empty_like(beta)
-        dbias = torch.empty_like(beta)
-        ws, nbytes = _workspace(rows, cout, z.device)
-        check(_lib.lib().hf_bn_relu_maxpool_bwd(groups, ctx.k, cout, ptr(z), ptr(dpooled), ptr(argmax), ptr(gamma),
-                                                ptr(beta), ptr(mean), ptr(invstd), ptr(dz), ptr(dgamma), ptr(dbeta),
-                                                ptr(dbias), ptr(ws), nbytes, stream_ptr()), "bn_relu_maxpool_bwd")
+        dz, dgamma, dbeta, dbias = _k.bn_maxpool_bwd(z, dpooled.contiguous(), argmax, ctx.k, gamma, beta, mean, invstd, colsum=True)
         dx = dz @ weight if ctx.needs_input_grad[0] else None
         dw = _splitk_wgrad(dz, x)
         return dx, dw, dbias, dgamma, dbeta, None, None, None, None, None
@@ -1124,10 +873,4 @@ def linear_bn_relu_maxpool(x, weight, bias, bn, k):
         return _LinearBNReLUMaxPool.apply(x, weight, bias, bn.weight, bn.bias, bn.running_mean, bn.running_var,
                                           bn.eps, bn.momentum, k)
     z = torch.addmm(bias, x, weight.t())
-    groups, cout = x.shape[0] // k, weight.shape[0]
-    pooled = torch.empty((groups, cout), dtype=torch.float32, device=x.device)
-    invstd = bn.eval_invstd()
-    check(_lib.lib().hf_bn_relu_maxpool_fwd(groups, k, cout, ptr(z), ptr(bn.weight), ptr(bn.bias), 0, bn.eps, bn.momentum,
-                                            None, None, ptr(bn.running_mean), ptr(invstd), ptr(pooled), None, None, 0,
-                                            stream_ptr()), "bn_relu_maxpool_fwd")
-    return pooled
+    return _k.bn_maxpool_fwd(z, k, bn.weight, bn.bias, bn.running_mean, bn.eval_invstd(), want_argmax=False)[0]

@@ -33,7 +33,8 @@ from . import _lib
 from ._lib import check, ptr, require, stream_ptr
 from .grouping import INVERSE_MAX_TARGETS, concat_group, group_point, index_inverse, knn_point
 from .sampling import farthest_point_sample, gather_point
-from .mlp import BatchNormReLU, bf16_route, linear_bf16_eval, linear_nobias, running_stats_written
+from . import _dense_kernels as _k
+from .mlp import BatchNormReLU, bf16_route, linear_bf16_eval, linear_nobias
 
 
 class EluBN(nn.Module):
@@ -53,7 +54,7 @@ class EluBN(nn.Module):
 
 def _linear_elu_bn_bf16(x, weight, post):
     """linear -> `post` (an EluBN in eval mode) as one launch of the bf16 inference kernel; the caller has asked mlp.bf16_route"""
-    y = linear_bf16_eval(x.reshape(-1, x.shape[-1]), weight, None, post.bn, _bn_mode(post.bn))
+    y = linear_bf16_eval(x.reshape(-1, x.shape[-1]), weight, None, post.bn, post.bn.mode)
     return y.reshape(*x.shape[:-1], weight.shape[0])
 
 
@@ -85,55 +86,20 @@ class _DenseChainElu(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w0, g0, b0, w1, g1, b1, bn0, bn1):
-        L = _lib.lib()
-        rows = x.shape[0]
-        c0, c1 = w0.shape[0], w1.shape[0]
-        dev = x.device
-
-        def layer(inp, w, bn, in_bn, want_act):
-            running_stats_written()
-            cout, cin = w.shape
-            nbytes = L.hf_linear_bn_fwd_workspace(cout)
-            ws = torch.empty((nbytes // 4,), dtype=torch.float32, device=dev)
-            z = torch.empty((rows, cout), dtype=torch.float32, device=dev)
-            mean, invstd = torch.empty((cout,), dtype=torch.float32, device=dev), torch.empty((cout,), dtype=torch.float32, device=dev)
-            act = torch.empty_like(inp) if want_act else None
-            g, b, m, i = in_bn if in_bn is not None else (None, None, None, None)
-            check(L.hf_linear_elu_bn_fwd(rows, cin, cout, ptr(inp), ptr(g), ptr(b), ptr(m), ptr(i), ptr(act), ptr(w), ptr(z), bn.eps,
-                                         bn.momentum, ptr(bn.running_mean), ptr(bn.running_var), ptr(mean), ptr(invstd), ptr(ws), nbytes,
-                                         stream_ptr()), "linear_elu_bn_fwd")
-            return z, mean, invstd, act
-
         w0, w1 = w0.contiguous(), w1.contiguous()
-        z0, m0, i0, _ = layer(x, w0, bn0, None, False)
-        z1, m1, i1, y0 = layer(z0, w1, bn1, (g0, b0, m0, i0), True)
-        out = torch.empty_like(z1)
-        check(L.hf_bn_relu_fwd_eval(rows, c1, ptr(z1), ptr(g1), ptr(b1), ptr(m1), ptr(i1), 2, ptr(out), stream_ptr()), "bn_elu_apply")
+        z0, m0, i0, _ = _k.linear_elu_bn_fwd(x, w0, bn0)
+        z1, m1, i1, y0 = _k.linear_elu_bn_fwd(z0, w1, bn1, (g0, b0, m0, i0), keep_act=True)
+        out = _k.bn_apply(z1, g1, b1, m1, i1, 2)
         ctx.save_for_backward(x, z0, m0, i0, y0, z1, m1, i1, w0, g0, b0, w1, g1, b1)
         return out
 
     @staticmethod
     def backward(ctx, dout):
         from .mlp import _splitk_wgrad
-        L = _lib.lib()
         x, z0, m0, i0, y0, z1, m1, i1, w0, g0, b0, w1, g1, b1 = ctx.saved_tensors
-        rows, c0, c1 = x.shape[0], w0.shape[0], w1.shape[0]
-        dout = dout.contiguous()
-        dz1 = torch.empty_like(z1)
-        dg1, db1 = torch.empty_like(g1), torch.empty_like(b1)
-        ws, nbytes = _bn_ws(rows, c1, x.device)
-        check(L.hf_bn_relu_bwd(rows, c1, ptr(z1), ptr(dout), ptr(g1), ptr(b1), ptr(m1), ptr(i1), 2, ptr(dz1), ptr(dg1), ptr(db1), None,
-                               ptr(ws), nbytes, stream_ptr()), "bn_elu_bwd")
-        dy0 = torch.empty_like(z0)
-        dg0, db0 = torch.empty_like(g0), torch.empty_like(b0)
-        nbytes = L.hf_linear_bn_bwd_workspace(c0)
-        ws = torch.empty((nbytes // 4,), dtype=torch.float32, device=x.device)
-        w1t = w1.t().contiguous()
-        check(L.hf_linear_elu_bn_bwd(rows, c1, c0, ptr(dz1), ptr(w1t), ptr(dy0), ptr(z0), ptr(g0), ptr(b0), ptr(m0), ptr(i0), ptr(dg0),
-                                     ptr(db0), ptr(ws), nbytes, stream_ptr()), "linear_elu_bn_bwd")
-        dz0 = torch.empty_like(z0)
-        check(L.hf_bn_relu_bwd_dx(rows, c0, ptr(z0), ptr(dy0), ptr(g0), ptr(b0), ptr(m0), ptr(i0), ptr(dg0), ptr(db0), 2, ptr(dz0),
-                                  stream_ptr()), "bn_elu_bwd_dx")
+        dz1, dg1, db1, _ = _k.bn_bwd(z1, dout.contiguous(), g1, b1, m1, i1, 2)
+        dy0, dg0, db0 = _k.linear_elu_bn_bwd(dz1, w1.t().contiguous(), z0, g0, b0, m0, i0)
+        dz0 = _k.bn_bwd_dx(z0, dy0, g0, b0, m0, i0, dg0, db0, 2)
         dx = dz0 @ w0 if ctx.needs_input_grad[0] else None
         return dx, _splitk_wgrad(dz0, x), dg0, db0, _splitk_wgrad(dz1, y0), dg1, db1, None, None
 
@@ -146,62 +112,29 @@ class _LiftChain(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w0, g0, b0, w1, g1, b1, bn0, bn1):
-        running_stats_written()
-        L = _lib.lib()
-        rows, c0, c1, dev = x.shape[0], w0.shape[0], w1.shape[0], x.device
         w0, w1 = w0.contiguous(), w1.contiguous()
-        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
-        m0, i0, m1, i1, z1 = new(c0), new(c0), new(c1), new(c1), new(rows, c1)
-        nbytes = L.hf_lift_elu_bn_fwd_workspace(c0, c1)
-        ws = new(nbytes // 4)
-        check(L.hf_lift_elu_bn_fwd(rows, c0, c1, ptr(x), ptr(w0), ptr(g0), ptr(b0), bn0.eps, bn0.momentum, ptr(bn0.running_mean),
-                                   ptr(bn0.running_var), ptr(m0), ptr(i0), ptr(w1), ptr(z1), bn1.eps, bn1.momentum,
-                                   ptr(bn1.running_mean), ptr(bn1.running_var), ptr(m1), ptr(i1), ptr(ws), nbytes, stream_ptr()),
-              "lift_elu_bn_fwd")
-        out = torch.empty_like(z1)
-        check(L.hf_bn_relu_fwd_eval(rows, c1, ptr(z1), ptr(g1), ptr(b1), ptr(m1), ptr(i1), 2, ptr(out), stream_ptr()), "bn_elu_apply")
+        m0, i0, z1, m1, i1 = _k.lift_elu_bn_fwd(x, w0, g0, b0, bn0, w1, bn1)
+        out = _k.bn_apply(z1, g1, b1, m1, i1, 2)
         ctx.save_for_backward(x, m0, i0, z1, m1, i1, w0, g0, b0, w1, g1, b1)
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        L = _lib.lib()
         x, m0, i0, z1, m1, i1, w0, g0, b0, w1, g1, b1 = ctx.saved_tensors
-        rows, c0, c1, dev = x.shape[0], w0.shape[0], w1.shape[0], x.device
-        dout = dout.contiguous()
-        dz1 = torch.empty_like(z1)
-        dg1, db1 = torch.empty_like(g1), torch.empty_like(b1)
-        ws, nbytes = _bn_ws(rows, c1, dev)
-        check(L.hf_bn_relu_bwd(rows, c1, ptr(z1), ptr(dout), ptr(g1), ptr(b1), ptr(m1), ptr(i1), 2, ptr(dz1), ptr(dg1), ptr(db1), None,
-                               ptr(ws), nbytes, stream_ptr()), "bn_elu_bwd")
-        dw0_t = torch.empty((3, c0), dtype=torch.float32, device=dev)
-        dw1 = torch.empty_like(w1)
-        dg0, db0 = torch.empty_like(g0), torch.empty_like(b0)
-        nbytes = L.hf_lift_elu_bn_bwd_workspace(rows, c0, c1)
-        ws = torch.empty((nbytes // 4,), dtype=torch.float32, device=dev)
-        w1t = w1.t().contiguous()
-        check(L.hf_lift_elu_bn_bwd(rows, c0, c1, ptr(x), ptr(w0), ptr(g0), ptr(b0), ptr(m0), ptr(i0), ptr(dz1), ptr(w1t), ptr(dw0_t),
-                                   ptr(dw1), ptr(dg0), ptr(db0), ptr(ws), nbytes, stream_ptr()), "lift_elu_bn_bwd")
+        dz1, dg1, db1, _ = _k.bn_bwd(z1, dout.contiguous(), g1, b1, m1, i1, 2)
+        dw0_t, dw1, dg0, db0 = _k.lift_elu_bn_bwd(x, w0, g0, b0, m0, i0, dz1, w1.t().contiguous())
         return None, dw0_t.t(), dg0, db0, dw1, dg1, db1, None, None
 
 
 def _lift_chain_eval(d0, d1, x):
     """inference twin of _LiftChain on the 3-channel input: the first layer's output is rebuilt from x inside the second GEMM with
     its RUNNING statistics, the second layer's running statistics are applied by one pass; nothing else is written"""
-    L = _lib.lib()
-    rows = x.numel() // 3
     bn0, bn1 = d0.post.bn, d1.post.bn
-    c0, c1 = d0.linear.out_features, d1.linear.out_features
-    x2 = x.reshape(rows, 3).contiguous()
-    z1 = torch.empty((rows, c1), dtype=torch.float32, device=x.device)
-    nbytes = L.hf_lift_elu_bn_fwd_workspace(c0, c1)
-    ws = torch.empty((nbytes // 4,), dtype=torch.float32, device=x.device)
-    w0, w1 = d0.linear.weight.contiguous(), d1.linear.weight.contiguous()
+    x2, w0, w1 = x.reshape(-1, 3).contiguous(), d0.linear.weight.contiguous(), d1.linear.weight.contiguous()
     # the second layer's a (elu(z1) - running_mean) + beta leaves the GEMM's epilogue: no normalisation pass
-    check(L.hf_lift_elu_fwd_eval_bn(rows, c0, c1, ptr(x2), ptr(w0), ptr(bn0.weight), ptr(bn0.bias), ptr(bn0.running_mean),
-                                    ptr(bn0.eval_invstd()), ptr(w1), ptr(bn1.weight), ptr(bn1.bias), ptr(bn1.running_mean),
-                                    ptr(bn1.eval_invstd()), ptr(z1), ptr(ws), nbytes, stream_ptr()), "lift_elu_fwd_eval_bn")
-    return z1.reshape(*x.shape[:-1], c1)
+    out = _k.lift_elu_fwd_eval_bn(x2, w0, (bn0.weight, bn0.bias, bn0.running_mean, bn0.eval_invstd()), w1,
+                                  (bn1.weight, bn1.bias, bn1.running_mean, bn1.eval_invstd()))
+    return out.reshape(*x.shape[:-1], out.shape[1])
 
 
 def dense_chain(d0, d1, x):
@@ -226,15 +159,6 @@ def dense_chain(d0, d1, x):
     return d1(d0(x))
 
 
-def _bn_mode(bn):
-    return (1 if bn.relu else 0) | (2 if bn.elu_in else 0)
-
-
-def _bn_ws(rows, c, device):
-    nbytes = _lib.lib().hf_bn_workspace(rows, c)
-    return torch.empty((nbytes // 4,), dtype=torch.float32, device=device), nbytes
-
-
 class _BNConcatGroup(torch.autograd.Function):
     """[bn(elu(z)) | points[idx]] for z (B*M*K, Ch), points (B,N,C), idx (B,M,K) -> (B,M,K,Ch+C): the BatchNorm of the lifting
     layer writes its output straight into the concat buffer of pointcnn.py:104 (row stride Ch+C) and the gather fills the
@@ -242,18 +166,12 @@ class _BNConcatGroup(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, z, gamma, beta, running_mean, running_var, eps, momentum, mode, points, idx, offsets, entries):
-        running_stats_written()          # the kernel below writes the running statistics through raw pointers
         L = _lib.lib()
         b, n, c = points.shape
         _, m, ns = idx.shape
-        rows, ch = z.shape
-        width = ch + c
+        ch, width = z.shape[1], z.shape[1] + c
         out = torch.empty((b, m, ns, width), dtype=torch.float32, device=z.device)
-        mean = torch.empty((ch,), dtype=torch.float32, device=z.device)
-        invstd = torch.empty((ch,), dtype=torch.float32, device=z.device)
-        ws, nbytes = _bn_ws(rows, ch, z.device)
-        check(L.hf_bn_relu_fwd_train_ld(rows, ch, ptr(z), ptr(gamma), ptr(beta), eps, momentum, ptr(running_mean), ptr(running_var),
-                                        mode, ptr(out), width, ptr(mean), ptr(invstd), ptr(ws), nbytes, stream_ptr()), "bn_relu_fwd_train_ld")
+        _, mean, invstd = _k.bn_fwd_train(z, gamma, beta, _k.Running(running_mean, running_var, eps, momentum), mode, out=out, ld=width)
         check(L.hf_group_point_into(b, n, c, m, ns, width, ch, ptr(points), ptr(idx), ptr(out), stream_ptr()), "group_point_into")
         ctx.save_for_backward(z, gamma, beta, mean, invstd, idx, *([offsets, entries] if offsets is not None else []))
         ctx.meta = (b, n, c, m, ns, ch, mode)
@@ -264,13 +182,9 @@ class _BNConcatGroup(torch.autograd.Function):
         L = _lib.lib()
         z, gamma, beta, mean, invstd, idx = ctx.saved_tensors[:6]
         b, n, c, m, ns, ch, mode = ctx.meta
-        rows, width = z.shape[0], ch + c
+        width = ch + c
         go = go.contiguous()
-        dz = torch.empty_like(z)
-        dgamma, dbeta = torch.empty_like(gamma), torch.empty_like(beta)
-        ws, nbytes = _bn_ws(rows, ch, z.device)
-        check(L.hf_bn_relu_bwd_ld(rows, ch, ptr(z), ptr(go), width, ptr(gamma), ptr(beta), ptr(mean), ptr(invstd), mode, ptr(dz),
-                                  ptr(dgamma), ptr(dbeta), None, ptr(ws), nbytes, stream_ptr()), "bn_relu_bwd_ld")
+        dz, dgamma, dbeta, _ = _k.bn_bwd(z, go, gamma, beta, mean, invstd, mode, ld=width)
         g = None
         if ctx.needs_input_grad[8]:
             g = torch.empty((b, n, c), dtype=torch.float32, device=z.device)
@@ -290,16 +204,10 @@ class _BNConcatSkip(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, z, gamma, beta, running_mean, running_var, eps, momentum, mode, skip):
-        running_stats_written()          # the kernel below writes the running statistics through raw pointers
-        L = _lib.lib()
         rows, c = z.shape
         cs = skip.shape[1]
         out = torch.empty((rows, c + cs), dtype=torch.float32, device=z.device)
-        mean = torch.empty((c,), dtype=torch.float32, device=z.device)
-        invstd = torch.empty((c,), dtype=torch.float32, device=z.device)
-        ws, nbytes = _bn_ws(rows, c, z.device)
-        check(L.hf_bn_relu_fwd_train_ld(rows, c, ptr(z), ptr(gamma), ptr(beta), eps, momentum, ptr(running_mean), ptr(running_var),
-                                        mode, ptr(out), c + cs, ptr(mean), ptr(invstd), ptr(ws), nbytes, stream_ptr()), "bn_relu_fwd_train_ld")
+        _, mean, invstd = _k.bn_fwd_train(z, gamma, beta, _k.Running(running_mean, running_var, eps, momentum), mode, out=out, ld=c + cs)
         out[:, c:].copy_(skip)
         ctx.save_for_backward(z, gamma, beta, mean, invstd)
         ctx.meta = (c, cs, mode)
@@ -307,16 +215,10 @@ class _BNConcatSkip(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, go):
-        L = _lib.lib()
         z, gamma, beta, mean, invstd = ctx.saved_tensors
         c, cs, mode = ctx.meta
-        rows = z.shape[0]
         go = go.contiguous()
-        dz = torch.empty_like(z)
-        dgamma, dbeta = torch.empty_like(gamma), torch.empty_like(beta)
-        ws, nbytes = _bn_ws(rows, c, z.device)
-        check(L.hf_bn_relu_bwd_ld(rows, c, ptr(z), ptr(go), c + cs, ptr(gamma), ptr(beta), ptr(mean), ptr(invstd), mode, ptr(dz),
-                                  ptr(dgamma), ptr(dbeta), None, ptr(ws), nbytes, stream_ptr()), "bn_relu_bwd_ld")
+        dz, dgamma, dbeta, _ = _k.bn_bwd(z, go, gamma, beta, mean, invstd, mode, ld=c + cs)
         return dz, dgamma, dbeta, None, None, None, None, None, (go[:, c:] if ctx.needs_input_grad[8] else None)
 
 
@@ -648,7 +550,7 @@ class XConv(nn.Module):
             # F_* <- [F_delta, F]: the second lifting layer's BatchNorm writes into the concat, the gather fills the rest
             off, ent = inverse if inverse is not None else (None, None)
             f = _BNConcatGroup.apply(f.reshape(-1, f.shape[-1]), bn1.weight, bn1.bias, bn1.running_mean, bn1.running_var, bn1.eps,
-                                     bn1.momentum, _bn_mode(bn1), fts.contiguous(), idx, off, ent)
+                                     bn1.momentum, bn1.mode, fts.contiguous(), idx, off, ent)
         elif not gather and fts is not None:
             f = concat_group(f, fts, idx, inverse)             # F_* <- [F_delta, F]: gathered straight into the concat
         if self.with_x:
@@ -670,7 +572,7 @@ class XConv(nn.Module):
             zc = linear_nobias(fx, self.conv.pointwise.weight, allow_bf16=bnc.training)
             if skip is not None and not self.with_global and _fusable(bnc, zc, zc.shape[-1], zc.shape[-1] + skip.shape[-1]):
                 out = _BNConcatSkip.apply(zc.reshape(-1, zc.shape[-1]), bnc.weight, bnc.bias, bnc.running_mean, bnc.running_var, bnc.eps,
-                                          bnc.momentum, _bn_mode(bnc), skip.reshape(-1, skip.shape[-1]).contiguous())
+                                          bnc.momentum, bnc.mode, skip.reshape(-1, skip.shape[-1]).contiguous())
                 return out.reshape(b, p, -1)
             out = self.conv.post(zc)
         else:
