@@ -148,6 +148,19 @@ def resume_state(checkpoint_dir, config, settings):
     return ck, path
 
 
+def add_run_arguments(ap, saved):
+    """DATASET_DIR and the flags of a run that train_rpn and train_rcnn share (`saved`: what --save holds, "model" / "trainer")"""
+    ap.add_argument("dataset_dir")
+    ap.add_argument("--split", default="train", help="a list file, or NAME for NAME.txt next to or inside DATASET_DIR")
+    ap.add_argument("--steps", type=int, default=100)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--save", default=None, help="path of the saved %s state_dict (torch.save)" % saved)
+    ap.add_argument("--log-every", type=int, default=10)
+    ap.add_argument("--workers", type=int, default=8, help="host threads that read and decode the files")
+    ap.add_argument("--lr", type=float, default=1e-3)
+    ap.add_argument("--no-graph", action="store_true", help="eager steps instead of the captured hipGraph")
+
+
 def add_train_op_arguments(ap, config_file):
     """--reference-train-op and the checkpoint flags (train_rpn and train_rcnn)"""
     ap.add_argument("--reference-train-op", action="store_true",

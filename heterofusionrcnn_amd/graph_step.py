@@ -334,8 +334,12 @@ class TrainStep:
         return self.loss
 
 
-def _rpn_loss(model, inputs, geometry, taps=None):
+def rpn_loss_parts(model, inputs, geometry, taps=None):
+    """RpnModel forward + RpnModel.loss -> (loss, parts): what train_loop.run logs from; _rpn_loss is its loss-only form"""
     seg_logits, head = model(inputs["xyz"], inputs["intensity"], geometry=geometry, img_fts=inputs.get("img_fts"),
                              calib=inputs.get("calib"), **({"taps": taps} if taps is not None else {}))
-    loss, _ = model.loss(inputs["xyz"], seg_logits, head, inputs["label_cls"], inputs["label_reg"])
-    return loss
+    return model.loss(inputs["xyz"], seg_logits, head, inputs["label_cls"], inputs["label_reg"])
+
+
+def _rpn_loss(model, inputs, geometry, taps=None):
+    return rpn_loss_parts(model, inputs, geometry, taps)[0]

@@ -243,12 +243,16 @@ class RcnnTrainer(nn.Module):
         return loss, parts
 
 
-def rcnn_train_loss(model, inputs, geometry):
-    """loss_fn of graph_step.TrainStep for an RcnnTrainer: inputs xyz, rpn_fts, intensity, fg_mask, proposals, proposal_count, gt,
+def rcnn_train_loss_parts(model, inputs, geometry):
+    """an RcnnTrainer's (loss, parts) from a step's inputs: xyz, rpn_fts, intensity, fg_mask, proposals, proposal_count, gt,
     gt_count, img_fts, calib (geometry is unused: the RoI crops are recomputed every step)"""
-    loss, _ = model(inputs["xyz"], inputs["rpn_fts"], inputs["intensity"], inputs["fg_mask"], inputs["proposals"],
-                    inputs["proposal_count"], inputs["gt"], inputs["gt_count"], inputs["img_fts"], inputs["calib"])
-    return loss
+    return model(inputs["xyz"], inputs["rpn_fts"], inputs["intensity"], inputs["fg_mask"], inputs["proposals"],
+                 inputs["proposal_count"], inputs["gt"], inputs["gt_count"], inputs["img_fts"], inputs["calib"])
+
+
+def rcnn_train_loss(model, inputs, geometry):
+    """loss_fn of graph_step.TrainStep for an RcnnTrainer: rcnn_train_loss_parts without the parts"""
+    return rcnn_train_loss_parts(model, inputs, geometry)[0]
 
 
 # ------------------------------------------------------------------------------------------------ with the image branch

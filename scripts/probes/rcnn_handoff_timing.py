@@ -77,6 +77,7 @@ def loader_and_step(root):
     from heterofusionrcnn_amd import train_rcnn
     from heterofusionrcnn_amd.graph_step import TrainStep
     from heterofusionrcnn_amd.optim import MultiTensorAdam
+    from heterofusionrcnn_amd.rcnn_train import rcnn_train_loss
     out = {}
     data = RD.KittiRcnnBatches(root, root, "train", batch=B, seed=0, workers=16)
     try:
@@ -92,9 +93,7 @@ def loader_and_step(root):
         trainer = train_rcnn.make_trainer(C, seed=0)
         cur = data.next()
         opt = MultiTensorAdam([p for p in trainer.parameters() if p.requires_grad], lr=1e-3, tf_epsilon=False)
-        step = TrainStep(trainer, opt, cur.train_inputs(), None, graph=True, loss_fn=lambda m, i, g: m(
-            i["xyz"], i["rpn_fts"], i["intensity"], i["fg_mask"], i["proposals"], i["proposal_count"], i["gt"], i["gt_count"],
-            i["img_fts"], i["calib"])[0])
+        step = TrainStep(trainer, opt, cur.train_inputs(), None, graph=True, loss_fn=rcnn_train_loss)
         for _ in range(3):
             step()
         torch.cuda.synchronize()

@@ -315,3 +315,20 @@ def test_export_and_second_stage_leave_no_worker_thread(dataset, handoff, tmp_pa
     totals = export_rpn.export(dataset, os.path.join(out, "rpn.pt"), str(tmp_path / "handoff"), "train", batch=2, img_conv=IMG_CONV,
                                workers=2, log=None)
     assert sorted(totals) == NAMES and workers() == []
+
+
+def test_a_failed_capture_leaves_no_loader_thread(dataset, handoff, monkeypatch):
+    """train_rcnn.train whose step cannot be built (the loop's TrainStep raises) closes the loader it opened: none of its reader
+    (hf-read-pool...) or read-ahead (hf-read-ahead...) threads survives the call, and the caller gets the exception as raised"""
+    from heterofusionrcnn_amd import train_loop, train_rcnn
+    readers = lambda: [t.name for t in threading.enumerate() if t.name.startswith("hf-read")]
+    refused = RuntimeError("the step cannot be captured")
+
+    def no_step(*args, **kwargs):
+        raise refused
+
+    monkeypatch.setattr(train_loop, "TrainStep", no_step)
+    assert readers() == []
+    with pytest.raises(RuntimeError) as caught:
+        train_rcnn.train(dataset, handoff[0], "train", steps=2, batch=2, seed=1, log_every=0, workers=2, img_conv=IMG_CONV)
+    assert caught.value is refused and readers() == []
