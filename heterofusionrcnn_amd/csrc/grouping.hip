@@ -12,6 +12,7 @@
 #include <algorithm>
 
 #include "hf_common.h"
+#include "row_gather.h"
 
 namespace hf {
 
@@ -110,117 +111,7 @@ __global__ __launch_bounds__(kQbThreads) void qbp_bruteforce_kernel(int n, int m
     }
 }
 
-// ------------------------------------------------------------------------------------------
-// group_point: out[b,j,k,:] = points[b, idx[b,j,k], :]   (tf_grouping_g.cu:40-57)
-// Row copies; VEC floats per lane so that both the gathered source row segment and the
-// destination are contiguous (16-byte accesses when c % 4 == 0).
-// ------------------------------------------------------------------------------------------
-template <int VEC>
-__global__ void group_point_kernel(int n, int c, long long rows_per_batch, long long nrows,
-                                   const float *__restrict__ points, const int *__restrict__ idx,
-                                   float *__restrict__ out)
-{
-    typedef float vec_t __attribute__((ext_vector_type(VEC)));
-    const int cv = c / VEC;  // vectors per row
-    const long long total = nrows * cv;
-    for (long long e = blockIdx.x * static_cast<long long>(blockDim.x) + threadIdx.x; e < total;
-         e += static_cast<long long>(gridDim.x) * blockDim.x) {
-        const long long row = e / cv;
-        const int l = static_cast<int>(e - row * cv);
-        const long long bb = row / rows_per_batch;
-        const int ii = idx[row];
-        const vec_t v = *reinterpret_cast<const vec_t *>(points + (bb * n + ii) * c + l * VEC);
-        *reinterpret_cast<vec_t *>(out + row * c + l * VEC) = v;
-    }
-}
-
-// The same op when c / 4 is a power of two (c = 16 .. 1024): no integer division (lane -> row by a shift, the batch is
-// grid.y), ROWS rows per thread in flight (index loads, then ROWS independent 16-byte gathers before the first store),
-// nontemporal stores for the write-once output so that the feature table stays in the XCD's L2.
-template <int ROWS>
-__global__ __launch_bounds__(256) void group_point_pow2_kernel(int nbatch, int n, int c, int cv_shift, int rows_per_batch,
-                                                               const float *__restrict__ points,
-                                                               const int *__restrict__ idx, float *__restrict__ out)
-{
-    typedef float v4 __attribute__((ext_vector_type(4)));
-    // linear workgroup id = cloud + b * chunk: workgroups are dealt round-robin over the 8 XCDs, so with b a multiple of 8
-    // every workgroup of a cloud runs on ONE XCD and that cloud's table stays in its 4 MB L2 (speed only)
-    const int bb = blockIdx.x % nbatch;
-    const unsigned gxb = gridDim.x / nbatch;
-    const unsigned tid = (blockIdx.x / nbatch) * 256u + threadIdx.x;
-    const int l = static_cast<int>(tid & ((1u << cv_shift) - 1u));
-    const int rstride = static_cast<int>((gxb * 256u) >> cv_shift);
-    const float *base = points + static_cast<size_t>(bb) * n * c + l * 4;
-    const int *ib = idx + static_cast<size_t>(bb) * rows_per_batch;
-    float *ob = out + static_cast<size_t>(bb) * rows_per_batch * c + l * 4;
-    for (int row0 = static_cast<int>(tid >> cv_shift); row0 < rows_per_batch; row0 += rstride * ROWS) {
-        v4 v[ROWS];
-#pragma unroll
-        for (int i = 0; i < ROWS; ++i) {
-            const int row = row0 + i * rstride;
-            v[i] = *reinterpret_cast<const v4 *>(base + static_cast<size_t>(ib[row < rows_per_batch ? row : row0]) * c);
-        }
-#pragma unroll
-        for (int i = 0; i < ROWS; ++i) {
-            const int row = row0 + i * rstride;
-            if (row < rows_per_batch) __builtin_nontemporal_store(v[i], reinterpret_cast<v4 *>(ob + static_cast<size_t>(row) * c));
-        }
-    }
-}
-
-// group_point grad: atomicAdd scatter (tf_grouping_g.cu:61-78); target zeroed by the caller
-__global__ void group_point_grad_kernel(int n, int c, long long rows_per_batch, long long nrows,
-                                        const float *__restrict__ grad_out, const int *__restrict__ idx,
-                                        float *__restrict__ grad_points)
-{
-    const long long total = nrows * c;
-    for (long long e = blockIdx.x * static_cast<long long>(blockDim.x) + threadIdx.x; e < total;
-         e += static_cast<long long>(gridDim.x) * blockDim.x) {
-        const long long row = e / c;
-        const int l = static_cast<int>(e - row * c);
-        const long long bb = row / rows_per_batch;
-        const int ii = idx[row];
-        atomicAdd(grad_points + (bb * n + ii) * c + l, grad_out[e]);
-    }
-}
-
-// group_point gradient in gather form: for every data point the rows of grad_out that name it (CSR inverse of idx, built
-// with the geometry: hf_index_inverse) are summed in ascending (query, slot) order -- the order of the reference's sequential
-// CPU loop (grouping/test/query_ball_point.cpp:53-66) -- and the point's gradient row is written ONCE: no atomics, no zero
-// fill, deterministic.  c / VEC lanes per data point; grad_out rows have stride `width`, the gathered columns start at `col`.
-template <int VEC>
-__global__ void group_point_grad_gather_kernel(int n, int c, int width, int col, int cv, long long rows_per_batch, long long data_rows,
-                                               const float *__restrict__ grad_out, const int *__restrict__ offsets,
-                                               const int *__restrict__ entries, float *__restrict__ grad_points)
-{
-    const int rows_per_block = blockDim.x / cv;
-    const int cvec = threadIdx.x % cv, rsub = threadIdx.x / cv;
-    if (rsub >= rows_per_block) return;
-    for (long long row = blockIdx.x * static_cast<long long>(rows_per_block) + rsub; row < data_rows;
-         row += static_cast<long long>(gridDim.x) * rows_per_block) {
-        const long long bb = row / n;
-        const int k = static_cast<int>(row - bb * n);
-        const int *off = offsets + bb * (n + 1);
-        const int *ent = entries + bb * rows_per_batch;
-        const float *go = grad_out + bb * rows_per_batch * width + col + cvec * VEC;
-        float acc[VEC];
-#pragma unroll
-        for (int i = 0; i < VEC; ++i) acc[i] = 0.0f;
-        const int lo = off[k], hi = off[k + 1];
-        for (int a = lo; a < hi; ++a) {
-            const float *src = go + static_cast<long long>(ent[a]) * width;
-            if constexpr (VEC == 4) {
-                const float4 v = *reinterpret_cast<const float4 *>(src);
-                acc[0] += v.x; acc[1] += v.y; acc[2] += v.z; acc[3] += v.w;
-            } else {
-                acc[0] += src[0];
-            }
-        }
-        float *dst = grad_points + row * c + cvec * VEC;
-        if constexpr (VEC == 4) *reinterpret_cast<float4 *>(dst) = make_float4(acc[0], acc[1], acc[2], acc[3]);
-        else dst[0] = acc[0];
-    }
-}
+// group_point (+ _into, + the three gradients) and the gradient of group_concat are instances of the row-gather family: row_gather.h
 
 // ------------------------------------------------------------------------------------------
 // group_concat: the concat of sample_and_group (pointnet_util.py:58-60) written directly,
@@ -251,21 +142,6 @@ __global__ void group_concat_kernel(int n, int c, int w4, int xyz_col, int feat_
             v[i] = (jf >= 0 && jf < c) ? src[jf] : ((jx >= 0 && jx < 3) ? g[jx] : 0.0f);
         }
         *reinterpret_cast<float4 *>(out + e * 4) = make_float4(v[0], v[1], v[2], v[3]);
-    }
-}
-
-// gradient w.r.t. points: the feature columns 3..3+c of every row scattered back (target zeroed by the caller)
-__global__ void group_concat_grad_kernel(int n, int c, int width, int feat_col, long long rows_per_batch, long long nrows,
-                                         const float *__restrict__ grad_out, const int *__restrict__ idx,
-                                         float *__restrict__ grad_points)
-{
-    const long long total = nrows * c;
-    for (long long e = blockIdx.x * static_cast<long long>(blockDim.x) + threadIdx.x; e < total;
-         e += static_cast<long long>(gridDim.x) * blockDim.x) {
-        const long long row = e / c;
-        const int l = static_cast<int>(e - row * c);
-        const long long bb = row / rows_per_batch;
-        atomicAdd(grad_points + (bb * n + idx[row]) * c + l, grad_out[row * width + feat_col + l]);
     }
 }
 
@@ -448,51 +324,6 @@ __global__ void select_top_k_kernel(int n, long long nrows, int k, const float *
             }
         }
     }
-}
-
-// group_point writing into / its gradient reading from a COLUMN SLICE of wider rows: out[row][col .. col+c) of rows of
-// `width` floats.  PointCNN concatenates the lifted coordinates with the gathered features of the previous layer
-// (pointcnn.py:96-99): gathering straight into the concat buffer saves the copy of the larger part of it, and the gradient
-// of the concat is read in place.
-template <int VEC>
-__global__ void group_point_into_kernel(int n, int c, int width, int col, long long rows_per_batch, long long nrows,
-                                        const float *__restrict__ points, const int *__restrict__ idx, float *__restrict__ out)
-{
-    const int cv = c / VEC;
-    const long long total = nrows * cv;
-    for (long long e = blockIdx.x * static_cast<long long>(blockDim.x) + threadIdx.x; e < total;
-         e += static_cast<long long>(gridDim.x) * blockDim.x) {
-        const long long row = e / cv;
-        const int l = static_cast<int>(e - row * cv) * VEC;
-        const long long bb = row / rows_per_batch;
-        const float *src = points + (bb * n + idx[row]) * c + l;
-        float *dst = out + row * width + col + l;
-        if (VEC == 4) *reinterpret_cast<float4 *>(dst) = *reinterpret_cast<const float4 *>(src);
-        else dst[0] = src[0];
-    }
-}
-
-__global__ void group_point_grad_from_kernel(int n, int c, int width, int col, long long rows_per_batch, long long nrows,
-                                             const float *__restrict__ grad_out, const int *__restrict__ idx,
-                                             float *__restrict__ grad_points)
-{
-    const long long total = nrows * c;
-    for (long long e = blockIdx.x * static_cast<long long>(blockDim.x) + threadIdx.x; e < total;
-         e += static_cast<long long>(gridDim.x) * blockDim.x) {
-        const long long row = e / c;
-        const int l = static_cast<int>(e - row * c);
-        const long long bb = row / rows_per_batch;
-        atomicAdd(grad_points + (bb * n + idx[row]) * c + l, grad_out[row * width + col + l]);
-    }
-}
-
-static int grid_for(long long work_items, int block)
-{
-    long long g = (work_items + block - 1) / block;
-    const long long cap = static_cast<long long>(kNumCU) * 8;
-    if (g > cap) g = cap;
-    if (g < 1) g = 1;
-    return static_cast<int>(g);
 }
 
 static int launch_ball_query_bruteforce(int b, int n, int m, float thresh, int nsample, const float *xyz1,
@@ -886,68 +717,36 @@ HF_API int hf_query_ball_group_xyz_ws(int variant, int b, int n, int m, float ra
                              workspace_bytes, as_stream(stream));
 }
 
+// The row copies below are instances of the row-gather family (row_gather.h): group_point reaches the pow2, 16-byte or scalar
+// forward form, group_point_into the 16-byte or scalar one; the three scatter gradients are one kernel.
 HF_API int hf_group_point(int b, int n, int c, int m, int nsample, const float *points, const int *idx, float *out,
                           hf_stream_t stream)
 {
     if (b < 0 || n <= 0 || c <= 0 || m < 0 || nsample < 0 || !points || !idx || !out) return HF_EINVAL;
-    const long long nrows = static_cast<long long>(b) * m * nsample;
-    if (nrows == 0) return HF_OK;
     const long long rpb = static_cast<long long>(m) * nsample;
-    const int block = 256;
-    hipStream_t st = as_stream(stream);
-    const bool al16 = (reinterpret_cast<uintptr_t>(points) % 16 == 0) && (reinterpret_cast<uintptr_t>(out) % 16 == 0);
-    const int cv = c / 4;
-    if (c % 4 == 0 && al16 && cv >= 4 && cv <= 256 && (cv & (cv - 1)) == 0 && b <= 65535 && rpb * cv < (1LL << 31)) {
-        int cv_shift = 0;
-        while ((1 << cv_shift) < cv) ++cv_shift;
-        long long gx = (rpb * cv + 256 * 4 - 1) / (256 * 4);
-        const long long cap = std::max<long long>(1, (kNumCU * 8) / b);
-        if (gx > cap) gx = cap;
-        hipLaunchKernelGGL((group_point_pow2_kernel<4>), dim3(static_cast<unsigned>(gx * b)), dim3(256), 0, st, b, n, c, cv_shift,
-                           static_cast<int>(rpb), points, idx, out);
-    } else if (c % 4 == 0 && al16)
-        hipLaunchKernelGGL((group_point_kernel<4>), dim3(grid_for(nrows * (c / 4), block)), dim3(block), 0, st, n, c,
-                           rpb, nrows, points, idx, out);
-    else
-        hipLaunchKernelGGL((group_point_kernel<1>), dim3(grid_for(nrows * c, block)), dim3(block), 0, st, n, c, rpb,
-                           nrows, points, idx, out);
-    return launch_status();
+    if (b * rpb == 0) return HF_OK;
+    return launch_gather_rows<1>(true, b, n, c, rpb, c, 0, points, idx, nullptr, out, as_stream(stream));
 }
 
 HF_API int hf_group_point_grad(int b, int n, int c, int m, int nsample, const float *grad_out, const int *idx,
                                float *grad_points, hf_stream_t stream)
 {
     if (b < 0 || n <= 0 || c <= 0 || m < 0 || nsample < 0 || !grad_out || !idx || !grad_points) return HF_EINVAL;
+    const long long rpb = static_cast<long long>(m) * nsample;
     if (b == 0) return HF_OK;
     hipStream_t st = as_stream(stream);
-    int rc = hip_status(hipMemsetAsync(grad_points, 0, sizeof(float) * static_cast<size_t>(b) * n * c, st));
-    if (rc != HF_OK) return rc;
-    const long long nrows = static_cast<long long>(b) * m * nsample;
-    if (nrows == 0) return HF_OK;
-    const int block = 256;
-    hipLaunchKernelGGL(group_point_grad_kernel, dim3(grid_for(nrows * c, block)), dim3(block), 0, st, n, c,
-                       static_cast<long long>(m) * nsample, nrows, grad_out, idx, grad_points);
-    return launch_status();
+    const int rc = hip_status(hipMemsetAsync(grad_points, 0, sizeof(float) * static_cast<size_t>(b) * n * c, st));
+    if (rc != HF_OK || rpb == 0) return rc;
+    return launch_scatter_rows<1>(b, n, c, rpb, c, 0, grad_out, idx, nullptr, grad_points, st);
 }
 
 HF_API int hf_group_point_into(int b, int n, int c, int m, int nsample, int width, int col, const float *points, const int *idx,
                                float *out, hf_stream_t stream)
 {
     if (b < 0 || n <= 0 || c <= 0 || m < 0 || nsample < 0 || col < 0 || width < col + c || !points || !idx || !out) return HF_EINVAL;
-    const long long nrows = static_cast<long long>(b) * m * nsample;
-    if (nrows == 0) return HF_OK;
     const long long rpb = static_cast<long long>(m) * nsample;
-    const int block = 256;
-    hipStream_t st = as_stream(stream);
-    const bool vec = c % 4 == 0 && width % 4 == 0 && col % 4 == 0 && reinterpret_cast<uintptr_t>(points) % 16 == 0 &&
-                     reinterpret_cast<uintptr_t>(out) % 16 == 0;
-    if (vec)
-        hipLaunchKernelGGL((group_point_into_kernel<4>), dim3(grid_for(nrows * (c / 4), block)), dim3(block), 0, st, n, c, width, col,
-                           rpb, nrows, points, idx, out);
-    else
-        hipLaunchKernelGGL((group_point_into_kernel<1>), dim3(grid_for(nrows * c, block)), dim3(block), 0, st, n, c, width, col, rpb,
-                           nrows, points, idx, out);
-    return launch_status();
+    if (b * rpb == 0) return HF_OK;
+    return launch_gather_rows<1>(false, b, n, c, rpb, width, col, points, idx, nullptr, out, as_stream(stream));
 }
 
 HF_API int hf_group_point_grad_from(int b, int n, int c, int m, int nsample, int width, int col, const float *grad_out,
@@ -955,42 +754,22 @@ HF_API int hf_group_point_grad_from(int b, int n, int c, int m, int nsample, int
 {
     if (b < 0 || n <= 0 || c <= 0 || m < 0 || nsample < 0 || col < 0 || width < col + c || !grad_out || !idx || !grad_points)
         return HF_EINVAL;
+    const long long rpb = static_cast<long long>(m) * nsample;
     if (b == 0) return HF_OK;
     hipStream_t st = as_stream(stream);
-    int rc = hip_status(hipMemsetAsync(grad_points, 0, sizeof(float) * static_cast<size_t>(b) * n * c, st));
-    if (rc != HF_OK) return rc;
-    const long long nrows = static_cast<long long>(b) * m * nsample;
-    if (nrows == 0) return HF_OK;
-    const int block = 256;
-    hipLaunchKernelGGL(group_point_grad_from_kernel, dim3(grid_for(nrows * c, block)), dim3(block), 0, st, n, c, width, col,
-                       static_cast<long long>(m) * nsample, nrows, grad_out, idx, grad_points);
-    return launch_status();
+    const int rc = hip_status(hipMemsetAsync(grad_points, 0, sizeof(float) * static_cast<size_t>(b) * n * c, st));
+    if (rc != HF_OK || rpb == 0) return rc;
+    return launch_scatter_rows<1>(b, n, c, rpb, width, col, grad_out, idx, nullptr, grad_points, st);
 }
 
 HF_API int hf_group_point_grad_gather(int b, int n, int c, int m, int nsample, int width, int col, const float *grad_out,
                                       const int *offsets, const int *entries, float *grad_points, hf_stream_t stream)
 {
     if (b < 0 || n <= 0 || c <= 0 || m < 0 || nsample < 0 || col < 0 || width < col + c || !offsets || !grad_points) return HF_EINVAL;
-    const long long data_rows = static_cast<long long>(b) * n;
-    if (data_rows == 0) return HF_OK;
+    if (b == 0) return HF_OK;
     const long long rpb = static_cast<long long>(m) * nsample;
     if (rpb > 0 && (!grad_out || !entries)) return HF_EINVAL;
-    const bool vec4 = c % 4 == 0 && width % 4 == 0 && col % 4 == 0 &&
-                      ((reinterpret_cast<uintptr_t>(grad_out) | reinterpret_cast<uintptr_t>(grad_points)) % 16 == 0);
-    const int cv = vec4 ? c / 4 : c;
-    if (cv > 1024) return HF_EINVAL;
-    int block = 256;
-    if (cv > block) block = ((cv + 63) / 64) * 64;
-    const int rows_per_block = block / cv;
-    long long grid = (data_rows + rows_per_block - 1) / rows_per_block;
-    if (grid > kNumCU * 64ll) grid = kNumCU * 64ll;
-    if (vec4)
-        hipLaunchKernelGGL((group_point_grad_gather_kernel<4>), dim3(static_cast<unsigned>(grid)), dim3(block), 0, as_stream(stream), n, c,
-                           width, col, cv, rpb, data_rows, grad_out, offsets, entries, grad_points);
-    else
-        hipLaunchKernelGGL((group_point_grad_gather_kernel<1>), dim3(static_cast<unsigned>(grid)), dim3(block), 0, as_stream(stream), n, c,
-                           width, col, cv, rpb, data_rows, grad_out, offsets, entries, grad_points);
-    return launch_status();
+    return launch_grad_gather_rows<1>(b, n, c, rpb, width, col, grad_out, nullptr, offsets, entries, grad_points, as_stream(stream));
 }
 
 HF_API int hf_group_concat(int b, int n, int c, int m, int nsample, int width, int xyz_last, const float *grouped_xyz,
@@ -1011,17 +790,13 @@ HF_API int hf_group_concat_grad(int b, int n, int c, int m, int nsample, int wid
                                 const int *idx, float *grad_points, hf_stream_t stream)
 {
     if (b < 0 || n <= 0 || c <= 0 || m < 0 || nsample < 0 || width < 3 + c || !grad_points) return HF_EINVAL;
+    const long long rpb = static_cast<long long>(m) * nsample;
     if (b == 0) return HF_OK;
     hipStream_t st = as_stream(stream);
-    int rc = hip_status(hipMemsetAsync(grad_points, 0, sizeof(float) * static_cast<size_t>(b) * n * c, st));
-    if (rc != HF_OK) return rc;
-    const long long nrows = static_cast<long long>(b) * m * nsample;
-    if (nrows == 0) return HF_OK;  // empty tensors carry null pointers
-    if (!grad_out || !idx) return HF_EINVAL;
-    const int block = 256;
-    hipLaunchKernelGGL(group_concat_grad_kernel, dim3(grid_for(nrows * c, block)), dim3(block), 0, st, n, c, width,
-                       xyz_last ? 0 : 3, static_cast<long long>(m) * nsample, nrows, grad_out, idx, grad_points);
-    return launch_status();
+    const int rc = hip_status(hipMemsetAsync(grad_points, 0, sizeof(float) * static_cast<size_t>(b) * n * c, st));
+    if (rc != HF_OK || rpb == 0) return rc;
+    if (!grad_out || !idx) return HF_EINVAL;  // (empty tensors carry null pointers: checked only here)
+    return launch_scatter_rows<1>(b, n, c, rpb, width, xyz_last ? 0 : 3, grad_out, idx, nullptr, grad_points, st);
 }
 
 HF_API int hf_knn_point(int b, int n, int m, int k, const float *xyz1, const float *xyz2, float *val, int *idx,

@@ -78,6 +78,14 @@ constexpr int kNumXCD = 8;
 
 inline int div_up(long long a, long long b) { return static_cast<int>((a + b - 1) / b); }
 
+// workgroups for a grid-stride kernel over `work_items` items, `per_block` a workgroup: at most 8 per CU, at least one
+inline int grid_for(long long work_items, int per_block)
+{
+    const long long g = (work_items + per_block - 1) / per_block;
+    const long long cap = static_cast<long long>(kNumCU) * 8;
+    return static_cast<int>(g < 1 ? 1 : (g > cap ? cap : g));
+}
+
 // ---- wave64 cross-lane primitives (DPP) ----
 // old = 0 + bound_ctrl lets hipcc fold the move into v_max_u32_dpp / v_min_u32_dpp.
 template <int CTRL>

@@ -11,6 +11,7 @@
 #include <algorithm>
 
 #include "hf_common.h"
+#include "row_gather.h"
 
 namespace hf {
 
@@ -94,78 +95,8 @@ __global__ void three_interpolate_cf_grad_kernel(int c, int n, int m, const floa
     atomicAdd(g + k[2], go * w[2]);
 }
 
-// channel-last (the Python surface's layout): points (b,m,c) -> out (b,n,c).  VEC floats per lane,
-// c/VEC lanes per output row: row reads and writes are contiguous (16-byte when c % 4 == 0).
-template <int VEC>
-__global__ void three_interpolate_cl_kernel(int m, int c, long long n_per_batch, long long nrows,
-                                            const float *__restrict__ points, const int *__restrict__ idx,
-                                            const float *__restrict__ weight, float *__restrict__ out)
-{
-    typedef float vec_t __attribute__((ext_vector_type(VEC)));
-    const int cv = c / VEC;
-    const long long total = nrows * cv;
-    for (long long e = blockIdx.x * static_cast<long long>(blockDim.x) + threadIdx.x; e < total;
-         e += static_cast<long long>(gridDim.x) * blockDim.x) {
-        const long long row = e / cv;
-        const int l = static_cast<int>(e - row * cv);
-        const long long bb = row / n_per_batch;
-        const int *k = idx + row * 3;
-        const float *w = weight + row * 3;
-        const float *base = points + bb * m * c + l * VEC;
-        const vec_t p0 = *reinterpret_cast<const vec_t *>(base + static_cast<size_t>(k[0]) * c);
-        const vec_t p1 = *reinterpret_cast<const vec_t *>(base + static_cast<size_t>(k[1]) * c);
-        const vec_t p2 = *reinterpret_cast<const vec_t *>(base + static_cast<size_t>(k[2]) * c);
-        const vec_t r = w[0] * p0 + w[1] * p1 + w[2] * p2;  // left to right, no contraction
-        *reinterpret_cast<vec_t *>(out + row * c + l * VEC) = r;
-    }
-}
-
-// The same op when c / 4 is a power of two (c = 16 .. 1024, every width the reference configs use): no integer
-// division anywhere (lane -> row by a shift, the batch is grid.y), ROWS rows per thread in flight (3 * ROWS independent
-// 16-byte gathers before the first use), the write-once output leaves with nontemporal stores so that the points table
-// (a few MB per cloud) stays in the XCD's L2.  Consecutive lanes cover consecutive 16-byte pieces of consecutive rows.
-template <int ROWS>
-__global__ __launch_bounds__(256) void three_interpolate_cl_pow2_kernel(int nbatch, int m, int c, int cv_shift, int n,
-                                                                        const float *__restrict__ points,
-                                                                        const int *__restrict__ idx,
-                                                                        const float *__restrict__ weight,
-                                                                        float *__restrict__ out)
-{
-    typedef float v4 __attribute__((ext_vector_type(4)));
-    // linear workgroup id = cloud + b * chunk: workgroups are dealt round-robin over the 8 XCDs, so with b a multiple of 8
-    // every workgroup of a cloud runs on ONE XCD and that cloud's table stays in its 4 MB L2 (speed only)
-    const int bb = blockIdx.x % nbatch;
-    const unsigned gxb = gridDim.x / nbatch;
-    const unsigned tid = (blockIdx.x / nbatch) * 256u + threadIdx.x;
-    const int l = static_cast<int>(tid & ((1u << cv_shift) - 1u));
-    const int rstride = static_cast<int>((gxb * 256u) >> cv_shift);
-    const float *base = points + static_cast<size_t>(bb) * m * c + l * 4;
-    const int *kb = idx + static_cast<size_t>(bb) * n * 3;
-    const float *wb = weight + static_cast<size_t>(bb) * n * 3;
-    float *ob = out + static_cast<size_t>(bb) * n * c + l * 4;
-    for (int row0 = static_cast<int>(tid >> cv_shift); row0 < n; row0 += rstride * ROWS) {
-        v4 p[ROWS][3];
-        float w[ROWS][3];
-#pragma unroll
-        for (int i = 0; i < ROWS; ++i) {
-            const int row = row0 + i * rstride;
-            const int rr = row < n ? row : row0;
-#pragma unroll
-            for (int t = 0; t < 3; ++t) {
-                w[i][t] = wb[rr * 3 + t];
-                p[i][t] = *reinterpret_cast<const v4 *>(base + static_cast<size_t>(kb[rr * 3 + t]) * c);
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < ROWS; ++i) {
-            const int row = row0 + i * rstride;
-            if (row < n) {
-                const v4 r = w[i][0] * p[i][0] + w[i][1] * p[i][1] + w[i][2] * p[i][2];  // left to right, no contraction
-                __builtin_nontemporal_store(r, reinterpret_cast<v4 *>(ob + static_cast<size_t>(row) * c));
-            }
-        }
-    }
-}
+// channel-last (the Python surface's layout): points (b,m,c) -> out (b,n,c) and its two gradients are the weighted (NSRC = 3)
+// instances of the row-gather family: row_gather.h
 
 // three_interpolate written straight into the concat of pointnet_fp_module (pointnet_util.py:311-313):
 //   out[b,j,:] = [ sum_t w_t * points[b, idx_t, 0:c], skip[b,j,0:c1], 0 ... ]      (row width `width`, multiple of 4)
@@ -211,29 +142,9 @@ __global__ void three_interpolate_concat_kernel(int m, int c, int c1, int w4, lo
     }
 }
 
-__global__ void three_interpolate_cl_grad_kernel(int m, int c, long long n_per_batch, long long nrows,
-                                                 const float *__restrict__ grad_out, const int *__restrict__ idx,
-                                                 const float *__restrict__ weight, float *__restrict__ grad_points)
-{
-    const long long total = nrows * c;
-    for (long long e = blockIdx.x * static_cast<long long>(blockDim.x) + threadIdx.x; e < total;
-         e += static_cast<long long>(gridDim.x) * blockDim.x) {
-        const long long row = e / c;
-        const int l = static_cast<int>(e - row * c);
-        const long long bb = row / n_per_batch;
-        const int *k = idx + row * 3;
-        const float *w = weight + row * 3;
-        const float go = grad_out[e];
-        float *g = grad_points + bb * m * c + l;
-        atomicAdd(g + static_cast<size_t>(k[0]) * c, go * w[0]);
-        atomicAdd(g + static_cast<size_t>(k[1]) * c, go * w[1]);
-        atomicAdd(g + static_cast<size_t>(k[2]) * c, go * w[2]);
-    }
-}
-
 // ------------------------------------------------------------------------------------------
 // Inverse of a three_nn index (CSR over the known points) and the gather form of the interpolation gradient.
-// The scatter form above issues 3*N*C float atomics; with the inverse each known point sums its referencing
+// The scatter form (row_gather.h) issues 3*N*C float atomics; with the inverse each known point sums its referencing
 // rows in registers and writes once, in ascending (unknown point, slot) order -- the accumulation order of the
 // sequential loop in tf_interpolate.cpp:150-167, so the result is deterministic and matches it bit for bit.
 // One 1024-thread workgroup per cloud: counts and cursors live in LDS (2*m ints).
@@ -296,55 +207,6 @@ __global__ __launch_bounds__(kInvThreads) void three_nn_inverse_kernel(long long
     }
 }
 
-template <int VEC>
-__global__ void three_interpolate_cl_grad_gather_kernel(int n, int m, int c, int ld, int cv, long long known_rows,
-                                                        const float *__restrict__ grad_out,
-                                                        const float *__restrict__ weight,
-                                                        const int *__restrict__ offsets,
-                                                        const int *__restrict__ entries,
-                                                        float *__restrict__ grad_points)
-{
-    const int rows_per_block = blockDim.x / cv;
-    const int cvec = threadIdx.x % cv, rsub = threadIdx.x / cv;
-    if (rsub >= rows_per_block) return;
-    for (long long row = blockIdx.x * static_cast<long long>(rows_per_block) + rsub; row < known_rows;
-         row += static_cast<long long>(gridDim.x) * rows_per_block) {
-        const long long bb = row / m;
-        const int k = static_cast<int>(row - bb * m);
-        const int *off = offsets + bb * (m + 1);
-        const int *ent = entries + bb * 3ll * n;
-        const float *go = grad_out + bb * n * ld + cvec * VEC;  // ld: row stride of grad_out (>= c)
-        const float *w = weight + bb * 3ll * n;
-        float acc[VEC];
-#pragma unroll
-        for (int i = 0; i < VEC; ++i) acc[i] = 0.0f;
-        const int lo = off[k], hi = off[k + 1];
-        for (int a = lo; a < hi; ++a) {
-            const int e = ent[a];
-            const float wt = w[e];
-            const float *src = go + static_cast<long long>(e / 3) * ld;
-            if constexpr (VEC == 4) {
-                const float4 v = *reinterpret_cast<const float4 *>(src);
-                acc[0] += v.x * wt; acc[1] += v.y * wt; acc[2] += v.z * wt; acc[3] += v.w * wt;
-            } else {
-                acc[0] += src[0] * wt;
-            }
-        }
-        float *dst = grad_points + row * c + cvec * VEC;
-        if constexpr (VEC == 4) *reinterpret_cast<float4 *>(dst) = make_float4(acc[0], acc[1], acc[2], acc[3]);
-        else dst[0] = acc[0];
-    }
-}
-
-static int grid_for(long long work_items, int block)
-{
-    long long g = (work_items + block - 1) / block;
-    const long long cap = static_cast<long long>(kNumCU) * 8;
-    if (g > cap) g = cap;
-    if (g < 1) g = 1;
-    return static_cast<int>(g);
-}
-
 }  // namespace hf
 
 using namespace hf;
@@ -391,28 +253,8 @@ HF_API int hf_three_interpolate_cl(int b, int m, int c, int n, const float *poin
                                    const float *weight, float *out, hf_stream_t stream)
 {
     if (b < 0 || c <= 0 || m <= 0 || n < 0 || !points || !idx || !weight || !out) return HF_EINVAL;
-    const long long nrows = static_cast<long long>(b) * n;
-    if (nrows == 0) return HF_OK;
-    const int block = 256;
-    hipStream_t st = as_stream(stream);
-    const bool al16 = (reinterpret_cast<uintptr_t>(points) % 16 == 0) && (reinterpret_cast<uintptr_t>(out) % 16 == 0);
-    const int cv = c / 4;
-    if (c % 4 == 0 && al16 && cv >= 4 && cv <= 256 && (cv & (cv - 1)) == 0 && b <= 65535 && static_cast<long long>(n) * cv < (1LL << 31)) {
-        int cv_shift = 0;
-        while ((1 << cv_shift) < cv) ++cv_shift;
-        // 4 rows in flight per thread; enough workgroups for ~8 per CU across the batch
-        long long gx = (static_cast<long long>(n) * cv + 256 * 4 - 1) / (256 * 4);
-        const long long cap = std::max<long long>(1, (kNumCU * 8) / b);
-        if (gx > cap) gx = cap;
-        hipLaunchKernelGGL((three_interpolate_cl_pow2_kernel<4>), dim3(static_cast<unsigned>(gx * b)), dim3(256), 0, st, b, m, c,
-                           cv_shift, n, points, idx, weight, out);
-    } else if (c % 4 == 0 && al16)
-        hipLaunchKernelGGL((three_interpolate_cl_kernel<4>), dim3(grid_for(nrows * (c / 4), block)), dim3(block), 0, st,
-                           m, c, static_cast<long long>(n), nrows, points, idx, weight, out);
-    else
-        hipLaunchKernelGGL((three_interpolate_cl_kernel<1>), dim3(grid_for(nrows * c, block)), dim3(block), 0, st, m, c,
-                           static_cast<long long>(n), nrows, points, idx, weight, out);
-    return launch_status();
+    if (static_cast<long long>(b) * n == 0) return HF_OK;
+    return launch_gather_rows<3>(true, b, m, c, n, c, 0, points, idx, weight, out, as_stream(stream));
 }
 
 HF_API int hf_three_interpolate_cl_grad(int b, int n, int c, int m, const float *grad_out, const int *idx,
@@ -421,13 +263,18 @@ HF_API int hf_three_interpolate_cl_grad(int b, int n, int c, int m, const float 
     if (b < 0 || c <= 0 || m <= 0 || n < 0 || !grad_out || !idx || !weight || !grad_points) return HF_EINVAL;
     if (b == 0) return HF_OK;
     hipStream_t st = as_stream(stream);
-    int rc = hip_status(hipMemsetAsync(grad_points, 0, sizeof(float) * static_cast<size_t>(b) * m * c, st));
-    if (rc != HF_OK) return rc;
-    const long long nrows = static_cast<long long>(b) * n;
-    if (nrows == 0) return HF_OK;
-    const int block = 256;
-    hipLaunchKernelGGL(three_interpolate_cl_grad_kernel, dim3(grid_for(nrows * c, block)), dim3(block), 0, st, m, c,
-                       static_cast<long long>(n), nrows, grad_out, idx, weight, grad_points);
+    const int rc = hip_status(hipMemsetAsync(grad_points, 0, sizeof(float) * static_cast<size_t>(b) * m * c, st));
+    if (rc != HF_OK || n == 0) return rc;
+    return launch_scatter_rows<3>(b, m, c, n, c, 0, grad_out, idx, weight, grad_points, st);
+}
+
+// `total` index values per cloud, each in [0, m): one launch for both inverse entry points, which keep their own limits on m
+static int launch_index_inverse(int b, long long total, int m, const int *idx, int *offsets, int *entries, hipStream_t st)
+{
+    const size_t lds = sizeof(int) * 2 * static_cast<size_t>(m);   // m = 8192: 64 KB, above the default limit
+    const int lrc = ensure_dynamic_lds(reinterpret_cast<const void *>(&three_nn_inverse_kernel), lds);
+    if (lrc != HF_OK) return lrc;
+    hipLaunchKernelGGL(three_nn_inverse_kernel, dim3(b), dim3(kInvThreads), lds, st, total, m, idx, offsets, entries);
     return launch_status();
 }
 
@@ -436,11 +283,7 @@ HF_API int hf_three_nn_inverse(int b, int n, int m, const int *idx, int *offsets
     if (b < 0 || n < 0 || m <= 0 || m > kInvMaxKnown || !offsets || (n > 0 && (!idx || !entries))) return HF_EINVAL;
     if (b == 0) return HF_OK;
     if (static_cast<long long>(n) * 3 > 0x7fffffffll) return HF_EINVAL;
-    const size_t lds = sizeof(int) * 2 * static_cast<size_t>(m);   // m = 8192: 64 KB, above the default limit
-    const int lrc = ensure_dynamic_lds(reinterpret_cast<const void *>(&three_nn_inverse_kernel), lds);
-    if (lrc != HF_OK) return lrc;
-    hipLaunchKernelGGL(three_nn_inverse_kernel, dim3(b), dim3(kInvThreads), lds, as_stream(stream), 3ll * n, m, idx, offsets, entries);
-    return launch_status();
+    return launch_index_inverse(b, 3ll * n, m, idx, offsets, entries, as_stream(stream));
 }
 
 HF_API int hf_index_inverse(int b, long long total, int m, const int *idx, int *offsets, int *entries, hf_stream_t stream)
@@ -448,37 +291,18 @@ HF_API int hf_index_inverse(int b, long long total, int m, const int *idx, int *
     if (b < 0 || total < 0 || m <= 0 || m > kInvMaxTargets || total > 0x7fffffffll || !offsets || (total > 0 && (!idx || !entries)))
         return HF_EINVAL;
     if (b == 0) return HF_OK;
-    const size_t lds = sizeof(int) * 2 * static_cast<size_t>(m);
-    const int lrc = ensure_dynamic_lds(reinterpret_cast<const void *>(&three_nn_inverse_kernel), lds);
-    if (lrc != HF_OK) return lrc;
-    hipLaunchKernelGGL(three_nn_inverse_kernel, dim3(b), dim3(kInvThreads), lds, as_stream(stream), total, m, idx, offsets, entries);
-    return launch_status();
+    return launch_index_inverse(b, total, m, idx, offsets, entries, as_stream(stream));
 }
 
+// both gather-form gradient entries: grad_out rows of stride ld >= c, the interpolated columns first
 static int interpolate_grad_gather(int b, int n, int c, int ld, int m, const float *grad_out, const float *weight,
                                    const int *offsets, const int *entries, float *grad_points, hf_stream_t stream)
 {
     if (b < 0 || n < 0 || c < 0 || ld < c || m <= 0 || !offsets || !grad_points ||
         (n > 0 && c > 0 && (!grad_out || !weight || !entries)))
         return HF_EINVAL;
-    const long long known_rows = static_cast<long long>(b) * m;
-    if (known_rows == 0 || c == 0) return HF_OK;
-    const bool vec4 = (c % 4 == 0) && (ld % 4 == 0) &&
-                      ((reinterpret_cast<uintptr_t>(grad_out) | reinterpret_cast<uintptr_t>(grad_points)) % 16 == 0);
-    const int cv = vec4 ? c / 4 : c;
-    if (cv > 1024) return HF_EINVAL;
-    int block = 256;
-    if (cv > block) block = ((cv + 63) / 64) * 64;
-    const int rows_per_block = block / cv;
-    long long grid = (known_rows + rows_per_block - 1) / rows_per_block;
-    if (grid > kNumCU * 64ll) grid = kNumCU * 64ll;
-    if (vec4)
-        hipLaunchKernelGGL((three_interpolate_cl_grad_gather_kernel<4>), dim3(static_cast<unsigned>(grid)), dim3(block), 0,
-                           as_stream(stream), n, m, c, ld, cv, known_rows, grad_out, weight, offsets, entries, grad_points);
-    else
-        hipLaunchKernelGGL((three_interpolate_cl_grad_gather_kernel<1>), dim3(static_cast<unsigned>(grid)), dim3(block), 0,
-                           as_stream(stream), n, m, c, ld, cv, known_rows, grad_out, weight, offsets, entries, grad_points);
-    return launch_status();
+    if (b == 0 || c == 0) return HF_OK;
+    return launch_grad_gather_rows<3>(b, m, c, n, ld, 0, grad_out, weight, offsets, entries, grad_points, as_stream(stream));
 }
 
 HF_API size_t hf_three_nn_workspace(int b, int m)

@@ -17,6 +17,7 @@
 #include <math.h>
 
 #include "hf_common.h"
+#include "row_gather.h"
 
 namespace hf {
 
@@ -526,34 +527,7 @@ __global__ __launch_bounds__(1024) void fps_scratch_kernel(int n, int m, const f
     }
 }
 
-// gather_point: out[b,j,:] = inp[b,idx[b,j],:]   (tf_sampling_g.cu:172-181)
-__global__ void gather_point_kernel(int n, int m, long long total, const float *__restrict__ inp,
-                                    const int *__restrict__ idx, float *__restrict__ out)
-{
-    // one thread per output float: coalesced 4-byte stores, 12-byte segments gathered through L2
-    for (long long e = blockIdx.x * static_cast<long long>(blockDim.x) + threadIdx.x; e < total;
-         e += static_cast<long long>(gridDim.x) * blockDim.x) {
-        const long long row = e / 3;
-        const int c = static_cast<int>(e - row * 3);
-        const long long bb = row / m;
-        const int a = idx[row];
-        out[e] = inp[(bb * n + a) * 3 + c];
-    }
-}
-
-// gather_point grad: atomicAdd scatter (tf_sampling_g.cu:183-192), target zeroed by the caller
-__global__ void gather_point_grad_kernel(int n, int m, long long total, const float *__restrict__ out_g,
-                                         const int *__restrict__ idx, float *__restrict__ inp_g)
-{
-    for (long long e = blockIdx.x * static_cast<long long>(blockDim.x) + threadIdx.x; e < total;
-         e += static_cast<long long>(gridDim.x) * blockDim.x) {
-        const long long row = e / 3;
-        const int c = static_cast<int>(e - row * 3);
-        const long long bb = row / m;
-        const int a = idx[row];
-        atomicAdd(&inp_g[(bb * n + a) * 3 + c], out_g[e]);
-    }
-}
+// gather_point (tf_sampling_g.cu:172-192) and its gradient are the c = 3 copy instances of the row-gather family: row_gather.h
 
 template <int PPT, int NT>
 static int launch_fps_bucket(int b, int n, int m, const float *inp, int *out, hipStream_t st)
@@ -677,26 +651,18 @@ HF_API int hf_farthest_point_sample_variant(int kernel, int threads, int b, int 
 HF_API int hf_gather_point(int b, int n, int m, const float *inp, const int *idx, float *out, hf_stream_t stream)
 {
     if (b < 0 || n <= 0 || m < 0 || !inp || !idx || !out) return HF_EINVAL;
-    const long long total = static_cast<long long>(b) * m * 3;
-    if (total == 0) return HF_OK;
-    const int block = 256;
-    const int grid = static_cast<int>(std::min<long long>((total + block - 1) / block, kNumCU * 8));
-    hipLaunchKernelGGL(gather_point_kernel, dim3(grid), dim3(block), 0, as_stream(stream), n, m, total, inp, idx, out);
-    return launch_status();
+    if (static_cast<long long>(b) * m == 0) return HF_OK;
+    // one thread per output float: coalesced 4-byte stores, 12-byte segments gathered through L2
+    return launch_gather_rows<1, 3>(false, b, n, 3, m, 3, 0, inp, idx, nullptr, out, as_stream(stream));
 }
 
 HF_API int hf_gather_point_grad(int b, int n, int m, const float *out_g, const int *idx, float *inp_g,
                                 hf_stream_t stream)
 {
     if (b < 0 || n <= 0 || m < 0 || !out_g || !idx || !inp_g) return HF_EINVAL;
-    hipStream_t st = as_stream(stream);
     if (b == 0) return HF_OK;
-    int rc = hip_status(hipMemsetAsync(inp_g, 0, sizeof(float) * static_cast<size_t>(b) * n * 3, st));
-    if (rc != HF_OK) return rc;
-    const long long total = static_cast<long long>(b) * m * 3;
-    if (total == 0) return HF_OK;
-    const int block = 256;
-    const int grid = static_cast<int>(std::min<long long>((total + block - 1) / block, kNumCU * 8));
-    hipLaunchKernelGGL(gather_point_grad_kernel, dim3(grid), dim3(block), 0, st, n, m, total, out_g, idx, inp_g);
-    return launch_status();
+    hipStream_t st = as_stream(stream);
+    const int rc = hip_status(hipMemsetAsync(inp_g, 0, sizeof(float) * static_cast<size_t>(b) * n * 3, st));
+    if (rc != HF_OK || m == 0) return rc;
+    return launch_scatter_rows<1, 3>(b, n, 3, m, 3, 0, out_g, idx, nullptr, inp_g, st);
 }

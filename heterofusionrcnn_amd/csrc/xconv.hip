@@ -919,12 +919,6 @@ __global__ __launch_bounds__(kXcThreads) void xconv_dw_bwd_fts_kernel(long long 
     }
 }
 
-static int grid_for(long long items, int per_block)
-{
-    const long long blocks = (items + per_block - 1) / per_block;
-    return static_cast<int>(blocks < 1 ? 1 : (blocks > 8 * kNumCU ? 8 * kNumCU : blocks));
-}
-
 template <int K>
 static int launch_apply(long long rows, int c, const float *x, const float *f, float *out, bool transposed, hipStream_t st)
 {

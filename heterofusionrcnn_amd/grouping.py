@@ -42,12 +42,39 @@ def query_ball_point(radius, nsample, xyz1, xyz2, variant="auto"):
     return idx, cnt
 
 
+def gather_rows_into(points, idx, out, col):
+    """out[..., col:col+C] = points[idx] for points (B,N,C), idx (B,M,K) and out (B,M,K,width) contiguous: the gather written
+    straight into a column slice of wider rows (hf_group_point_into)"""
+    b, n, c = points.shape
+    _, m, ns = idx.shape
+    check(_lib.lib().hf_group_point_into(b, n, c, m, ns, out.shape[-1], col, ptr(points), ptr(idx), ptr(out), stream_ptr()),
+          "group_point_into")
+
+
+def gather_rows_grad(grad_out, col, idx, n, c, inverse=None):
+    """the gradient of that gather w.r.t. points, (B,N,C), read in place from columns col.. of grad_out (B,M,K,width) contiguous:
+    by the inverse index (offsets, entries) = index_inverse(idx, N) where it came with the geometry -- every row written once,
+    no atomics -- else scattered with atomics into a zero-filled target"""
+    b, m, ns = idx.shape
+    width = grad_out.shape[-1]
+    g = torch.empty((b, n, c), dtype=torch.float32, device=grad_out.device)
+    if inverse is not None:
+        offsets, entries = inverse
+        check(_lib.lib().hf_group_point_grad_gather(b, n, c, m, ns, width, col, ptr(grad_out), ptr(offsets), ptr(entries), ptr(g),
+                                                    stream_ptr()), "group_point_grad_gather")
+    else:
+        check(_lib.lib().hf_group_point_grad_from(b, n, c, m, ns, width, col, ptr(grad_out), ptr(idx), ptr(g), stream_ptr()),
+              "group_point_grad_from")
+    return g
+
+
 class _GroupPoint(torch.autograd.Function):
     @staticmethod
     def forward(ctx, points, idx):
         b, n, c = points.shape
         _, m, ns = idx.shape
         out = torch.empty((b, m, ns, c), dtype=torch.float32, device=points.device)
+        # dense rows: hf_group_point also has the form for power-of-two widths, which the column-slice entry does not take
         check(_lib.lib().hf_group_point(b, n, c, m, ns, ptr(points), ptr(idx), ptr(out), stream_ptr()), "group_point")
         ctx.save_for_backward(idx)
         ctx.shape = (b, n, c)
@@ -57,12 +84,7 @@ class _GroupPoint(torch.autograd.Function):
     def backward(ctx, grad_out):
         (idx,) = ctx.saved_tensors
         b, n, c = ctx.shape
-        _, m, ns = idx.shape
-        grad_out = grad_out.contiguous()
-        g = torch.empty((b, n, c), dtype=torch.float32, device=grad_out.device)
-        check(_lib.lib().hf_group_point_grad(b, n, c, m, ns, ptr(grad_out), ptr(idx), ptr(g), stream_ptr()),
-              "group_point_grad")
-        return g, None
+        return gather_rows_grad(grad_out.contiguous(), 0, idx, n, c), None
 
 
 def group_point(points, idx):
@@ -104,8 +126,7 @@ class _ConcatGroup(torch.autograd.Function):
         ch = head.shape[-1]
         out = torch.empty((b, m, ns, ch + c), dtype=torch.float32, device=points.device)
         out[..., :ch].copy_(head)
-        check(_lib.lib().hf_group_point_into(b, n, c, m, ns, ch + c, ch, ptr(points), ptr(idx), ptr(out), stream_ptr()),
-              "group_point_into")
+        gather_rows_into(points, idx, out, ch)
         ctx.save_for_backward(idx, *([offsets, entries] if offsets is not None else []))
         ctx.shape = (b, n, c, ch)
         return out
@@ -114,18 +135,10 @@ class _ConcatGroup(torch.autograd.Function):
     def backward(ctx, grad_out):
         idx = ctx.saved_tensors[0]
         b, n, c, ch = ctx.shape
-        _, m, ns = idx.shape
         grad_out = grad_out.contiguous()
         g = None
-        if ctx.needs_input_grad[1]:
-            g = torch.empty((b, n, c), dtype=torch.float32, device=grad_out.device)
-            if len(ctx.saved_tensors) == 3:   # the inverse index came with the geometry: gather, every row written once
-                offsets, entries = ctx.saved_tensors[1:]
-                check(_lib.lib().hf_group_point_grad_gather(b, n, c, m, ns, ch + c, ch, ptr(grad_out), ptr(offsets), ptr(entries),
-                                                            ptr(g), stream_ptr()), "group_point_grad_gather")
-            else:
-                check(_lib.lib().hf_group_point_grad_from(b, n, c, m, ns, ch + c, ch, ptr(grad_out), ptr(idx), ptr(g), stream_ptr()),
-                      "group_point_grad_from")
+        if ctx.needs_input_grad[1]:   # with the inverse index of the geometry: gather, every row written once
+            g = gather_rows_grad(grad_out, ch, idx, n, c, ctx.saved_tensors[1:] or None)
         return (grad_out[..., :ch] if ctx.needs_input_grad[0] else None), g, None, None, None
 
 

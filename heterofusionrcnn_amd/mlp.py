@@ -15,6 +15,7 @@ from . import _dense_kernels as _k
 from . import _lib
 from ._dense_kernels import _STATS_GENERATION, Running, running_stats_written  # noqa: F401  (re-exported: the counter lives there)
 from ._lib import check, ptr, stream_ptr
+from .grouping import gather_rows_grad
 
 
 def _on_gpu(*tensors):
@@ -551,7 +552,6 @@ class _GatherLinear(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dz, _dmean, _dinvstd):
-        L = _lib.lib()
         idx, gxyz, weight, *rest = ctx.saved_tensors
         points = rest[0] if rest else None
         b, m, k, c, n_src, cout, xyz_first = ctx.dims
@@ -561,8 +561,7 @@ class _GatherLinear(torch.autograd.Function):
         if points is not None and ctx.needs_input_grad[0]:
             wf = (weight[:, 3:3 + c] if xyz_first else weight[:, :c]).contiguous()
             dg = dz @ wf                                               # (rows, c): the gradient of the gathered features
-            dpoints = torch.empty((b, n_src, c), dtype=torch.float32, device=dz.device)
-            check(L.hf_group_point_grad(b, n_src, c, m, k, ptr(dg), ptr(idx), ptr(dpoints), stream_ptr()), "group_point_grad")
+            dpoints = gather_rows_grad(dg, 0, idx, n_src, c)
         # the bias feeds a BatchNorm: its gradient is exactly zero (see _SharedMLPChain.backward)
         return dpoints, None, None, dw, torch.zeros((cout,), dtype=torch.float32, device=dz.device), None, None, None
 

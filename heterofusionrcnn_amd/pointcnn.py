@@ -31,7 +31,7 @@ import torch.nn.functional as F
 
 from . import _lib
 from ._lib import check, ptr, require, stream_ptr
-from .grouping import INVERSE_MAX_TARGETS, concat_group, group_point, index_inverse, knn_point
+from .grouping import INVERSE_MAX_TARGETS, concat_group, gather_rows_grad, gather_rows_into, group_point, index_inverse, knn_point
 from .sampling import farthest_point_sample, gather_point
 from . import _dense_kernels as _k
 from .mlp import BatchNormReLU, bf16_route, linear_bf16_eval, linear_nobias
@@ -166,20 +166,18 @@ class _BNConcatGroup(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, z, gamma, beta, running_mean, running_var, eps, momentum, mode, points, idx, offsets, entries):
-        L = _lib.lib()
         b, n, c = points.shape
         _, m, ns = idx.shape
         ch, width = z.shape[1], z.shape[1] + c
         out = torch.empty((b, m, ns, width), dtype=torch.float32, device=z.device)
         _, mean, invstd = _k.bn_fwd_train(z, gamma, beta, _k.Running(running_mean, running_var, eps, momentum), mode, out=out, ld=width)
-        check(L.hf_group_point_into(b, n, c, m, ns, width, ch, ptr(points), ptr(idx), ptr(out), stream_ptr()), "group_point_into")
+        gather_rows_into(points, idx, out, ch)
         ctx.save_for_backward(z, gamma, beta, mean, invstd, idx, *([offsets, entries] if offsets is not None else []))
         ctx.meta = (b, n, c, m, ns, ch, mode)
         return out
 
     @staticmethod
     def backward(ctx, go):
-        L = _lib.lib()
         z, gamma, beta, mean, invstd, idx = ctx.saved_tensors[:6]
         b, n, c, m, ns, ch, mode = ctx.meta
         width = ch + c
@@ -187,14 +185,7 @@ class _BNConcatGroup(torch.autograd.Function):
         dz, dgamma, dbeta, _ = _k.bn_bwd(z, go, gamma, beta, mean, invstd, mode, ld=width)
         g = None
         if ctx.needs_input_grad[8]:
-            g = torch.empty((b, n, c), dtype=torch.float32, device=z.device)
-            if len(ctx.saved_tensors) == 8:
-                offsets, entries = ctx.saved_tensors[6:]
-                check(L.hf_group_point_grad_gather(b, n, c, m, ns, width, ch, ptr(go), ptr(offsets), ptr(entries), ptr(g), stream_ptr()),
-                      "group_point_grad_gather")
-            else:
-                check(L.hf_group_point_grad_from(b, n, c, m, ns, width, ch, ptr(go), ptr(idx), ptr(g), stream_ptr()),
-                      "group_point_grad_from")
+            g = gather_rows_grad(go, ch, idx, n, c, ctx.saved_tensors[6:] or None)
         return dz, dgamma, dbeta, None, None, None, None, None, g, None, None, None
 
 
