@@ -139,6 +139,9 @@ _SIGNATURES = {
     "hf_xconv_depthwise_gather_grad": [_i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                        _vp, _sz, _vp],
     "hf_xconv_depthwise_gather_grad_workspace": [_i, _i, _i, _i, _i, _i],
+    "hf_xconv_depthwise_gather_bn": [_i] * 7 + [_vp] * 10 + [_vp],
+    "hf_xconv_depthwise_gather_bn_grad": [_i] * 7 + [_vp] * 18 + [_vp, _sz, _vp],
+    "hf_xconv_depthwise_gather_bn_grad_workspace": [_i, _i, _i, _i, _i, _i],
     "hf_kitti_eval_workspace": [_i, ctypes.c_longlong, ctypes.c_longlong],
     "hf_kitti_eval_overlaps": [_i, _vp, _vp, _vp, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, _i, _i, _vp, _vp, _vp, _vp],
     "hf_kitti_eval": [_i, _vp, _vp, _vp, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, _i, _i] + [_vp] * 6 + [_i, _i]
@@ -170,6 +173,7 @@ _RESTYPES = {
     "hf_linear_bn_fwd_workspace": _sz,
     "hf_linear_bn_bwd_workspace": _sz,
     "hf_xconv_depthwise_gather_grad_workspace": _sz,
+    "hf_xconv_depthwise_gather_bn_grad_workspace": _sz,
     "hf_lift_elu_bn_fwd_workspace": _sz,
     "hf_depthwise_k_grad_workspace": _sz,
     "hf_lift_elu_bn_bwd_workspace": _sz,

@@ -34,7 +34,7 @@ from ._lib import check, ptr, require, stream_ptr
 from .grouping import INVERSE_MAX_TARGETS, concat_group, gather_rows_grad, gather_rows_into, group_point, index_inverse, knn_point
 from .sampling import farthest_point_sample, gather_point
 from . import _dense_kernels as _k
-from .mlp import BatchNormReLU, bf16_route, linear_bf16_eval, linear_nobias
+from .mlp import BatchNormReLU, bf16_route, linear_bf16_eval, linear_nobias, training_precision_name
 
 
 class EluBN(nn.Module):
@@ -82,48 +82,63 @@ class _DenseChainElu(torch.autograd.Function):
     node on the fp32 MFMA kernels.  Forward: each layer's batch statistics come out of its GEMM's accumulators (no statistics
     pass), the first layer's normalisation is applied while the second GEMM stages its operand (no normalisation pass; the
     normalised activation is stored once, for the weight gradient).  Backward: the BatchNorm-backward sums of the first layer
-    come out of the input-gradient GEMM of the second (no reduction pass)."""
+    come out of the input-gradient GEMM of the second (no reduction pass).
+    fold: the node stops before the second layer's normalisation and returns (z1, mean1, invstd1) for a consumer that applies it on load
+    (_XConvDepthwiseGatherBN); its backward then receives dz1 itself, and the gradients of g1 / b1 come from that consumer."""
 
     @staticmethod
-    def forward(ctx, x, w0, g0, b0, w1, g1, b1, bn0, bn1):
+    def forward(ctx, x, w0, g0, b0, w1, g1, b1, bn0, bn1, fold=False):
         w0, w1 = w0.contiguous(), w1.contiguous()
         z0, m0, i0, _ = _k.linear_elu_bn_fwd(x, w0, bn0)
         z1, m1, i1, y0 = _k.linear_elu_bn_fwd(z0, w1, bn1, (g0, b0, m0, i0), keep_act=True)
-        out = _k.bn_apply(z1, g1, b1, m1, i1, 2)
+        ctx.fold = fold
         ctx.save_for_backward(x, z0, m0, i0, y0, z1, m1, i1, w0, g0, b0, w1, g1, b1)
-        return out
+        if fold:
+            ctx.mark_non_differentiable(m1, i1)
+            return z1, m1, i1
+        return _k.bn_apply(z1, g1, b1, m1, i1, 2)
 
     @staticmethod
-    def backward(ctx, dout):
+    def backward(ctx, dout, *_):
         from .mlp import _splitk_wgrad
         x, z0, m0, i0, y0, z1, m1, i1, w0, g0, b0, w1, g1, b1 = ctx.saved_tensors
-        dz1, dg1, db1, _ = _k.bn_bwd(z1, dout.contiguous(), g1, b1, m1, i1, 2)
+        if ctx.fold:
+            dz1, dg1, db1 = dout.contiguous(), None, None
+        else:
+            dz1, dg1, db1, _ = _k.bn_bwd(z1, dout.contiguous(), g1, b1, m1, i1, 2)
         dy0, dg0, db0 = _k.linear_elu_bn_bwd(dz1, w1.t().contiguous(), z0, g0, b0, m0, i0)
         dz0 = _k.bn_bwd_dx(z0, dy0, g0, b0, m0, i0, dg0, db0, 2)
         dx = dz0 @ w0 if ctx.needs_input_grad[0] else None
-        return dx, _splitk_wgrad(dz0, x), dg0, db0, _splitk_wgrad(dz1, y0), dg1, db1, None, None
+        return dx, _splitk_wgrad(dz0, x), dg0, db0, _splitk_wgrad(dz1, y0), dg1, db1, None, None, None
 
 
 class _LiftChain(torch.autograd.Function):
     """The lifting chain on a THREE-channel input (the local coordinates, pointcnn.py:96-99) without its first layer's output in
     memory: the statistics of elu(W0 x) from one pass over x, y0 = BN0(elu(W0 x)) rebuilt from x inside the second GEMM's operand
     staging, inside the weight-gradient GEMM and inside the two backward passes (hf_lift_elu_bn_fwd / _bwd).  Of the chain's
-    rows x C tensors only z1 (pre-activation of the second layer), the output and dz1 are ever written."""
+    rows x C tensors only z1 (pre-activation of the second layer), the output and dz1 are ever written.
+    fold (as _DenseChainElu): returns (z1, mean1, invstd1) and the output is not written either."""
 
     @staticmethod
-    def forward(ctx, x, w0, g0, b0, w1, g1, b1, bn0, bn1):
+    def forward(ctx, x, w0, g0, b0, w1, g1, b1, bn0, bn1, fold=False):
         w0, w1 = w0.contiguous(), w1.contiguous()
         m0, i0, z1, m1, i1 = _k.lift_elu_bn_fwd(x, w0, g0, b0, bn0, w1, bn1)
-        out = _k.bn_apply(z1, g1, b1, m1, i1, 2)
+        ctx.fold = fold
         ctx.save_for_backward(x, m0, i0, z1, m1, i1, w0, g0, b0, w1, g1, b1)
-        return out
+        if fold:
+            ctx.mark_non_differentiable(m1, i1)
+            return z1, m1, i1
+        return _k.bn_apply(z1, g1, b1, m1, i1, 2)
 
     @staticmethod
-    def backward(ctx, dout):
+    def backward(ctx, dout, *_):
         x, m0, i0, z1, m1, i1, w0, g0, b0, w1, g1, b1 = ctx.saved_tensors
-        dz1, dg1, db1, _ = _k.bn_bwd(z1, dout.contiguous(), g1, b1, m1, i1, 2)
+        if ctx.fold:
+            dz1, dg1, db1 = dout.contiguous(), None, None
+        else:
+            dz1, dg1, db1, _ = _k.bn_bwd(z1, dout.contiguous(), g1, b1, m1, i1, 2)
         dw0_t, dw1, dg0, db0 = _k.lift_elu_bn_bwd(x, w0, g0, b0, m0, i0, dz1, w1.t().contiguous())
-        return None, dw0_t.t(), dg0, db0, dw1, dg1, db1, None, None
+        return None, dw0_t.t(), dg0, db0, dw1, dg1, db1, None, None, None
 
 
 def _lift_chain_eval(d0, d1, x):
@@ -137,8 +152,10 @@ def _lift_chain_eval(d0, d1, x):
     return out.reshape(*x.shape[:-1], out.shape[1])
 
 
-def dense_chain(d0, d1, x):
-    """d1(d0(x)) for two Dense modules; tall batches on the device take the one-node MFMA route"""
+def dense_chain(d0, d1, x, fold=False):
+    """d1(d0(x)) for two Dense modules; tall batches on the device take the one-node MFMA route.
+    fold: where one of the two fused training nodes runs, it stops before d1's normalisation and this returns the tuple
+    (z1 (rows, c1), mean1, invstd1) instead of the output; on every other route fold changes nothing"""
     from .mlp import FUSED_FWD_MIN_ROWS
     rows = x.numel() // x.shape[-1]
     bn0, bn1 = d0.post.bn, d1.post.bn
@@ -151,11 +168,11 @@ def dense_chain(d0, d1, x):
             and rows >= FUSED_FWD_MIN_ROWS and c0 <= 160 and c1 <= 224 and x.shape[-1] <= 1024):
         if x.shape[-1] == 3 and c0 % 4 == 0 and not x.requires_grad:
             out = _LiftChain.apply(x.reshape(rows, 3).contiguous(), d0.linear.weight, bn0.weight, bn0.bias, d1.linear.weight, bn1.weight,
-                                   bn1.bias, bn0, bn1)
-            return out.reshape(*x.shape[:-1], c1)
+                                   bn1.bias, bn0, bn1, fold)
+            return out if fold else out.reshape(*x.shape[:-1], c1)
         out = _DenseChainElu.apply(x.reshape(rows, x.shape[-1]).contiguous(), d0.linear.weight, bn0.weight, bn0.bias, d1.linear.weight,
-                                   bn1.weight, bn1.bias, bn0, bn1)
-        return out.reshape(*x.shape[:-1], c1)
+                                   bn1.weight, bn1.bias, bn0, bn1, fold)
+        return out if fold else out.reshape(*x.shape[:-1], c1)
     return d1(d0(x))
 
 
@@ -368,7 +385,55 @@ class _XConvDepthwiseGather(torch.autograd.Function):
         return (gx.reshape(sx) if gx is not None else None), (gf.reshape(sf) if gf is not None else None), gt, None, None, None, gw, None
 
 
+class _XConvDepthwiseGatherBN(torch.autograd.Function):
+    """hf_xconv_depthwise_gather_bn (+ grad): _XConvDepthwiseGather with F_delta = BN1(elu(z1)) rebuilt on load from the lifting chain's
+    pre-activation z1 (B*P*K, C0) and (gamma, beta, mean, invstd): the normalisation pass of the chain and F_delta itself do not exist.
+    Backward: the kernel that stores the gradient of F_delta also sums that BatchNorm's dgamma / dbeta (no reduction pass), and
+    bn_bwd_dx turns it into dz1 for the chain's node.  Forward output and the x / fts / wd gradients are the bits of the unfolded route."""
+
+    @staticmethod
+    def forward(ctx, x, z1, gamma, beta, mean, invstd, fts, idx, offsets, entries, wd):
+        k, c, m = wd.shape
+        b, p = idx.shape[0], idx.shape[1]
+        c0, c1, n = z1.shape[-1], fts.shape[-1], fts.shape[1]
+        x2, z, t2, w, idx = x.reshape(-1, k, k).contiguous(), z1.contiguous(), fts.contiguous(), wd.contiguous(), idx.contiguous()
+        gamma, beta = gamma.contiguous(), beta.contiguous()
+        out = torch.empty((b * p, c * m), dtype=torch.float32, device=fts.device)
+        check(_lib.lib().hf_xconv_depthwise_gather_bn(b, n, p, k, c0, c1, m, ptr(x2), ptr(z), ptr(gamma), ptr(beta), ptr(mean), ptr(invstd),
+                                                      ptr(t2), ptr(idx), ptr(w), ptr(out), stream_ptr()), "xconv_depthwise_gather_bn")
+        ctx.save_for_backward(x2, z, gamma, beta, mean, invstd, t2, idx, w, *([offsets, entries] if offsets is not None else []))
+        ctx.dims = (b, p, n, tuple(x.shape), tuple(z1.shape))
+        return out.reshape(b, p, c * m)
+
+    @staticmethod
+    def backward(ctx, go):
+        x2, z, gamma, beta, mean, invstd, t2, idx, w, *inv = ctx.saved_tensors
+        b, p, n, sx, sz = ctx.dims
+        k, c, m = w.shape
+        c0, c1 = z.shape[-1], t2.shape[-1]
+        go = go.reshape(-1, c * m).contiguous()
+        gx = torch.empty_like(x2) if ctx.needs_input_grad[0] else None
+        gf = torch.empty_like(z) if ctx.needs_input_grad[1] else None
+        gt = torch.empty_like(t2) if ctx.needs_input_grad[6] else None
+        gw = torch.empty_like(w) if ctx.needs_input_grad[10] else None
+        dgamma, dbeta = (torch.empty_like(gamma), torch.empty_like(beta)) if gf is not None else (None, None)
+        require(gt is None or inv, "xconv_depthwise_gather_bn: the gradient of the feature table needs the inverse neighbour table")
+        off, ent = inv if inv else (None, None)
+        L = _lib.lib()
+        nbytes = L.hf_xconv_depthwise_gather_bn_grad_workspace(b, p, k, c0, c1, m)
+        ws = torch.empty((nbytes // 4,), dtype=torch.float32, device=go.device)
+        check(L.hf_xconv_depthwise_gather_bn_grad(b, n, p, k, c0, c1, m, ptr(x2), ptr(z), ptr(gamma), ptr(beta), ptr(mean), ptr(invstd), ptr(t2),
+                                                  ptr(idx), ptr(w), ptr(go), ptr(off), ptr(ent), ptr(gx), ptr(gf), ptr(gt), ptr(gw), ptr(dgamma),
+                                                  ptr(dbeta), ptr(ws), nbytes, stream_ptr()), "xconv_depthwise_gather_bn_grad")
+        dz1 = _k.bn_bwd_dx(z, gf, gamma, beta, mean, invstd, dgamma, dbeta, 2).reshape(sz) if gf is not None else None
+        return (gx.reshape(sx) if gx is not None else None), dz1, dgamma, dbeta, None, None, gt, None, None, None, gw
+
+
 _XDW_KM = {(8, 1), (8, 2), (8, 3), (8, 4), (4, 1), (4, 4), (12, 1), (12, 2)}
+_XBN_KM = {(8, 1), (8, 2), (8, 4)}      # (K, M) of hf_xconv_depthwise_gather_bn: the gather layers of the shipped configurations
+# The lifting branch's last BatchNorm applied inside the X-Conv kernels (gather route, training, the fused chain nodes); False keeps the
+# chain's own normalisation pass and hf_xconv_depthwise_gather everywhere (tests/test_xconv_bn_route.py compares the two)
+FOLD_LIFT_BN = True
 
 
 def xconv_depthwise_gather(x, f_delta, fts, idx, wd, inverse=None, use_workspace=True):
@@ -524,18 +589,27 @@ class XConv(nn.Module):
                     lside.wait_stream(cur)
         gather = self.with_x and fts is not None and _gather_fusable(pts, c_delta, fts, self.conv.depthwise, inverse)
         fuse_concat = (not gather) and fts is not None and _fusable(bn1, fts, c_delta, c_delta + fts.shape[-1])
+        # fold: where the chain runs as one of its fused training nodes, it hands over (z1, mean, invstd) instead of F_delta and the
+        # X-Conv kernels normalise on load (hf_xconv_depthwise_gather_bn: its (K, M) set and 32-bit element offsets)
+        kd, cd, md = self.conv.depthwise.shape
+        fold = (gather and FOLD_LIFT_BN and training_precision_name() == "fp32" and (kd, md) in _XBN_KM and b * p * k * cd < (1 << 32)
+                and b * fts.shape[1] * cd < (1 << 32))
+        folded = None
         # the coordinate-only part of the lifting branch (on its side stream when there is one) ...
         with torch.cuda.stream(lside) if lside is not None else contextlib.nullcontext():
             local = offsets()                                    # (B,P,K,3)  P' <- P - p
             if gather:
-                f = dense_chain(self.lift0, self.lift1, local)    # F_delta alone: the neighbours' features are read in place below
+                f = dense_chain(self.lift0, self.lift1, local, fold=fold)    # F_delta alone: the neighbours' features are read in place below
+                if isinstance(f, tuple):
+                    folded, f = f, f[0]
             elif fuse_concat:
                 f = linear_nobias(self.lift0(local), self.lift1.linear.weight)      # z of the second lifting layer
             else:
                 f = self.lift1(self.lift0(local))                 # F_delta
         if lside is not None:                                  # join: this stream's next kernel reads f
             cur.wait_stream(lside)
-            f.record_stream(cur)
+            for t in (folded if folded is not None else (f,)):   # folded: z1 and the two statistics vectors, read where f was
+                t.record_stream(cur)
         # ... and the part that reads the previous layer's features
         if fuse_concat:
             # F_* <- [F_delta, F]: the second lifting layer's BatchNorm writes into the concat, the gather fills the rest
@@ -551,8 +625,13 @@ class XConv(nn.Module):
             else:
                 x = self._x_transform(local, b, p, k)
             # F_X <- X x F_*, then the depthwise half of the separable convolution, in one pass
-            fx = (xconv_depthwise_gather(x, f, fts, idx, self.conv.depthwise, inverse) if gather
-                  else xconv_depthwise(x, f, self.conv.depthwise))
+            if folded is not None:
+                off, ent = inverse if inverse is not None else (None, None)
+                fx = _XConvDepthwiseGatherBN.apply(x, folded[0], bn1.weight, bn1.bias, folded[1], folded[2], fts, idx, off, ent,
+                                                   self.conv.depthwise)
+            else:
+                fx = (xconv_depthwise_gather(x, f, fts, idx, self.conv.depthwise, inverse) if gather
+                      else xconv_depthwise(x, f, self.conv.depthwise))
             bnc = self.conv.post.bn
             if not bnc.training and bf16_route(fx, self.conv.pointwise.weight):
                 # inference in bf16: the pointwise half with its ELU and BatchNorm as one launch (SeparableK.forward's route)

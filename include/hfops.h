@@ -659,6 +659,35 @@ int hf_xconv_depthwise_gather_grad(int b, int n_src, int rows_per_cloud, int k, 
                                    const float *grad_out, const int *offsets, const int *entries, float *grad_x,
                                    float *grad_f_delta, float *grad_fts, float *grad_wd, void *workspace, size_t workspace_bytes,
                                    hf_stream_t stream);
+/* The same pass with the lifting branch's last BatchNorm folded in (csrc/xconv_bn.hip).  On the gather route
+ * F_delta = BN1(elu(z1)) is an elementwise function of the second lifting layer's pre-activation z1 (rows, k, c0) and of
+ * gamma, beta, mean, invstd (c0 each; the batch statistics hf_lift_elu_bn_fwd / hf_linear_elu_bn_fwd return).  These entries take
+ * those five in place of f_delta and rebuild it on load,
+ *   a = gamma * invstd;  F_delta = a * (elu(z1) - mean) + beta     (hf_bn_relu_fwd_eval's sequence with mode 2, ELU on exp2),
+ * so the normalisation pass and F_delta itself do not exist:
+ *   hf_xconv_depthwise_gather_bn(.., z1, gamma, beta, mean, invstd, ..) = hf_xconv_depthwise_gather(.., F_delta, ..), bit for bit.
+ * hf_xconv_depthwise_gather_bn_grad: grad_x, grad_fts, grad_wd as hf_xconv_depthwise_gather_grad with a workspace, bit for bit;
+ * grad_f (rows, k, c0) is the gradient with respect to F_delta, the BatchNorm's OUTPUT (the same bits again), and with it come the
+ * two sums of that BatchNorm's backward pass over the rows x k values of a channel,
+ *   dbeta = sum grad_f,   dgamma = sum grad_f * xhat,   xhat = (elu(z1) - mean) * invstd,
+ * taken from the values the kernel stores (per lane over its rows, the waves of a block in a fixed order, the blocks in double: no
+ * atomics, the same bits on every call; they agree with hf_bn_relu_bwd's to fp32 rounding).  dz1 is then one call of
+ * hf_bn_relu_bwd_dx(z1, grad_f, .., dgamma, dbeta, mode 2).  dgamma and dbeta are required with grad_f and untouched without it.
+ * workspace (hf_xconv_depthwise_gather_bn_grad_workspace bytes) is required whenever there are rows:
+ * [hf_xconv_depthwise_gather_grad's two regions][BatchNorm partial sums: row chunks x 2 x c0].
+ * Limits, beyond those of the twins: (k, m) in {(8,1), (8,2), (8,4)}, the gather layers of the shipped PointCNN configurations;
+ * rows * k * (c0 + c1) and b * n_src * (c0 + c1) below 2^32 (32-bit element offsets).  Anything else: HF_EINVAL, and the caller
+ * keeps hf_bn_relu_fwd_eval + hf_xconv_depthwise_gather. */
+size_t hf_xconv_depthwise_gather_bn_grad_workspace(int b, int rows_per_cloud, int k, int c0, int c1, int m);
+int hf_xconv_depthwise_gather_bn(int b, int n_src, int rows_per_cloud, int k, int c0, int c1, int m, const float *x,
+                                 const float *z1, const float *gamma, const float *beta, const float *mean, const float *invstd,
+                                 const float *fts, const int *idx, const float *wd, float *out, hf_stream_t stream);
+int hf_xconv_depthwise_gather_bn_grad(int b, int n_src, int rows_per_cloud, int k, int c0, int c1, int m, const float *x,
+                                      const float *z1, const float *gamma, const float *beta, const float *mean,
+                                      const float *invstd, const float *fts, const int *idx, const float *wd,
+                                      const float *grad_out, const int *offsets, const int *entries, float *grad_x,
+                                      float *grad_f, float *grad_fts, float *grad_wd, float *dgamma, float *dbeta,
+                                      void *workspace, size_t workspace_bytes, hf_stream_t stream);
 
 /* The FIRST layer of a set-abstraction MLP on neighbourhoods read in place: sample_and_group
  * (hf/core/feature_extractors/pointnet_util.py:42-64) materialises new_points (B,M,K,C+3) = [grouped_xyz - centre | points[idx]] and

@@ -1,0 +1,112 @@
+"""Kernel set of csrc/xconv_bn.hip, on any machine with hipcc: the file is compiled to assembly with the Makefile's flags and its code
+object must hold exactly the three BatchNorm-folding twins at the (K, M) their entry points dispatch (the forward also by V2), plus
+the finalize kernel; none of them may spill a vector register or touch scratch.  Only the kernel-metadata table is read (names, LDS,
+registers, spills, scratch).  Run as a script, the module prints the table committed as profiles/xconv_bn_instantiations.md."""
+import os
+import sys
+import tempfile
+
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from test_gemm_instantiations_cpu import compile_to_assembly, kernel_table  # noqa: E402
+
+XBN_DISPATCH = ((8, 1), (8, 2), (8, 4))        # HF_XBN_DISPATCH of csrc/xconv_bn.hip = _XBN_KM of pointcnn.py
+
+
+def expected():
+    want = {("xconv_bn_finalize_kernel", ())}
+    for k, m in XBN_DISPATCH:
+        want |= {("xconv_bn_fwd_kernel", (k, m, False)), ("xconv_bn_fwd_kernel", (k, m, True)), ("xconv_bn_bwd_fw_kernel", (k, m)),
+                 ("xconv_bn_bwd_x_kernel", (k, m))}
+    return want
+
+
+@pytest.fixture(scope="module")
+def table(tmp_path_factory):
+    return kernel_table(compile_to_assembly(tmp_path_factory.mktemp("xconv_bn_asm"), "xconv_bn.hip"))
+
+
+def test_the_kernel_set_is_the_three_twins_at_the_dispatched_arguments_plus_the_finalize(table):
+    compiled = {(name, args) for name, args, _ in table}
+    assert compiled == expected(), sorted(compiled ^ expected())
+    assert len(table) == len(compiled) == 4 * len(XBN_DISPATCH) + 1
+
+
+def test_the_routing_table_of_the_package_is_the_dispatched_set():
+    from heterofusionrcnn_amd import pointcnn
+    assert pointcnn._XBN_KM == set(XBN_DISPATCH) and pointcnn._XBN_KM <= pointcnn._XDW_KM
+
+
+def test_no_kernel_spills_or_uses_scratch(table):
+    for name, args, f in table:
+        assert f["spill"] == 0 and f["scratch"] == 0, (name, args, f)
+
+
+def test_the_backward_keeps_four_waves_per_simd(table):
+    """xdw_bwd_grid launches four blocks per CU, one wave of each per SIMD: 512 VGPRs / 4 = 128 is what the attribute on
+    xconv_bn_bwd_fw_kernel holds the kernel to"""
+    for name, args, f in table:
+        if name == "xconv_bn_bwd_fw_kernel":
+            assert f["vgpr"] <= 128, (args, f["vgpr"])
+
+
+def check_argument_limits():
+    """one past each limit of the two entry points returns HF_EINVAL before any launch (fake non-null pointers, never dereferenced); the
+    limit itself passes the argument check and is stopped by the missing workspace.  tests/test_xconv_bn_abi.py runs this on the GPU too"""
+    import ctypes
+    from heterofusionrcnn_amd import _lib
+    L = _lib.lib()
+    fake = ctypes.c_void_p(256)
+    EINVAL, EWS = _lib.HF_EINVAL, _lib.HF_EWORKSPACE
+
+    def fwd(b=2, n=50, p=37, k=8, c0=64, c1=32, m=1, null=None, out=fake):
+        ins = [None if i == null else fake for i in range(9)]           # x z1 gamma beta mean invstd fts idx wd
+        return L.hf_xconv_depthwise_gather_bn(b, n, p, k, c0, c1, m, *ins, out, None)
+
+    def bwd(b=2, n=50, p=37, k=8, c0=64, c1=32, m=1, null=None, inv=(fake, fake), grads=(fake, fake, fake, fake), sums=(fake, fake), ws=None, nbytes=0):
+        ins = [None if i == null else fake for i in range(10)]          # ... and grad_out
+        return L.hf_xconv_depthwise_gather_bn_grad(b, n, p, k, c0, c1, m, *ins, *inv, *grads, *sums, ws, nbytes, None)
+
+    bad = {}
+    for name, f in (("fwd", fwd), ("bwd", bwd)):
+        bad.update({"%s: c0 = 48" % name: f(c0=48), "%s: c0 = 0" % name: f(c0=0), "%s: c1 = 0" % name: f(c1=0), "%s: n_src = 0" % name: f(n=0),
+                    "%s: (8, 3)" % name: f(m=3), "%s: (8, 8)" % name: f(m=8), "%s: (4, 1)" % name: f(k=4), "%s: (12, 1)" % name: f(k=12),
+                    "%s: b < 0" % name: f(b=-1),
+                    "%s: rows k c = 2^32" % name: f(b=1024, p=1024, c0=256, c1=256), "%s: table rows x c = 2^32" % name: f(b=1024, n=8192, p=1, c0=256, c1=256)})
+        bad.update({"%s: input %d is NULL" % (name, i): f(null=i) for i in range(9)})
+    bad.update({"fwd: no output": fwd(out=None), "bwd: no grad_out": bwd(null=9), "bwd: nothing asked for": bwd(grads=(None,) * 4),
+                "bwd: grad_fts without the inverse table": bwd(inv=(None, None)), "bwd: grad_f without dgamma": bwd(sums=(None, fake)),
+                "bwd: grad_f without dbeta": bwd(sums=(fake, None))})
+    wrong = {name: got for name, got in bad.items() if got != EINVAL}
+    assert not wrong, wrong
+    # the limits themselves: only the workspace is left to refuse
+    assert bwd() == EWS and bwd(m=2) == EWS and bwd(m=4) == EWS and bwd(c0=128) == EWS
+    assert bwd(b=1024, p=1023, c0=256, c1=256) == EWS and bwd(b=1024, n=8191, p=1, c0=256, c1=256) == EWS
+    need = L.hf_xconv_depthwise_gather_bn_grad_workspace(2, 37, 8, 64, 32, 1)
+    assert need > L.hf_xconv_depthwise_gather_grad_workspace(2, 37, 8, 64, 32, 1) and bwd(ws=fake, nbytes=need - 1) == EWS
+    assert bwd(grads=(fake, None, fake, fake), sums=(None, None)) == EWS        # without grad_f the two sums are not required
+    assert L.hf_xconv_depthwise_gather_bn_grad_workspace(0, 37, 8, 64, 32, 1) == 0
+    assert fwd(b=0) == _lib.HF_OK                                               # an empty batch launches nothing
+
+
+def test_one_past_each_argument_limit_is_refused():
+    check_argument_limits()
+
+
+def render(table):
+    lines = ["# Kernels and template instantiations of csrc/xconv_bn.hip", "",
+             "Compiled for gfx950 with the Makefile's flags (`-O3 -ffp-contract=off`); produced by",
+             "`python tests/test_xconv_bn_instantiations_cpu.py`.  Template arguments: `xconv_bn_fwd_kernel<K, M, V2>`,",
+             "`xconv_bn_bwd_fw_kernel` / `xconv_bn_bwd_x_kernel<K, M>`.  LDS is the static part (`xconv_bn_bwd_x_kernel` takes its own at launch).", "",
+             "| kernel | template arguments | LDS bytes | VGPRs | spilled VGPRs | spilled SGPRs | scratch bytes |", "|---|---|---:|---:|---:|---:|---:|"]
+    for name, args, f in table:
+        lines.append("| `%s` | %s | %d | %d | %d | %d | %d |" % (name, ", ".join(str(a).lower() for a in args) or "-", f["lds"], f["vgpr"], f["spill"],
+                                                                f["sgpr_spill"], f["scratch"]))
+    lines += ["", "%d kernels." % len(table)]
+    return "\n".join(lines)
+
+
+if __name__ == "__main__":
+    with tempfile.TemporaryDirectory() as d:
+        print(render(kernel_table(compile_to_assembly(d, "xconv_bn.hip"))))
