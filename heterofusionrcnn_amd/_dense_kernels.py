@@ -3,7 +3,8 @@ hf_narrow_linear_dx entries of the C ABI (csrc/mlp.hip, gemm.hip, fp_linear.hip,
 
 A function takes contiguous fp32 device tensors and plain numbers, allocates the outputs and the workspace its entry asks for, makes the
 one call and returns the outputs.  No autograd, no routing and no validation live here (mlp.py and pointcnn.py own those, and their public
-entry points refuse host tensors); the only state is the generation counter of the running statistics.  Conventions:
+entry points refuse host tensors); the only state is the generation counter of the running statistics.  One function chooses between
+two entries that compute the same gradients: lift_elu_bn_bwd, by the module switch LIFT_BWD_ONE_PASS and the entry's limit.  Conventions:
   bn       anything with .eps, .momentum, .running_mean, .running_var (a BatchNormReLU, or Running(...) inside a node that was handed
            the four separately); the running buffers are updated in place
   in_bn    (gamma, beta, mean, invstd) of the layer before, applied to the operand while it is staged, or None
@@ -298,10 +299,23 @@ def lift_elu_bn_fwd(x, w0, g0, b0, bn0, w1, bn1):
     return m0, i0, z1, m1, i1
 
 
+# The chain's backward with dy0 = dz1 W1 formed once (hf_onepass_lift_elu_bn_bwd, csrc/lift_bwd.hip) wherever that entry takes the shape;
+# False keeps the two-pass entry everywhere.  Same dW1, dgamma0, dbeta0 bits either way; dW0 differs by fp32 rounding of its sums.
+LIFT_BWD_ONE_PASS = True
+LIFT_BWD_ONE_PASS_MAX_C0 = 128      # the entry's limit (include/hfops.h); wider chains take the two-pass entry
+
+
 def lift_elu_bn_bwd(x, w0, g0, b0, m0, i0, dz1, w1t):
     """-> (dW0^T (3, c0), dW1, dgamma0, dbeta0)"""
     rows, c0, c1 = x.shape[0], w0.shape[0], dz1.shape[1]
     dw0_t, dw1, dg0, db0 = _f32(x, 3, c0), _f32(x, c1, c0), torch.empty_like(g0), torch.empty_like(b0)
+    if LIFT_BWD_ONE_PASS and c0 <= LIFT_BWD_ONE_PASS_MAX_C0:
+        nbytes = lib().hf_onepass_lift_elu_bn_bwd_workspace(rows, c0, c1)
+        ws = _ws(x, nbytes)
+        check(lib().hf_onepass_lift_elu_bn_bwd(rows, c0, c1, ptr(x), ptr(w0), ptr(g0), ptr(b0), ptr(m0), ptr(i0), ptr(dz1), ptr(w1t),
+                                               ptr(dw0_t), ptr(dw1), ptr(dg0), ptr(db0), ptr(ws), nbytes, stream_ptr()),
+              "onepass_lift_elu_bn_bwd")
+        return dw0_t, dw1, dg0, db0
     nbytes = lib().hf_lift_elu_bn_bwd_workspace(rows, c0, c1)
     ws = _ws(x, nbytes)
     check(lib().hf_lift_elu_bn_bwd(rows, c0, c1, ptr(x), ptr(w0), ptr(g0), ptr(b0), ptr(m0), ptr(i0), ptr(dz1), ptr(w1t), ptr(dw0_t),

@@ -104,6 +104,8 @@ _SIGNATURES = {
     "hf_lift_elu_fwd_eval_bn": [ctypes.c_longlong, _i, _i] + [_vp] * 12 + [_vp, _sz, _vp],
     "hf_lift_elu_bn_bwd_workspace": [ctypes.c_longlong, _i, _i],
     "hf_lift_elu_bn_bwd": [ctypes.c_longlong, _i, _i] + [_vp] * 12 + [_vp, _sz, _vp],
+    "hf_onepass_lift_elu_bn_bwd_workspace": [ctypes.c_longlong, _i, _i],
+    "hf_onepass_lift_elu_bn_bwd": [ctypes.c_longlong, _i, _i] + [_vp] * 12 + [_vp, _sz, _vp],
     "hf_f32_to_bf16": [ctypes.c_longlong, _vp, _vp, _vp],
     "hf_linear_bf16_fwd_eval": [ctypes.c_longlong, _i, _i] + [_vp] * 7 + [_i, _vp, _vp],
     "hf_f32_to_bf16_transpose": [_i, _i, _vp, _vp, _vp],
@@ -177,6 +179,7 @@ _RESTYPES = {
     "hf_lift_elu_bn_fwd_workspace": _sz,
     "hf_depthwise_k_grad_workspace": _sz,
     "hf_lift_elu_bn_bwd_workspace": _sz,
+    "hf_onepass_lift_elu_bn_bwd_workspace": _sz,
     "hf_kitti_eval_workspace": _sz,
     "hf_rpn_batch_points_workspace": _sz,
     "hf_rpn_batch_image_workspace": _sz,

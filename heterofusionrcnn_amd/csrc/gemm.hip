@@ -25,6 +25,7 @@
 
 #include "hf_common.h"
 #include "gemm_common.h"
+#include "lift_common.h"
 
 namespace hf {
 
@@ -439,54 +440,10 @@ __global__ __launch_bounds__(kGemmThreads) __attribute__((amdgpu_waves_per_eu(2)
 // The lifting chain of an X-Conv (pointcnn.py:96-99): two pf.dense layers on the K local coordinates of every point,
 //   y0 = BN0(elu(W0 x)),  x (rows, 3);      z1 = y0 W1^T,  out = BN1(elu(z1)).
 // The first layer has THREE input channels: its output (rows x C0, 268 MB at a million rows) is cheaper to recompute from x
-// wherever it is needed than to write once and read four times.  Every kernel below forms z0 the same way (lift_z), so the
-// forward statistics, the operand of the second GEMM, the weight gradient and both backward passes see the same bits.
+// wherever it is needed than to write once and read four times.  Every kernel below forms z0 the same way (lift_z of
+// lift_common.h, with LiftTab and the other shared pieces), so the forward statistics, the operand of the second GEMM, the weight
+// gradient and both backward passes see the same bits.
 // ------------------------------------------------------------------------------------------
-constexpr int kLiftMaxC = 256;
-struct LiftTab {
-    float wx[kLiftMaxC], wy[kLiftMaxC], wz[kLiftMaxC], a[kLiftMaxC], mu[kLiftMaxC], be[kLiftMaxC], is[kLiftMaxC];
-};
-
-__device__ __forceinline__ void lift_tab_load(LiftTab &T, int c, const float *__restrict__ w0, const float *__restrict__ gamma,
-                                              const float *__restrict__ beta, const float *__restrict__ mean,
-                                              const float *__restrict__ invstd)
-{
-    for (int k = threadIdx.x; k < c; k += blockDim.x) {
-        T.wx[k] = w0[3 * k];
-        T.wy[k] = w0[3 * k + 1];
-        T.wz[k] = w0[3 * k + 2];
-        T.a[k] = gamma[k] * invstd[k];
-        T.mu[k] = mean[k];
-        T.be[k] = beta[k];
-        T.is[k] = invstd[k];
-    }
-}
-__device__ __forceinline__ float lift_z(float wx, float wy, float wz, float x0, float x1, float x2) { return (x0 * wx + x1 * wy) + x2 * wz; }
-// the first layer's ELU is evaluated five times per element instead of once, and expm1f (~30 instructions) made the lift
-// kernels VALU-bound (the forward wrote its 268 MB in 119 us): elu_hw, exp(x) - 1 on the hardware exponential
-__device__ __forceinline__ float lift_y(const LiftTab &T, int k, float x0, float x1, float x2)
-{
-    return T.a[k] * (elu_hw(lift_z(T.wx[k], T.wy[k], T.wz[k], x0, x1, x2)) - T.mu[k]) + T.be[k];
-}
-// the three coordinates of row `row`, zero outside [0, row_end)
-__device__ __forceinline__ void lift_load_x(const float *__restrict__ x3, long long row, long long row_end, float (&x)[3])
-{
-    const bool ok = row < row_end;
-    const float *px = x3 + (ok ? row : 0) * 3;
-    const float a = px[0], b = px[1], c = px[2];
-    x[0] = ok ? a : 0.f; x[1] = ok ? b : 0.f; x[2] = ok ? c : 0.f;
-}
-// y0 of channels k .. k+3 of a row with coordinates x; zero outside the matrix
-__device__ __forceinline__ float4 lift_y4(const LiftTab &T, int k, int c0, bool rin, const float (&x)[3])
-{
-    float4 v;
-    v.x = (rin && k < c0) ? lift_y(T, k, x[0], x[1], x[2]) : 0.f;
-    v.y = (rin && k + 1 < c0) ? lift_y(T, k + 1, x[0], x[1], x[2]) : 0.f;
-    v.z = (rin && k + 2 < c0) ? lift_y(T, k + 2, x[0], x[1], x[2]) : 0.f;
-    v.w = (rin && k + 3 < c0) ? lift_y(T, k + 3, x[0], x[1], x[2]) : 0.f;
-    return v;
-}
-
 // batch statistics of elu(W0 x): a lane owns a channel, the waves of a block walk a chunk of rows (x is wave-uniform)
 __global__ __launch_bounds__(256) void lift_stats_kernel(long long rows, int c, long long rows_per_block,
                                                          const float *__restrict__ x3, const float *__restrict__ w0,
@@ -1058,21 +1015,11 @@ HF_API size_t hf_lift_elu_bn_bwd_workspace(long long rows, int c0, int c1)
     return hf_linear_wgrad_workspace(rows, c1, c0) + sizeof(float) * 3 * static_cast<size_t>(c0) * kBnMaxBlocks;
 }
 
-HF_API int hf_lift_elu_bn_bwd(long long rows, int c0, int c1, const float *x3, const float *w0, const float *gamma0, const float *beta0,
-                              const float *mean0, const float *invstd0, const float *dz1, const float *w1_t, float *grad_w0_t,
-                              float *grad_w1, float *dgamma0, float *dbeta0, void *workspace, size_t workspace_bytes,
-                              hf_stream_t stream)
+// dW1 = dz1^T y0 of both backward entries of the chain: lift_wgrad_kernel into the head of the workspace, then the fixed-order sum
+static void lift_wgrad_launch(long long rows, int c0, int c1, const WgradPlan &p, const float *x3, const float *w0, const float *gamma0,
+                              const float *beta0, const float *mean0, const float *invstd0, const float *dz1, float *wpartial,
+                              float *grad_w1, hipStream_t st)
 {
-    if (rows <= 0 || c0 <= 0 || c0 > 160 || c0 % 4 != 0 || c1 <= 0 || c1 > 256 || !x3 || !w0 || !gamma0 || !beta0 || !mean0 || !invstd0 ||
-        !dz1 || !w1_t || !grad_w0_t || !grad_w1 || !dgamma0 || !dbeta0)
-        return HF_EINVAL;
-    if (!workspace || workspace_bytes < hf_lift_elu_bn_bwd_workspace(rows, c0, c1)) return HF_EWORKSPACE;
-    hipStream_t st = as_stream(stream);
-    // dW1 = dz1^T y0
-    const WgradPlan p = wgrad_plan(rows, c1, c0);
-    if (p.chunks > 65535) return HF_EINVAL;
-    float *wpartial = static_cast<float *>(workspace);
-    float *spartial = reinterpret_cast<float *>(static_cast<unsigned char *>(workspace) + hf_linear_wgrad_workspace(rows, c1, c0));
     const dim3 wgrid(p.mtiles * p.ntiles, p.chunks);
 #define HF_LIFT_WG(M, N)                                                                                                \
     hipLaunchKernelGGL((lift_wgrad_kernel<M, N>), wgrid, dim3(kGemmThreads), 0, st, rows, c1, c0, p.mtiles, p.rows_per_chunk, \
@@ -1083,6 +1030,23 @@ HF_API int hf_lift_elu_bn_bwd(long long rows, int c0, int c1, const float *x3, c
     else HF_LIFT_WG(1, 1);
 #undef HF_LIFT_WG
     launch_partial_reduce(c1 * c0, p.chunks, wpartial, grad_w1, st);
+}
+
+HF_API int hf_lift_elu_bn_bwd(long long rows, int c0, int c1, const float *x3, const float *w0, const float *gamma0, const float *beta0,
+                              const float *mean0, const float *invstd0, const float *dz1, const float *w1_t, float *grad_w0_t,
+                              float *grad_w1, float *dgamma0, float *dbeta0, void *workspace, size_t workspace_bytes,
+                              hf_stream_t stream)
+{
+    if (rows <= 0 || c0 <= 0 || c0 > 160 || c0 % 4 != 0 || c1 <= 0 || c1 > 256 || !x3 || !w0 || !gamma0 || !beta0 || !mean0 || !invstd0 ||
+        !dz1 || !w1_t || !grad_w0_t || !grad_w1 || !dgamma0 || !dbeta0)
+        return HF_EINVAL;
+    if (!workspace || workspace_bytes < hf_lift_elu_bn_bwd_workspace(rows, c0, c1)) return HF_EWORKSPACE;
+    hipStream_t st = as_stream(stream);
+    const WgradPlan p = wgrad_plan(rows, c1, c0);
+    if (p.chunks > 65535) return HF_EINVAL;
+    float *wpartial = static_cast<float *>(workspace);
+    float *spartial = reinterpret_cast<float *>(static_cast<unsigned char *>(workspace) + hf_linear_wgrad_workspace(rows, c1, c0));
+    lift_wgrad_launch(rows, c0, c1, p, x3, w0, gamma0, beta0, mean0, invstd0, dz1, wpartial, grad_w1, st);
     // the first layer's BatchNorm-backward sums, then its weight gradient: dy0 = dz1 W1 rebuilt in the accumulators both times
     const long long ntiles = (rows + kFwdRows - 1) / kFwdRows;
     const int nt = div_up(c0, 32);
@@ -1106,4 +1070,29 @@ HF_API int hf_lift_elu_bn_bwd(long long rows, int c0, int c1, const float *x3, c
 #undef HF_LIFT_BWD
     hipLaunchKernelGGL(partial_rows_sum_kernel, dim3(3 * c0), dim3(256), 0, st, nblk, spartial, grad_w0_t);
     return launch_status();
+}
+
+HF_API size_t hf_onepass_lift_elu_bn_bwd_workspace(long long rows, int c0, int c1)
+{
+    if (rows <= 0 || c0 <= 0 || c1 <= 0) return 0;
+    return hf_linear_wgrad_workspace(rows, c1, c0) + sizeof(float) * kLiftOnePassSums * static_cast<size_t>(c0) * kBnMaxBlocks;
+}
+
+// the same gradients with dy0 = dz1 W1 formed ONCE: dW1 as above, then the one sweep and the finalize of lift_bwd.hip
+HF_API int hf_onepass_lift_elu_bn_bwd(long long rows, int c0, int c1, const float *x3, const float *w0, const float *gamma0,
+                                      const float *beta0, const float *mean0, const float *invstd0, const float *dz1, const float *w1_t,
+                                      float *grad_w0_t, float *grad_w1, float *dgamma0, float *dbeta0, void *workspace,
+                                      size_t workspace_bytes, hf_stream_t stream)
+{
+    if (rows <= 0 || c0 <= 0 || c0 > kLiftOnePassMaxC0 || c0 % 4 != 0 || c1 <= 0 || c1 > 256 || !x3 || !w0 || !gamma0 || !beta0 || !mean0 ||
+        !invstd0 || !dz1 || !w1_t || !grad_w0_t || !grad_w1 || !dgamma0 || !dbeta0)
+        return HF_EINVAL;
+    if (!workspace || workspace_bytes < hf_onepass_lift_elu_bn_bwd_workspace(rows, c0, c1)) return HF_EWORKSPACE;
+    hipStream_t st = as_stream(stream);
+    const WgradPlan p = wgrad_plan(rows, c1, c0);
+    if (p.chunks > 65535) return HF_EINVAL;
+    float *wpartial = static_cast<float *>(workspace);
+    float *spartial = reinterpret_cast<float *>(static_cast<unsigned char *>(workspace) + hf_linear_wgrad_workspace(rows, c1, c0));
+    lift_wgrad_launch(rows, c0, c1, p, x3, w0, gamma0, beta0, mean0, invstd0, dz1, wpartial, grad_w1, st);
+    return launch_lift_bwd_onepass(rows, c1, c0, dz1, w1_t, x3, w0, gamma0, mean0, invstd0, spartial, grad_w0_t, dgamma0, dbeta0, st);
 }

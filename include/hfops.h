@@ -396,6 +396,18 @@ size_t hf_lift_elu_bn_bwd_workspace(long long rows, int c0, int c1);
 int hf_lift_elu_bn_bwd(long long rows, int c0, int c1, const float *x3, const float *w0, const float *gamma0, const float *beta0,
                        const float *mean0, const float *invstd0, const float *dz1, const float *w1_t, float *grad_w0_t,
                        float *grad_w1, float *dgamma0, float *dbeta0, void *workspace, size_t workspace_bytes, hf_stream_t stream);
+/* hf_lift_elu_bn_bwd with dy0 = dz1 W1 formed ONCE (csrc/lift_bwd.hip): the same arguments and outputs.  One sweep over dz1 keeps
+ * eleven sums per first-layer channel -- sum dy0, sum dy0 xhat0 and, with s = elu'(z0) and d = 0, 1, 2, A_d = sum dy0 (s x_d),
+ * B_d = sum s x_d, C_d = sum xhat0 (s x_d) -- and a finalize kernel adds the workgroups' partials in fp64 and evaluates
+ *   grad_w0_t[d][c] = gamma0_c invstd0_c (A_d - (dbeta0_c / rows) B_d - (dgamma0_c / rows) C_d)
+ * in fp64, rounded once.  grad_w1, dgamma0 and dbeta0 are bit-identical to hf_lift_elu_bn_bwd's; grad_w0_t agrees with it to fp32
+ * rounding of the sums (no atomics: two calls give the same bits).  c0 a multiple of 4 and <= 128 (wider chains: hf_lift_elu_bn_bwd),
+ * c1 <= 256; anything else is HF_EINVAL, a missing or short workspace HF_EWORKSPACE, both before any launch. */
+size_t hf_onepass_lift_elu_bn_bwd_workspace(long long rows, int c0, int c1);
+int hf_onepass_lift_elu_bn_bwd(long long rows, int c0, int c1, const float *x3, const float *w0, const float *gamma0, const float *beta0,
+                               const float *mean0, const float *invstd0, const float *dz1, const float *w1_t, float *grad_w0_t,
+                               float *grad_w1, float *dgamma0, float *dbeta0, void *workspace, size_t workspace_bytes,
+                               hf_stream_t stream);
 
 /* Reduced-precision inference of the wide dense layers (csrc/linear_bf16.hip): the only entry points of the library that do not
  * compute in fp32 end to end.  bf16 values travel as uint16_t (the upper half of the fp32 bit pattern).
