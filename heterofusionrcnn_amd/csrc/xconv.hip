@@ -467,78 +467,19 @@ __global__ __launch_bounds__(kXcThreads) void xconv_dw_bwd_fw_kernel(long long r
 }
 
 // gradient w.r.t. X: dX[r][k][j] = sum_ch dF_X[r][k][ch] * F[r][j][ch] with dF_X rebuilt from grad_out and Wd on the fly;
-// a wave per row, the 64 partial K x K matrices of the lanes meet in LDS (as xconv_dx_kernel)
+// a wave per row.  The body is xc_bwd_x_body of xconv_common.h (shared with xconv_bn_bwd_x_kernel): Wd staged in LDS once per
+// block, scalar row bases with 32-bit lane offsets, the next trip's loads in flight behind the current products, and the 64
+// partial K x K matrices of the lanes summed by a halving exchange across the lanes (no LDS, 6 adds per entry).
+// Dynamic LDS: xc_bwd_x_lds_bytes(c, 0, K * M).
 template <int K, int M, bool GATHER>
 __global__ __launch_bounds__(kXcThreads) void xconv_dw_bwd_x_kernel(long long rows, int c, int c0, const float *__restrict__ f,
                                                                    const float *__restrict__ fts, const int *__restrict__ idx, int n_src,
                                                                    int rows_per_cloud, const float *__restrict__ wd,
                                                                    const float *__restrict__ grad_out, float *__restrict__ grad_x)
 {
-    // the 64 partial K x K matrices of a wave's lanes are first summed inside each quad of lanes (two DPP adds per entry),
-    // the 16 quad sums meet in LDS: a quarter of the LDS of the one-slot-per-lane form (4.2 KB per wave: 9 blocks per CU
-    // instead of 2, which is what the gathered loads need to stay in flight) and a quarter of its reads
     extern __shared__ float lds[];
-    constexpr int KK = K * K, STRIDE = KK + 1, QUADS = 16;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    float *mine = lds + static_cast<size_t>(w) * QUADS * STRIDE;
-    const long long wave = w + static_cast<long long>(blockIdx.x) * (kXcThreads / 64);
-    const long long nwaves = static_cast<long long>(gridDim.x) * (kXcThreads / 64);
-    const int c1 = c - c0;
-    for (long long r = wave; r < rows; r += nwaves) {
-        float acc[K][K];
-#pragma unroll
-        for (int i = 0; i < K; ++i)
-#pragma unroll
-            for (int j = 0; j < K; ++j) acc[i][j] = 0.f;
-        long long trow[K];   // the K table rows of this row's neighbours, once per row (wave-uniform)
-        if constexpr (GATHER) {
-            const long long tbase = static_cast<long long>(static_cast<unsigned>(r) / static_cast<unsigned>(rows_per_cloud)) * n_src;
-#pragma unroll
-            for (int j = 0; j < K; ++j) trow[j] = tbase + idx[r * K + j];
-        }
-        for (int ch = lane; ch < c; ch += 64) {
-            float fv[K], g[M];
-            if constexpr (GATHER) {
-                // selects, no branch around the loads
-                const bool gathered = ch >= c0;
-                const float *base = gathered ? fts + (ch - c0) : f + ch;
-                const long long stride = gathered ? c1 : c0;
-#pragma unroll
-                for (int j = 0; j < K; ++j) fv[j] = base[(gathered ? trow[j] : r * K + j) * stride];
-            } else {
-#pragma unroll
-                for (int j = 0; j < K; ++j) fv[j] = f[(r * K + j) * c + ch];
-            }
-            load_m<M>(grad_out, static_cast<size_t>(r * c + ch) * M, g);
-#pragma unroll
-            for (int k = 0; k < K; ++k) {
-                float a = 0.f;
-#pragma unroll
-                for (int m = 0; m < M; ++m) a = a + g[m] * wd[(static_cast<size_t>(k) * c + ch) * M + m];
-#pragma unroll
-                for (int j = 0; j < K; ++j) acc[k][j] = acc[k][j] + a * fv[j];
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < K; ++i)
-#pragma unroll
-            for (int j = 0; j < K; ++j) {
-                float v = acc[i][j];
-                v = v + __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0xb1, 0xf, 0xf, true));   // quad_perm [1,0,3,2]
-                v = v + __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x4e, 0xf, 0xf, true));   // quad_perm [2,3,0,1]
-                if ((lane & 3) == 0) mine[(lane >> 2) * STRIDE + i * K + j] = v;
-            }
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        for (int p = lane; p < KK; p += 64) {
-            float s = 0.f;
-#pragma unroll
-            for (int l = 0; l < QUADS; ++l) s = s + mine[l * STRIDE + p];
-            grad_x[r * KK + p] = s;
-        }
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-    }
+    xc_bwd_x_body<K, M, GATHER, false>(rows, c, c0, f, nullptr, nullptr, nullptr, nullptr, fts, idx, n_src, rows_per_cloud, wd, grad_out,
+                                       grad_x, lds);
 }
 
 // gradient w.r.t. the gathered feature table (GATHER mode): table row s collects, in ascending (row, slot) order (the CSR
@@ -980,7 +921,7 @@ static int xdw_backward(long long rows, int k, int c, int c0, int m, const float
         if (rc != HF_OK) return rc;
     }
     if (grad_x) {
-        const size_t lds = sizeof(float) * (kXcThreads / 64) * 16 * (static_cast<size_t>(k) * k + 1);   // <= 37 KB at K = 12
+        const size_t lds = xc_bwd_x_lds_bytes(c, 0, k * m);   // the staged Wd: at most 16 KB
 #define HF_XDW_BX(KK, MM)                                                                                              \
         if (idx) hipLaunchKernelGGL((xconv_dw_bwd_x_kernel<KK, MM, true>), dim3(grid_for(rows, kXcThreads / 64)), dim3(kXcThreads), lds, st, rows, c, c0, f, fts, idx, n_src, rows_per_cloud, wd, grad_out, grad_x); \
         else hipLaunchKernelGGL((xconv_dw_bwd_x_kernel<KK, MM, false>), dim3(grid_for(rows, kXcThreads / 64)), dim3(kXcThreads), lds, st, rows, c, c0, f, fts, idx, n_src, rows_per_cloud, wd, grad_out, grad_x);

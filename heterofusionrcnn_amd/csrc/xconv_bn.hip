@@ -234,7 +234,7 @@ __global__ __launch_bounds__(kXcThreads) void xconv_bn_finalize_kernel(int c0, i
     }
 }
 
-// gradient w.r.t. X: xconv_dw_bwd_x_kernel<K, M, true> with the lifted values normalised on load
+// gradient w.r.t. X: xconv_dw_bwd_x_kernel<K, M, true> with the lifted values normalised on load (xc_bwd_x_body with BN on)
 template <int K, int M>
 __global__ __launch_bounds__(kXcThreads) void xconv_bn_bwd_x_kernel(long long rows, int c, int c0, const float *__restrict__ z1,
                                                                    const float *__restrict__ gamma, const float *__restrict__ beta,
@@ -244,66 +244,7 @@ __global__ __launch_bounds__(kXcThreads) void xconv_bn_bwd_x_kernel(long long ro
                                                                    const float *__restrict__ grad_out, float *__restrict__ grad_x)
 {
     extern __shared__ float lds[];
-    constexpr int KK = K * K, STRIDE = KK + 1, QUADS = 16;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    float *mine = lds + static_cast<size_t>(w) * QUADS * STRIDE;
-    const long long wave = w + static_cast<long long>(blockIdx.x) * (kXcThreads / 64);
-    const long long nwaves = static_cast<long long>(gridDim.x) * (kXcThreads / 64);
-    const int c1 = c - c0;
-    for (long long r = wave; r < rows; r += nwaves) {
-        float acc[K][K];
-#pragma unroll
-        for (int i = 0; i < K; ++i)
-#pragma unroll
-            for (int j = 0; j < K; ++j) acc[i][j] = 0.f;
-        long long trow[K];   // the K table rows of this row's neighbours, once per row (wave-uniform)
-        const long long tbase = static_cast<long long>(static_cast<unsigned>(r) / static_cast<unsigned>(rows_per_cloud)) * n_src;
-#pragma unroll
-        for (int j = 0; j < K; ++j) trow[j] = tbase + idx[r * K + j];
-        for (int ch = lane; ch < c; ch += 64) {
-            float fv[K], g[M];
-            // selects, no branch around the loads.  c0 is a multiple of 64, so the 64 channels of a trip lie on one side of the
-            // split: the normalisation sits behind a wave-uniform branch and the gathered trips (most of them) pay nothing
-            const bool gathered = ch >= c0;
-            const float *base = gathered ? fts + (ch - c0) : z1 + ch;
-            const long long stride = gathered ? c1 : c0;
-#pragma unroll
-            for (int j = 0; j < K; ++j) fv[j] = base[(gathered ? trow[j] : r * K + j) * stride];
-            if (ch - lane < c0) {
-                const float ba = gamma[ch] * invstd[ch], bmu = mean[ch], bb = beta[ch];
-#pragma unroll
-                for (int j = 0; j < K; ++j) fv[j] = ba * (elu_stream(fv[j]) - bmu) + bb;
-            }
-            load_m<M>(grad_out, static_cast<size_t>(r * c + ch) * M, g);
-#pragma unroll
-            for (int k = 0; k < K; ++k) {
-                float a = 0.f;
-#pragma unroll
-                for (int m = 0; m < M; ++m) a = a + g[m] * wd[(static_cast<size_t>(k) * c + ch) * M + m];
-#pragma unroll
-                for (int j = 0; j < K; ++j) acc[k][j] = acc[k][j] + a * fv[j];
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < K; ++i)
-#pragma unroll
-            for (int j = 0; j < K; ++j) {
-                float v = acc[i][j];
-                v = v + __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0xb1, 0xf, 0xf, true));   // quad_perm [1,0,3,2]
-                v = v + __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x4e, 0xf, 0xf, true));   // quad_perm [2,3,0,1]
-                if ((lane & 3) == 0) mine[(lane >> 2) * STRIDE + i * K + j] = v;
-            }
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        for (int p = lane; p < KK; p += 64) {
-            float s = 0.f;
-#pragma unroll
-            for (int l = 0; l < QUADS; ++l) s = s + mine[l * STRIDE + p];
-            grad_x[r * KK + p] = s;
-        }
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-    }
+    xc_bwd_x_body<K, M, true, true>(rows, c, c0, z1, gamma, beta, mean, invstd, fts, idx, n_src, rows_per_cloud, wd, grad_out, grad_x, lds);
 }
 
 }  // namespace hf
@@ -410,7 +351,7 @@ HF_API int hf_xconv_depthwise_gather_bn_grad(int b, int n_src, int rows_per_clou
         if (rc != HF_OK) return rc;
     }
     if (grad_x) {
-        const size_t lds = sizeof(float) * (kXcThreads / 64) * 16 * (static_cast<size_t>(k) * k + 1);
+        const size_t lds = xc_bwd_x_lds_bytes(c, c0, k * m);   // the staged Wd and BatchNorm constants
 #define HF_XBN_BX(KK, MM)                                                                                              \
         hipLaunchKernelGGL((xconv_bn_bwd_x_kernel<KK, MM>), dim3(grid_for(rows, kXcThreads / 64)), dim3(kXcThreads), lds, st, rows, c, c0, z1, gamma, beta, mean, invstd, fts, idx, n_src, rows_per_cloud, wd, grad_out, grad_x);
         HF_XBN_DISPATCH(HF_XBN_BX)

@@ -195,6 +195,325 @@ __device__ __forceinline__ XcSource xc_source(int ch, int c, int c0, const float
     return s;
 }
 
+// ---- the two backward kernels: xconv_dw_bwd_x_kernel / xconv_bn_bwd_x_kernel and xconv_dw_bwd_fw_kernel / xconv_bn_bwd_fw_kernel ----
+// Each pair of twins is ONE body (`BN` switches the normalisation on load and the dgamma / dbeta sums on): the folded route and
+// the two-launch route give the same bits because they run the same code.
+//
+// Addresses: a row's tensors are reached through wave-uniform 64-bit bases (F + r K stride, grad_out + r c M, the K table rows of
+// the row's neighbours) formed on the scalar side once per row; a lane adds a 32-bit element offset (its channel, plus j * stride
+// inside the row's K x stride block of F), so the loads take their base from scalar registers and no 64-bit product is formed
+// per element.  The offset inside a row is below K c M, whatever the tensor's size: nothing here depends on xdw_offsets_fit.
+
+// the M floats of a (row, channel) pair at p; `arg` is the tensor's first element (a kernel argument), whose alignment decides
+// for every (row, channel) pair alike
+template <int M>
+__device__ __forceinline__ void xc_load_m(const float *arg, const float *p, float (&v)[M])
+{
+    if constexpr (M == 4) {
+        if ((reinterpret_cast<uintptr_t>(arg) & 15) == 0) {
+            const float4 t = *reinterpret_cast<const float4 *>(p);
+            v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+            return;
+        }
+    } else if constexpr (M == 2) {
+        if ((reinterpret_cast<uintptr_t>(arg) & 7) == 0) { const float2 t = *reinterpret_cast<const float2 *>(p); v[0] = t.x; v[1] = t.y; return; }
+    }
+#pragma unroll
+    for (int m = 0; m < M; ++m) v[m] = p[m];
+}
+
+// first table row of row r's cloud; `next` is the first row of the following cloud.  The division runs only when a wave's rows
+// cross into another cloud (rows ascend per wave, by any stride).
+struct XcCloudDiv {
+    long long first, next;
+    long long tbase;
+};
+
+__device__ __forceinline__ long long xc_tbase_div(XcCloudDiv &cl, long long r, int rows_per_cloud, int n_src)
+{
+    if (r >= cl.next || r < cl.first) {
+        const long long b = static_cast<long long>(static_cast<unsigned>(r) / static_cast<unsigned>(rows_per_cloud));
+        cl.first = b * rows_per_cloud;
+        cl.next = cl.first + rows_per_cloud;
+        cl.tbase = b * n_src;
+    }
+    return cl.tbase;
+}
+
+template <int CTRL>
+__device__ __forceinline__ float xc_dpp(float v)
+{
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true));
+}
+
+// Sum over the 64 lanes of N per-lane values v[OFF .. OFF + N), N = 64 or 16, by halving: in each step a lane hands half of its
+// values to a partner lane and adds the partner's other half to the half it keeps, so after log2(N) steps it holds ONE entry.
+//   N = 64: six steps; lane l ends with entry OFF + l summed over all 64 lanes, in v[OFF]
+//   N = 16: four steps leave entry OFF + (l >> 2) summed over 16 lanes; two adds across the quad finish it (the four lanes of a
+//           quad hold the same bits)
+// Partners: lane ^ 32 and lane ^ 16 by v_permlane32_swap / v_permlane16_swap (one swap and one add per pair of values, no select),
+// lane ^ 8 (row_ror:8), lane ^ 7 (row_half_mirror: the lanes of an 8-group pair up as 0-7, 1-6, 2-5, 3-4; the kept half goes by
+// bit 2), lane ^ 2 and lane ^ 1 (quad_perm) by DPP on the add, the half to keep picked by select.  A fixed tree: 6 adds on every
+// path, no LDS, no atomics, the same bits on every call.  63 (N = 64) / 17 (N = 16) adds per lane in all.
+template <int KK, int OFF, int N>
+__device__ __forceinline__ void xc_lane_fold(float (&v)[KK], int lane)
+{
+    static_assert(N == 64 || N == 16, "chunks of 64 or 16 entries");
+    typedef unsigned u2 __attribute__((ext_vector_type(2)));
+#pragma unroll
+    for (int i = 0; i < N / 2; ++i) {
+        const u2 s = __builtin_amdgcn_permlane32_swap(__float_as_uint(v[OFF + i]), __float_as_uint(v[OFF + i + N / 2]), false, false);
+        v[OFF + i] = __uint_as_float(s.x) + __uint_as_float(s.y);
+    }
+#pragma unroll
+    for (int i = 0; i < N / 4; ++i) {
+        const u2 s = __builtin_amdgcn_permlane16_swap(__float_as_uint(v[OFF + i]), __float_as_uint(v[OFF + i + N / 4]), false, false);
+        v[OFF + i] = __uint_as_float(s.x) + __uint_as_float(s.y);
+    }
+    const bool b3 = (lane & 8) != 0, b2 = (lane & 4) != 0;
+#pragma unroll
+    for (int i = 0; i < N / 8; ++i) {
+        const float lo = v[OFF + i], hi = v[OFF + i + N / 8];
+        v[OFF + i] = (b3 ? hi : lo) + xc_dpp<0x128>(b3 ? lo : hi);
+    }
+#pragma unroll
+    for (int i = 0; i < N / 16; ++i) {
+        const float lo = v[OFF + i], hi = v[OFF + i + N / 16];
+        v[OFF + i] = (b2 ? hi : lo) + xc_dpp<0x141>(b2 ? lo : hi);
+    }
+    if constexpr (N == 64) {
+        const bool b1 = (lane & 2) != 0, b0 = (lane & 1) != 0;
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const float lo = v[OFF + i], hi = v[OFF + i + 2];
+            v[OFF + i] = (b1 ? hi : lo) + xc_dpp<0x4e>(b1 ? lo : hi);   // quad_perm [2,3,0,1]
+        }
+        const float lo = v[OFF], hi = v[OFF + 1];
+        v[OFF] = (b0 ? hi : lo) + xc_dpp<0xb1>(b0 ? lo : hi);          // quad_perm [1,0,3,2]
+    } else {
+        v[OFF] = v[OFF] + xc_dpp<0x4e>(v[OFF]);
+        v[OFF] = v[OFF] + xc_dpp<0xb1>(v[OFF]);
+    }
+}
+
+// the K x K matrix of a row: every 64-entry chunk, then the 16-entry rest (K * K = 16, 64, 144)
+template <int KK, int OFF = 0>
+__device__ __forceinline__ void xc_store_dx(float (&acc)[KK], int lane, float *__restrict__ dst)
+{
+    static_assert((KK - OFF) % 64 == 0 || (KK - OFF) % 64 == 16, "K * K is a multiple of 64, or 16 more");
+    if constexpr (KK - OFF >= 64) {
+        xc_lane_fold<KK, OFF, 64>(acc, lane);
+        dst[OFF + lane] = acc[OFF];
+        xc_store_dx<KK, OFF + 64>(acc, lane, dst);
+    } else if constexpr (KK - OFF == 16) {
+        xc_lane_fold<KK, OFF, 16>(acc, lane);
+        if ((lane & 3) == 0) dst[OFF + (lane >> 2)] = acc[OFF];
+    }
+}
+
+// a float at a wave-uniform base plus a 32-bit byte offset per lane: the load takes the base from scalar registers
+__device__ __forceinline__ const float *xc_at(const float *base, unsigned byte_off)
+{
+    return reinterpret_cast<const float *>(reinterpret_cast<const char *>(base) + byte_off);
+}
+
+// LDS of xconv_*_bwd_x_kernel.  The block's K c M coefficients of Wd are staged once, as [trip][k M + m][64 lanes]: a trip reads its
+// K M values at compile-time offsets from one address per lane.  The BN twin stages gamma * invstd, mean and beta of its c0 lifted
+// channels behind them (c0 < c: at most 12 KB more).  Staged ("fast") while ceil(c / 64) K M <= kXcWdSlots (16 KB: every shipped
+// layer -- dec5 takes 40 slots, enc0 64; K = 8, M = 1 up to c = 512); past it the kernel reads the coefficients and the BatchNorm
+// constants from memory in every trip, as it did.
+constexpr int kXcWdSlots = 64;
+inline __host__ __device__ bool xc_bwd_x_fast(int c, int km) { return ((c + 63) >> 6) * km <= kXcWdSlots; }
+inline size_t xc_bwd_x_lds_bytes(int c, int c0_bn, int km)
+{
+    return xc_bwd_x_fast(c, km) ? sizeof(float) * (64 * static_cast<size_t>((c + 63) >> 6) * km + 3 * static_cast<size_t>(c0_bn)) : 0;
+}
+
+// One 64-channel trip's operands of a row, as loaded (the lifted values of the BN twin still un-normalised)
+template <int K, int M>
+struct XcTrip {
+    float fv[K], g[M];
+};
+
+// gradient w.r.t. X: dX[r][k][j] = sum_ch dF_X[r][k][ch] * F[r][j][ch], dF_X rebuilt from grad_out and Wd on the fly.
+// A wave per row (r = wave, wave + nwaves, ...), lanes walk the channels 64 at a time (a trip).  c0 is a multiple of 64 on the gather
+// entries, so a trip lies on one side of the lifted / gathered split: which side is decided once per trip on the scalar side.
+// The (row, trip) items of a wave run as one sequence: the next item's loads (the next trip's, or the next row's first trip's) are
+// issued before the current item's products -- always, in straight-line code, so that the wait counters stay exact: behind the
+// last item they fetch a valid row again and the values are dropped -- and the next row's neighbour indices are read at the
+// current row's first trip.
+// The accumulators start from the first trip's products (no zero fill; a lane with no channel in the first trip, c < 64, starts
+// from 0).  A lane past the last channel loads a clamped, valid channel and skips the products.
+// Rounding of an entry: M - 1 adds for dF_X, ceil(c / 64) - 1 across the trips, 6 across the lanes.
+template <int K, int M, bool GATHER, bool BN, bool FAST>
+__device__ __forceinline__ void xc_bwd_x_rows(long long rows, int c, int c0, const float *__restrict__ f,
+                                              const float *__restrict__ gamma, const float *__restrict__ beta,
+                                              const float *__restrict__ mean, const float *__restrict__ invstd,
+                                              const float *__restrict__ fts, const int *__restrict__ idx, int n_src, int rows_per_cloud,
+                                              const float *__restrict__ wd, const float *__restrict__ grad_out,
+                                              float *__restrict__ grad_x, float *lds)
+{
+    constexpr int KK = K * K, KM = K * M;
+    const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
+    const long long wave = w + static_cast<long long>(blockIdx.x) * (kXcThreads / 64);
+    const long long nwaves = static_cast<long long>(gridDim.x) * (kXcThreads / 64);
+    const int trips = (c + 63) >> 6, c1 = c - c0;
+    const unsigned lstride = GATHER ? c0 : c;
+    float *bnl = lds + trips * KM * 64;   // [3][c0]
+    if constexpr (FAST) {
+        for (int i = threadIdx.x; i < trips * KM * 64; i += kXcThreads) {
+            const int l = i & 63, s = i >> 6, t = s / KM, km = s - t * KM, ch = 64 * t + l;
+            lds[i] = ch < c ? wd[(static_cast<size_t>(km / M) * c + ch) * M + km % M] : 0.f;
+        }
+        if constexpr (BN) {
+            for (int i = threadIdx.x; i < c0; i += kXcThreads) {
+                bnl[i] = gamma[i] * invstd[i];
+                bnl[c0 + i] = mean[i];
+                bnl[2 * c0 + i] = beta[i];
+            }
+        }
+        __syncthreads();
+    }
+    if (wave >= rows) return;
+
+    int nidx[K];   // the neighbour indices of the wave's next row (wave-uniform)
+    auto load_idx = [&](long long r) {
+        if constexpr (GATHER) {
+            const long long rc = r < rows ? r : rows - 1;
+#pragma unroll
+            for (int j = 0; j < K; ++j) nidx[j] = idx[rc * K + j];
+        }
+    };
+    // what addresses a row, formed on the scalar side once per row (from nidx = the row's indices)
+    XcCloudDiv cl{0, 0, 0};
+    const float *fl = f, *go = grad_out, *tj[K];
+    auto set_row = [&](long long r) {
+        fl = f + r * K * static_cast<long long>(lstride);
+        go = grad_out + r * c * static_cast<long long>(M);
+        if constexpr (GATHER) {
+            const long long tb = xc_tbase_div(cl, r, rows_per_cloud, n_src);
+#pragma unroll
+            for (int j = 0; j < K; ++j) tj[j] = fts + static_cast<unsigned long long>(tb + nidx[j]) * static_cast<unsigned>(c1);
+        }
+    };
+    auto load_trip = [&](int t, XcTrip<K, M> &o) {
+        const int ch = 64 * t + lane;
+        const unsigned cc = ch < c ? ch : c - 1;
+        const float *bj[K];
+        unsigned sub = 0;
+        if (GATHER && 64 * t >= c0) {
+            sub = c0;
+#pragma unroll
+            for (int j = 0; j < K; ++j) bj[j] = tj[j];
+        } else {
+#pragma unroll
+            for (int j = 0; j < K; ++j) bj[j] = fl + j * static_cast<size_t>(lstride);
+        }
+        const unsigned off = (cc - sub) * 4u;
+#pragma unroll
+        for (int j = 0; j < K; ++j) o.fv[j] = *xc_at(bj[j], off);
+        xc_load_m<M>(grad_out, xc_at(go, cc * (4u * M)), o.g);
+    };
+
+    long long r = wave;
+    int t = 0;
+    load_idx(r);
+    set_row(r);
+    XcTrip<K, M> cur, nxt;
+    load_trip(0, cur);
+    static_assert(K % 2 == 0, "pairs of j");
+    f2 acc[K][K / 2];
+    for (;;) {
+        const bool last = t + 1 == trips;
+        const long long rn = last ? r + nwaves : r;
+        const int tn = last ? 0 : t + 1;
+        const bool more = rn < rows;
+        if (t == 0) load_idx(r + nwaves);
+        if (last) set_row(more ? rn : r);
+        load_trip(tn, nxt);
+        const int ch = 64 * t + lane;
+        const bool live = ch < c;
+        const unsigned cc = live ? ch : c - 1;
+        if (BN && 64 * t < c0) {   // z1 -> F_delta on the lifted trips
+            float ba, bmu, bb;
+            if constexpr (FAST) { ba = bnl[cc]; bmu = bnl[c0 + cc]; bb = bnl[2 * c0 + cc]; }
+            else { ba = gamma[cc] * invstd[cc]; bmu = mean[cc]; bb = beta[cc]; }
+#pragma unroll
+            for (int j = 0; j < K; ++j) cur.fv[j] = ba * (elu_stream(cur.fv[j]) - bmu) + bb;
+        }
+        // dF_X[k] = sum_m g[m] Wd[k][ch][m], on pairs of k (a packed product picks its half below, and no register of a pair
+        // belongs to a load still in flight)
+        f2 ap[K / 2];
+        {
+            const float *wt = lds + (t * KM * 64 + lane);
+            auto wv = [&](int k, int m) { return FAST ? wt[(k * M + m) * 64] : wd[(static_cast<size_t>(k) * c + cc) * M + m]; };
+#pragma unroll
+            for (int i = 0; i < K / 2; ++i) {
+                ap[i] = cur.g[0] * f2{wv(2 * i, 0), wv(2 * i + 1, 0)};
+#pragma unroll
+                for (int m = 1; m < M; ++m) ap[i] = ap[i] + cur.g[m] * f2{wv(2 * i, m), wv(2 * i + 1, m)};
+            }
+        }
+        // acc[k][j] (+)= a[k] * fv[j] on pairs of j: the K / 2 packed products of a row of the matrix, then its K / 2 packed adds, so
+        // that no add waits on the product issued just before it
+        f2 fp[K / 2];
+#pragma unroll
+        for (int i = 0; i < K / 2; ++i) fp[i] = f2{cur.fv[2 * i], cur.fv[2 * i + 1]};
+        if (t == 0) {
+            if (live) {
+#pragma unroll
+                for (int k = 0; k < K; ++k)
+#pragma unroll
+                    for (int i = 0; i < K / 2; ++i) acc[k][i] = ap[k / 2][k % 2] * fp[i];
+            } else {
+#pragma unroll
+                for (int k = 0; k < K; ++k)
+#pragma unroll
+                    for (int i = 0; i < K / 2; ++i) acc[k][i] = f2{0.f, 0.f};
+            }
+        } else if (live) {
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+                f2 p[K / 2];
+#pragma unroll
+                for (int i = 0; i < K / 2; ++i) p[i] = ap[k / 2][k % 2] * fp[i];
+                __builtin_amdgcn_sched_barrier(0);   // keep the row's products ahead of its adds
+#pragma unroll
+                for (int i = 0; i < K / 2; ++i) acc[k][i] = acc[k][i] + p[i];
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+        if (last) {
+            float flat[KK];
+#pragma unroll
+            for (int k = 0; k < K; ++k)
+#pragma unroll
+                for (int i = 0; i < K / 2; ++i) { flat[k * K + 2 * i] = acc[k][i].x; flat[k * K + 2 * i + 1] = acc[k][i].y; }
+            xc_store_dx<KK>(flat, lane, grad_x + r * KK);
+        }
+        if (!more) break;
+        cur = nxt;
+        r = rn;
+        t = tn;
+    }
+}
+
+// the body of xconv_dw_bwd_x_kernel (BN off) and xconv_bn_bwd_x_kernel (BN on): one wave-uniform switch between the staged form
+// and the one that reads Wd (and the BatchNorm constants) from memory, no further instantiation of the kernels
+template <int K, int M, bool GATHER, bool BN>
+__device__ __forceinline__ void xc_bwd_x_body(long long rows, int c, int c0, const float *__restrict__ f,
+                                              const float *__restrict__ gamma, const float *__restrict__ beta,
+                                              const float *__restrict__ mean, const float *__restrict__ invstd,
+                                              const float *__restrict__ fts, const int *__restrict__ idx, int n_src, int rows_per_cloud,
+                                              const float *__restrict__ wd, const float *__restrict__ grad_out,
+                                              float *__restrict__ grad_x, float *lds)
+{
+    if (xc_bwd_x_fast(c, K * M))
+        xc_bwd_x_rows<K, M, GATHER, BN, true>(rows, c, c0, f, gamma, beta, mean, invstd, fts, idx, n_src, rows_per_cloud, wd, grad_out, grad_x, lds);
+    else
+        xc_bwd_x_rows<K, M, GATHER, BN, false>(rows, c, c0, f, gamma, beta, mean, invstd, fts, idx, n_src, rows_per_cloud, wd, grad_out, grad_x, lds);
+}
+
 // ---- host side, defined in xconv.hip: the launch geometry of the fused kernels and the launcher of the table gradient ----
 // forward: channel pairs, 128 channels per block column, ~blocks_per_cu blocks per CU
 void xdw_pair_grid(long long rows, int c, dim3 &grid, int &rpb, int blocks_per_cu);
