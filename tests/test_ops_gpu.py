@@ -610,6 +610,60 @@ def test_oracle_crop(hf, oracle_mod):
     assert ne.any() and (~ne).any()
 
 
+@pytest.mark.parametrize("p,c,r,kind", [(5000, 256, 64, "one_unrolled_trip"), (5000, 260, 65, "unrolled_trip_and_tail"), (3000, 288, 512, "rcnn_size"),
+                                        (1, 20, 100, "one_point"), (15, 256, 64, "fewer_points_than_waves"), (5000, 20, 100, "crowded_wave"),
+                                        (5000, 256, 64, "crowded_wave")])
+def test_oracle_crop_copy_trips_and_short_clouds(hf, oracle_mod, p, c, r, kind):
+    """crop_kernel's feature copy moves four 16-byte pieces per thread and trip only when resize * channel / 4 >= 4 * 1024: (64, 256) is
+    exactly one such trip, (65, 260) one trip plus a tail whose (slot, piece) advance carries (1024 % 65 = 49 pieces), (512, 288) the
+    second stage's size.  The scan gives each of the 16 waves ceil(npts / 16) consecutive points: one point, fewer points than waves, and
+    a box with more than `resize` inside points in the first wave's range alone (the wave stops at `resize`, the later waves' lists are
+    never read).  Same exact comparison as test_oracle_crop."""
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+    from make_golden import box_3d_to_8co, random_boxes3d
+    rng = np.random.default_rng(p * 7 + c + r)
+    bsz, nb, waves, threads = 2, 24, 16, 1024
+    pts = kitti_uniform(rng, bsz, p)
+    pts[:, :, 1] = rng.uniform(0, 2, (bsz, p)).astype(np.float32)
+    fts = rng.standard_normal((bsz, p, c)).astype(np.float32)
+    inten = rng.uniform(-.5, .5, (bsz, p, 1)).astype(np.float32)
+    mask = rng.random((bsz, p)) < 0.2
+    b3 = random_boxes3d(rng, nb)
+    b3[:, 1] = 2.2
+    b3[:, 3:6] += rng.uniform(0, 25, (nb, 1)).astype(np.float32) * np.array([1, 1, 0.2], np.float32)
+    b3[:3, 3:6] = 0.01  # empty boxes
+    box_ind = rng.integers(0, bsz, nb).astype(np.int32)
+    centre = b3[:, :3] - np.array([0, 0.5, 0], np.float32) * b3[:, 5:6]
+    per = -(-p // waves)
+    if p <= waves:          # every point sits in the middle of one of the boxes 3 .. 10 of its frame
+        for f in range(bsz):
+            mine = [i for i in range(3, nb) if box_ind[i] == f][:8]
+            assert mine
+            pts[f] = centre[[mine[i % len(mine)] for i in range(p)]]
+    if kind == "crowded_wave":
+        assert per > r + 100
+        pts[box_ind[3], 10:r + 110] = centre[3] + rng.uniform(-0.2, 0.2, (r + 100, 3)).astype(np.float32)
+    boxes = box_3d_to_8co(b3)
+    res = hf.pc_crop_and_sample(dev(pts), dev(fts), dev(inten), dev(mask), dev(boxes), dev(box_ind), r)
+    want = oracle_mod.pc_crop_and_sample(pts, fts, inten, mask, boxes, box_ind, r)
+    for got, w, name in zip(res, want, ("pts", "fts", "int", "mask", "ind", "non_empty")):
+        assert np.array_equal(host(got), w), name
+    ne = want[5]
+    assert ne.any() and (~ne).any()
+    pieces = r * c // 4
+    if kind == "one_unrolled_trip":
+        assert pieces == 4 * threads
+    elif kind == "unrolled_trip_and_tail":
+        assert 4 * threads < pieces < 5 * threads and threads % (c // 4) != 0
+    elif kind == "rcnn_size":
+        assert pieces > 8 * threads and threads % (c // 4) != 0
+    elif kind == "crowded_wave":
+        assert (want[4][3] < per).all() and len(np.unique(want[4][3])) == r      # all of the box's slots come from the first wave's list
+    else:
+        assert p <= waves and (np.unique(want[4][ne]) < p).all()
+
+
 # ------------------------------------------------------------------ full BASELINE sizes
 def test_full_size_headline_ball_group(hf, oracle_mod):
     """B=8, N=16384, M=4096, K=32, kitti-uniform cloud, queries = gather(fps)"""
