@@ -11,6 +11,8 @@
 //           Fisher-Yates, one thread, <= R steps), then one thread per output slot;
 //   jitter  one thread per sampled RoI (fg: up to 10 tries, bg: 1 try), the IoU against its ASSIGNED gt.
 // Random numbers are a counter hash of (base seed, call number, frame, slot, draw); they do not follow NumPy's stream.
+// Pinned by tests/test_sampler_abi.py against the NumPy restatement of tests/sampler_cases.py: every draw (the hash is pure
+// integer arithmetic), every rule and branch, rois under 'single' / 'multiple' bit for bit, the 3D IoU against an fp64 clip.
 #include <math.h>
 
 #include "bev_common.h"

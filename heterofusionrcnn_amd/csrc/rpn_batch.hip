@@ -16,6 +16,12 @@
 //                      geometry, fp32 weights, rounded to nearest).
 // Random numbers are a counter hash of (seed, call number, frame, purpose, index); they do not follow NumPy's stream.  Every
 // output element has exactly one writer and no float is accumulated with atomics: a given rng_state gives the same bits.
+// tests/test_sampler_abi.py holds every draw, slot and pixel to the NumPy restatement of tests/sampler_cases.py.
+// The keyed permutation (4 Feistel rounds, round function masked to half the even bit count, cycle walk) is measurably
+// non-uniform on tiny domains: over 20 000 keys a host prototype is 11 sigma off in single-element inclusion counts at
+// n = 5 and has a position chi-square of 580 against 361 degrees of freedom at n = 20; from n = 64 up it is
+// indistinguishable from uniform (4034 against 3969 at n = 64, 89 858 against 89 401 at n = 300).  The training path
+// permutes thousands of points; changing the hash would change every seeded run and the exported hand-off files.
 #include <math.h>
 
 #include "hf_common.h"

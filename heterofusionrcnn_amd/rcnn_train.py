@@ -13,8 +13,9 @@ rcnn_loss is the op-by-op torch restatement (runs on CPU); rcnn_loss_fused is th
 (hf_rcnn_loss_fwd / _bwd in csrc/glue.hip).  RcnnTrainer chains targets -> RcnnModel -> encoding -> loss; rcnn_train_loss is
 its loss_fn for graph_step.TrainStep.
 
-Parity is unpinned against reference outputs (TensorFlow and shapely are not importable, and the random streams differ):
-what the tests pin is the sampling rules, the IoU arithmetic and the loss graph.
+Parity is unpinned against reference outputs (TensorFlow and shapely are not importable, and the random streams differ).
+What the tests pin: the target layer draw for draw against a NumPy restatement of its counter hash, rules and jitter, its
+3D IoU against an fp64 clip (tests/sampler_cases.py, tests/test_sampler_abi.py), and the loss graph.
 """
 from dataclasses import dataclass
 from typing import Tuple

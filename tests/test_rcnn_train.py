@@ -3,11 +3,14 @@ modules.box3d_iou and a NumPy restatement of kitti_dataset.py:545-680 (selection
 RCNN loss against the op-by-op torch form, and the RCNN train step at the config's own sizes, eager and replayed.
 The random streams differ from NumPy's: parity is in the rules, the IoU arithmetic and the loss graph."""
 import os
+import sys
 
 import numpy as np
 import pytest
 import torch
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import sampler_cases as sc  # noqa: E402
 from heterofusionrcnn_amd import kitti_io, modules
 from heterofusionrcnn_amd import rcnn_train as RT
 from heterofusionrcnn_amd.rcnn import RcnnConfig
@@ -207,49 +210,8 @@ def test_sampling_counts_hard_and_easy_when_plentiful():
 
 
 # ------------------------------------------------------------------------------------------------ 3. jitter
-def _np_convex_iou(a, b):
-    """float64 3D IoU with a Sutherland-Hodgman clip of the two rotated BEV rectangles (corners as bev_iou's rotate_around_center)"""
-    def corners(x):
-        c, s = np.cos(x[6]), np.sin(x[6])
-        out = []
-        for dx, dz in ((-1, -1), (1, -1), (1, 1), (-1, 1)):
-            px, pz = dx * x[3] / 2, dz * x[4] / 2
-            out.append((px * c + pz * s + x[0], -px * s + pz * c + x[2]))
-        return out
-
-    def clip(poly, p1, p2):
-        out = []
-        side = lambda q: (p2[0] - p1[0]) * (q[1] - p1[1]) - (p2[1] - p1[1]) * (q[0] - p1[0])
-        for i in range(len(poly)):
-            cur, prv = poly[i], poly[i - 1]
-            sc, sp = side(cur), side(prv)
-            if sc >= 0:
-                if sp < 0:
-                    t = sp / (sp - sc)
-                    out.append((prv[0] + t * (cur[0] - prv[0]), prv[1] + t * (cur[1] - prv[1])))
-                out.append(cur)
-            elif sp >= 0:
-                t = sp / (sp - sc)
-                out.append((prv[0] + t * (cur[0] - prv[0]), prv[1] + t * (cur[1] - prv[1])))
-        return out
-
-    def area(poly):
-        return 0.5 * abs(sum(poly[i - 1][0] * poly[i][1] - poly[i][0] * poly[i - 1][1] for i in range(len(poly))))
-
-    ca, cb = corners(a), corners(b)
-    if area(ca) > 0 and sum(ca[i - 1][0] * ca[i][1] - ca[i][0] * ca[i - 1][1] for i in range(4)) < 0:
-        ca = ca[::-1]
-    if sum(cb[i - 1][0] * cb[i][1] - cb[i][0] * cb[i - 1][1] for i in range(4)) < 0:
-        cb = cb[::-1]
-    poly = list(ca)
-    for i in range(4):
-        if not poly:
-            break
-        poly = clip(poly, cb[i], cb[(i + 1) % 4])
-    inter = area(poly) if len(poly) >= 3 else 0.0
-    oh = max(min(a[1], b[1]) - max(a[1] - a[5], b[1] - b[5]), 0.0)
-    o3 = inter * oh
-    return o3 / max(a[3] * a[4] * a[5] + b[3] * b[4] * b[5] - o3, 1e-7)
+# the float64 3D IoU (a Sutherland-Hodgman clip of the two rotated BEV rectangles) lives in tests/sampler_cases.py
+_np_convex_iou = sc.ref_iou3d
 
 
 def test_jitter_multiple():
