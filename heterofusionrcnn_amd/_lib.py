@@ -113,6 +113,9 @@ _SIGNATURES = {
     "hf_linear_bf16_wgrad": [ctypes.c_longlong, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp],
     "hf_project_gather": [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     "hf_project_gather_grad": [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
+    "hf_roi_image_boxes": [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
+    "hf_crop_and_resize": [_i, _i, _i, _i, ctypes.c_longlong, _i, _i, _vp, _vp, _vp, _f, _vp, _vp],
+    "hf_crop_and_resize_grad": [_i, _i, _i, _i, ctypes.c_longlong, _i, _i, _vp, _vp, _vp, _vp, _vp],
     "hf_fuse_concat": [ctypes.c_longlong, _i, _i, _vp, _vp, _vp, _vp, _vp],
     "hf_fuse_concat_grad": [ctypes.c_longlong, _i, _i, _vp, _vp, _vp, _vp, _vp],
     "hf_rpn_loss_workspace": [],

@@ -116,10 +116,48 @@ def fuse_point_image_features(pc_fts, proj_img_fts, method="concat", div=2.0, ma
     return torch.cat([pc_fts, proj_img_fts], dim=-1)
 
 
+def _on_device_f32(*tensors):
+    """every tensor lives on the GPU as fp32: the condition under which the RoI image ops go to their kernels"""
+    return all(t.is_cuda and t.dtype == torch.float32 for t in tensors)
+
+
+def _roi_image_boxes(boxes_3d, calib, image_hw, px, norm, yxyx):
+    """one hf_roi_image_boxes launch; px / norm / yxyx choose the outputs -> (B*n,4) tensors or None"""
+    b, n, _ = boxes_3d.shape
+    require(boxes_3d.shape[2] == 7 and calib.shape == (b, 3, 4), "RoI image boxes expect (B,n,7) boxes and (B,3,4) calib")
+    boxes_3d, calib = boxes_3d.detach().contiguous(), calib.detach().contiguous()
+    outs = [torch.empty((b * n, 4), dtype=torch.float32, device=boxes_3d.device) if want else None for want in (px, norm, yxyx)]
+    h, w = image_hw
+    check(_lib.lib().hf_roi_image_boxes(b, n, int(h), int(w), ptr(boxes_3d), ptr(calib), ptr(outs[0]), ptr(outs[1]), ptr(outs[2]),
+                                        stream_ptr()), "roi_image_boxes")
+    return outs
+
+
+def roi_image_boxes(proposals, calib, image_hw):
+    """rcnn_model.py:433-452 in one launch: proposals (B,n,7), calib (B,3,4), image_hw = (h, w) -> (B*n,4) [y1,x1,y2,x2], the
+    projected rectangles normalised by the image size, in the column order tf.image.crop_and_resize takes.  No gradient
+    (proposals are inputs of the stage).  Host tensors and other dtypes take project_boxes_to_image and a reorder."""
+    if _on_device_f32(proposals, calib):
+        return _roi_image_boxes(proposals, calib, image_hw, False, False, True)[2]
+    xyxy = project_boxes_to_image(proposals, calib, image_hw)[1].reshape(-1, 4)
+    return torch.stack([xyxy[:, 1], xyxy[:, 0], xyxy[:, 3], xyxy[:, 2]], dim=1)
+
+
 def project_boxes_to_image(boxes_3d, calib, image_hw):
     """hf/core/projection.py:35-96 (tf_project_to_image_space) for every frame at once: boxes_3d (B,n,7) [x,y,z,l,w,h,ry]
     (y = bottom), calib (B,3,4), image_hw = (h, w) -> (corners (B,n,4) [x1,y1,x2,y2] in pixels, the same normalised by
-    [w,h,w,h]): the 8 corners of a box are projected and the 2-D box is their bounding rectangle."""
+    [w,h,w,h]): the 8 corners of a box are projected and the 2-D box is their bounding rectangle.  fp32 tensors on the
+    device: one hf_roi_image_boxes launch (no gradient); anything else, or boxes that ask for a gradient: the tensor form."""
+    wants_grad = torch.is_grad_enabled() and (boxes_3d.requires_grad or calib.requires_grad)
+    if _on_device_f32(boxes_3d, calib) and not wants_grad:
+        b, n, _ = boxes_3d.shape
+        box, norm, _ = _roi_image_boxes(boxes_3d, calib, image_hw, True, True, False)
+        return box.view(b, n, 4), norm.view(b, n, 4)
+    return _project_boxes_to_image_tensor(boxes_3d, calib, image_hw)
+
+
+def _project_boxes_to_image_tensor(boxes_3d, calib, image_hw):
+    """project_boxes_to_image out of stock tensor operations: the host form, and the baseline of scripts/roi_image_timing.py"""
     from .modules import box_3d_to_box_8co
     b, n, _ = boxes_3d.shape
     corners = box_3d_to_box_8co(boxes_3d.reshape(-1, 7)).transpose(1, 2).reshape(b, n * 8, 3)    # (B, n*8, 3)
@@ -136,12 +174,50 @@ def project_boxes_to_image(boxes_3d, calib, image_hw):
     return box, box / denom
 
 
+class _CropAndResize(torch.autograd.Function):
+    """hf_crop_and_resize (+ grad): gradient w.r.t. the image only; the backward recomputes the sample coordinates"""
+
+    @staticmethod
+    def forward(ctx, img_fts, boxes, box_ind, crop, extrapolation):
+        b, h, w, c = img_fts.shape
+        n = boxes.shape[0]
+        out = torch.empty((n, crop, crop, c), dtype=torch.float32, device=img_fts.device)
+        check(_lib.lib().hf_crop_and_resize(b, h, w, c, n, crop, crop, ptr(img_fts), ptr(boxes), ptr(box_ind), extrapolation,
+                                            ptr(out), stream_ptr()), "crop_and_resize")
+        ctx.save_for_backward(boxes, box_ind)
+        ctx.dims = (b, h, w, c, n, crop)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        boxes, box_ind = ctx.saved_tensors
+        b, h, w, c, n, crop = ctx.dims
+        grad_out = grad_out.contiguous()
+        g = torch.empty((b, h, w, c), dtype=torch.float32, device=grad_out.device)
+        check(_lib.lib().hf_crop_and_resize_grad(b, h, w, c, n, crop, crop, ptr(grad_out), ptr(boxes), ptr(box_ind), ptr(g),
+                                                 stream_ptr()), "crop_and_resize_grad")
+        return g, None, None, None, None
+
+
 def image_crop_and_resize(img_fts, boxes_norm_yxyx, box_ind, crop_size, extrapolation_value=0.0):
     """tf.image.crop_and_resize (bilinear) as the RCNN uses it on the image feature map (rcnn_model.py:494-500): img_fts
     (B,H,W,C), boxes (N,4) [y1,x1,y2,x2] normalised, box_ind (N) -> (N,crop,crop,C).  Sample i of a crop sits at
     y1 (H-1) + i (y2-y1)(H-1)/(crop-1); a sample outside [0, H-1] x [0, W-1] takes the extrapolation value.
-    Plain torch gathers (N * crop^2 * 4 rows of C floats); TensorFlow is not importable here: parity unpinned beyond the
-    documented formula (tests/test_rcnn.py checks it against a loop)."""
+    fp32 tensors on the device: one HIP kernel each way (csrc/roi_image.hip), gradient w.r.t. img_fts only, and a row whose
+    rectangle is not finite adds nothing to it.  Host tensors and other dtypes: the tensor form below.  TensorFlow is not
+    importable here: parity unpinned beyond the documented formula (tests/test_rcnn.py checks the tensor form against a
+    loop, tests/roi_image_cases.py restates it for the kernels)."""
+    if _on_device_f32(img_fts, boxes_norm_yxyx) and box_ind.is_cuda:
+        require(img_fts.dim() == 4 and boxes_norm_yxyx.dim() == 2 and boxes_norm_yxyx.shape[1] == 4
+                and box_ind.shape == boxes_norm_yxyx.shape[:1], "image_crop_and_resize expects (B,H,W,C), (N,4) boxes and (N) box_ind")
+        return _CropAndResize.apply(img_fts.contiguous(), boxes_norm_yxyx.detach().contiguous(),
+                                    box_ind.detach().to(torch.int32).contiguous(), int(crop_size), float(extrapolation_value))
+    return _image_crop_and_resize_tensor(img_fts, boxes_norm_yxyx, box_ind, crop_size, extrapolation_value)
+
+
+def _image_crop_and_resize_tensor(img_fts, boxes_norm_yxyx, box_ind, crop_size, extrapolation_value=0.0):
+    """image_crop_and_resize as plain torch gathers (N * crop^2 * 4 rows of C floats): the host form, and the baseline of
+    scripts/roi_image_timing.py"""
     b, h, w, c = img_fts.shape
     n = boxes_norm_yxyx.shape[0]
     ch = cw = int(crop_size)

@@ -28,7 +28,7 @@ import torch.nn.functional as F
 
 from . import box_codec, modules
 from .cropping import pc_crop_and_sample
-from .fusion import image_crop_and_resize, path_drop_masks, project_boxes_to_image
+from .fusion import fuse_point_image_features, image_crop_and_resize, path_drop_masks, roi_image_boxes
 from .pointcnn import Dense, PointCnnBackbone, PointCnnConfig
 
 
@@ -153,10 +153,8 @@ class RcnnModel(nn.Module):
         b, n, _ = proposals.shape
         flat = proposals.reshape(-1, 7).contiguous()
         box_ind = torch.arange(b, device=xyz.device, dtype=torch.int32).repeat_interleave(n)
-        _, box2d_norm = project_boxes_to_image(proposals, calib, cfg.img_hw)                 # (B,n,4) [x1,y1,x2,y2]
-        xyxy = box2d_norm.reshape(-1, 4)
-        # reorder_projected_boxes; column copies, not a list index (that would copy an index tensor from the host: not capturable)
-        yxyx = torch.stack([xyxy[:, 1], xyxy[:, 0], xyxy[:, 3], xyxy[:, 2]], dim=1)
+        # projection + reorder_projected_boxes in one launch, the crop below in a second: the image half of the pooling
+        yxyx = roi_image_boxes(proposals, calib, cfg.img_hw)                                 # (N,4) [y1,x1,y2,x2] normalised
         boxes8 = modules.box_3d_to_box_8co(expand_proposals(flat, cfg.pooling_context_length)).contiguous()
         crop_pts, crop_fts, crop_int, crop_mask, crop_ind, non_empty = pc_crop_and_sample(
             xyz, rpn_fts.contiguous(), intensity, fg_mask, boxes8, box_ind, cfg.roi_crop_size)
@@ -185,13 +183,15 @@ class RcnnModel(nn.Module):
         merged = torch.cat([pool["crop_fts"], self.mlp(local)], dim=-1)                      # (N,R,2C)
         pc_rois = self.encoder(pts_ct, merged)                                               # (N,r,C')
         img_rois = pool["img_rois"]
+        masks = None
         if self.training and tuple(cfg.path_drop) != (1.0, 1.0):
             masks = path_drop_masks(cfg.path_drop[0], cfg.path_drop[1], torch.rand(3, device=xyz.device))
-            pc_rois, img_rois = pc_rois * masks[0], img_rois * masks[1]
         nroi = pc_rois.shape[0]
         if cfg.fusion == "flat_concat":
-            fuse = torch.cat([pc_rois.reshape(nroi, -1), img_rois.reshape(nroi, -1)], dim=-1)
+            fuse = fuse_point_image_features(pc_rois.reshape(nroi, -1), img_rois.reshape(nroi, -1), "concat", masks=masks)
         else:
+            if masks is not None:
+                pc_rois, img_rois = pc_rois * masks[0], img_rois * masks[1]
             fuse = torch.cat([pc_rois.mean(dim=1), img_rois.mean(dim=(1, 2))], dim=-1)
         cls_logits = self.cls_logits(self.cls_fc(fuse))
         reg = self.reg_out(self.reg_fc(fuse)).reshape(nroi, cfg.num_classes, cfg.head_width)

@@ -497,6 +497,29 @@ int hf_project_gather(int b, int p, int h, int w, int c, const float *pts, const
                       int *pix, hf_stream_t stream);
 int hf_project_gather_grad(int b, int p, int h, int w, int c, const float *grad_out, const int *pix, float *grad_img,
                            hf_stream_t stream);
+/* The image half of the second stage's RoI pooling (hf/core/models/rcnn_model.py:433-454, 494-501), csrc/roi_image.hip.
+ * hf_roi_image_boxes: hf/core/projection.py:35-96 (tf_project_to_image_space).  boxes3d (b,n,7) [x,y,z,l,w,h,ry], y at the
+ * bottom; calib (b,3,4) P2; h, w the image size the rectangle is normalised by.  The eight corners times P2, divided by depth,
+ * min and max over the corners: box_px (b*n,4) [x1,y1,x2,y2] in pixels, box_norm the same divided by [w,h,w,h], box_yxyx
+ * box_norm as [y1,x1,y2,x2] (anchor_projector.reorder_projected_boxes); each output may be NULL.  No clipping, no special case
+ * for corners behind the camera; a NaN corner gives a NaN rectangle.  b*n <= INT_MAX / 8.
+ * hf_crop_and_resize: tf.image.crop_and_resize (bilinear).  img (b,h,w,c), boxes_yxyx (n,4) normalised, box_ind (n) ->
+ * out (n,crop_h,crop_w,c).  Sample i sits at in_y = y1 (h-1) + i ((y2-y1) (h-1) / (crop_h-1)), or 0.5 (y1+y2) (h-1) when
+ * crop_h == 1 (the same in x), in fp32 in this order.  Inside 0 <= in_y <= h-1 and 0 <= in_x <= w-1: top = tl + (tr-tl) lx,
+ * bot = bl + (br-bl) lx, out = top + (bot-top) ly over the floor / ceil neighbours; outside (a NaN is outside), and in every
+ * row whose box_ind is not in [0,b): `extrapolation`.
+ * hf_crop_and_resize_grad: grad_img (b,h,w,c), zero-filled here (by a kernel on the stream), += the four weighted shares of every in-range sample of
+ * grad_out (n,crop_h,crop_w,c), by fp32 atomics (the sum order is not fixed); samples outside and rows with a bad box_ind add
+ * nothing.  The coordinates are recomputed as in the forward; there is no gradient w.r.t. the boxes.
+ * All three: no workspace, no host round trip, capturable.  n == 0 or b == 0 launch nothing (the gradient still zero-fills a
+ * non-empty grad_img).  HF_EINVAL: a negative size, h, w, c or crop < 1, a NULL required pointer of a non-empty tensor, a
+ * tensor of more than LLONG_MAX / 4 elements. */
+int hf_roi_image_boxes(int b, int n, int h, int w, const float *boxes3d, const float *calib, float *box_px, float *box_norm,
+                       float *box_yxyx, hf_stream_t stream);
+int hf_crop_and_resize(int b, int h, int w, int c, long long n, int crop_h, int crop_w, const float *img,
+                       const float *boxes_yxyx, const int *box_ind, float extrapolation, float *out, hf_stream_t stream);
+int hf_crop_and_resize_grad(int b, int h, int w, int c, long long n, int crop_h, int crop_w, const float *grad_out,
+                            const float *boxes_yxyx, const int *box_ind, float *grad_img, hf_stream_t stream);
 /* The 'concat' fusion of the RPN / RCNN with its path drop (hf/core/models/rpn_model.py:515-546, rcnn_model.py:560-590):
  * out (rows, c1+c2) = [a * masks[0] | b * masks[1]]; masks = two floats ON THE DEVICE (this step's path-drop decision,
  * create_path_drop_masks, rpn_model.py:1130-1193) or NULL for (1, 1).  _grad: grad_a = grad_out[:, :c1] * masks[0],
