@@ -10,6 +10,9 @@
 // step (batched-GEMM kernels at ~1.4 ms per layer, strided copies around every einsum).  Both are memory-bound by
 // nature: every operand is read once and every result written once, the K*K (or K*M) coefficients of a point live in
 // scalar registers / LDS.  fp32, multiply then add in index order (no FMA contraction), like the rest of the library.
+//
+// The two-kernel entries, the table gradient and every launcher live here.  The fused forward and F / Wd gradient kernels and the
+// body of the X gradient are the templates of xconv_common.h: this file instantiates them with BN off, xconv_bn.hip with BN on.
 #include "xconv_common.h"
 
 namespace hf {
@@ -303,169 +306,8 @@ __global__ __launch_bounds__(kXcThreads) void depthwise_dw_kernel(long long rows
     }
 }
 
-// ---------------------------------------------------------------------------------------------------------------
-// X-transform apply and the depthwise step of the separable convolution in one pass (pointcnn.py:133-140):
-//   out[r][ch*M + m] = sum_k (sum_j X[r][k][j] * F[r][j][ch]) * Wd[k][ch][m]
-// F_X = X x F_* (rows x K x C, the largest tensor of an X-Conv: 1.3 GB for the decoder layers at 131 072 points) is never
-// written: the K products of a (row, channel) stay in registers.  Same multiply / add order as hf_xconv_apply followed by
-// hf_depthwise_k, so the results are bit-identical to the two-kernel route.
-// Mapping: a lane owns ONE channel for the whole kernel (its K x M depthwise weights live in registers, blockIdx.y picks
-// the 64-channel chunk), the four waves of a block walk the rows of a chunk; the row's K x K matrix is wave-uniform.
-//
-// GATHER: F_* = [F_delta | F gathered] (pointcnn.py:124-127 concat of the lifted coordinates with the neighbours' features) is
-// not materialised either: channels below c0 come from `f` = F_delta (rows x K x c0), the others from the feature table
-// `fts` (clouds x n_src rows x c - c0) through the neighbour table `idx` (rows x K, indices inside the row's cloud).  c0 is a multiple of 64, so a block's 64-channel
-// chunk lies on one side.  The gathered rows (K x the table, 1.1 GB for the last decoder layers) were written by
-// group_point and read back here; now the table (134 MB, L2 / MALL resident) is read in place.
-// Channel pairs: a lane owns channels (ch, ch + 1), ch even, so a wave covers 128 channels and every product runs as ONE packed
-// f32 op on the pair (v_pk_mul_f32 / v_pk_add_f32 round each half like the scalar op; -ffp-contract=off keeps them unfused).
-// Packing runs across channels only: every output element keeps its own multiply-then-add sequence in index order.
-template <int K, int M, bool GATHER, bool V2>
-__global__ __launch_bounds__(kXcThreads) void xconv_dw_fwd_kernel(long long rows, int c, int c0, int rows_per_block,
-                                                                 const float *__restrict__ x, const float *__restrict__ f,
-                                                                 const float *__restrict__ fts, const int *__restrict__ idx, int n_src,
-                                                                 int rows_per_cloud, const float *__restrict__ wd, float *__restrict__ out)
-{
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
-    const int ch = blockIdx.y * 128 + 2 * lane;
-    const XcPair src = xc_pair(ch, c, c0, f, fts, GATHER);
-    const int cw = src.live ? ch : (c - 1) & ~1;
-    f2 w[K][M];
-#pragma unroll
-    for (int k = 0; k < K; ++k)
-#pragma unroll
-        for (int m = 0; m < M; ++m) w[k][m] = f2{wd[(static_cast<size_t>(k) * c + cw) * M + m], wd[(static_cast<size_t>(k) * c + cw + src.hi) * M + m]};
-    const unsigned lstride = GATHER ? c0 : c, c1 = c - c0;
-    const long long r0 = static_cast<long long>(blockIdx.x) * rows_per_block;
-    const long long r1 = r0 + rows_per_block < rows ? r0 + rows_per_block : rows;
-    __shared__ float xs[kXcThreads / 64][kXcRows][K * K];
-    XcCloud cl = xc_cloud(r0, rows_per_cloud, n_src);
-    for (long long rb = r0 + wave; rb < r1; rb += 4 * kXcRows) {
-        f2 fv[kXcRows][K];
-        long long rr[kXcRows];
-#pragma unroll
-        for (int i = 0; i < kXcRows; ++i) rr[i] = rb + 4 * i < r1 ? rb + 4 * i : r1 - 1;
-        XcXRows<K> xrow;
-        xrow.load(x, rr, lane);
-#pragma unroll
-        for (int i = 0; i < kXcRows; ++i) {
-            const unsigned tb = GATHER ? xc_tbase(cl, rr[i], rows_per_cloud, n_src) : 0u;
-            xc_gather_row<K, GATHER, V2>(src, rr[i], tb, idx, lstride, c1, fv[i]);
-        }
-        xrow.stage(xs[wave], lane);
-#pragma unroll
-        for (int i = 0; i < kXcRows; ++i) {
-            if (rb + 4 * i >= r1) break;
-            const float *xr = xs[wave][i];
-            f2 o[M];
-#pragma unroll
-            for (int m = 0; m < M; ++m) o[m] = f2{0.f, 0.f};
-#pragma unroll
-            for (int k = 0; k < K; ++k) {
-                f2 t = xr[k * K] * fv[i][0];
-#pragma unroll
-                for (int j = 1; j < K; ++j) t = t + xr[k * K + j] * fv[i][j];
-#pragma unroll
-                for (int m = 0; m < M; ++m) o[m] = o[m] + t * w[k][m];
-            }
-            if (src.live) st_pair_m<M, V2>(out + static_cast<size_t>(rr[i] * c + ch) * M, src.hi_live, o);
-        }
-    }
-}
-
-// gradients w.r.t. F and Wd, same mapping: per (row, channel) the gradient of F_X (K values), F_X itself (recomputed) and
-// the K input gradients stay in registers; a lane sums its channel's K x M weight gradients over its rows and adds them
-// to grad_wd with one atomic per coefficient (grad_wd zero-filled by the entry point)
-// GATHER: grad_f is the gradient of F_delta only (rows x K x c0); the gathered channels' gradient is either written to
-// grad_gathered (rows x K x c1, then summed per table row by hf_group_point_grad_gather) or rebuilt per table row by
-// xconv_dw_bwd_fts_kernel
-template <int K, int M, bool GATHER>
-__global__ __launch_bounds__(kXcThreads) void xconv_dw_bwd_fw_kernel(long long rows, int c, int c0, int rows_per_block,
-                                                                    const float *__restrict__ x, const float *__restrict__ f,
-                                                                    const float *__restrict__ fts, const int *__restrict__ idx, int n_src,
-                                                                    int rows_per_cloud, const float *__restrict__ wd,
-                                                                    const float *__restrict__ grad_out, float *__restrict__ grad_f,
-                                                                    float *__restrict__ grad_gathered, float *__restrict__ grad_wd,
-                                                                    float *__restrict__ wd_partial)
-{
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
-    const int ch = blockIdx.y * 64 + lane;
-    const bool live = ch < c;
-    const XcSource src = xc_source(live ? ch : blockIdx.y * 64, c, c0, f, fts, GATHER ? idx : nullptr);
-    if (GATHER && src.gathered && !grad_wd && !grad_gathered) return;   // nothing of this chunk is asked for (no partial to write either)
-    float w[K][M], gw[K][M];
-#pragma unroll
-    for (int k = 0; k < K; ++k)
-#pragma unroll
-        for (int m = 0; m < M; ++m) { w[k][m] = live ? wd[(static_cast<size_t>(k) * c + ch) * M + m] : 0.f; gw[k][m] = 0.f; }
-    const long long r0 = static_cast<long long>(blockIdx.x) * rows_per_block;
-    const long long r1 = r0 + rows_per_block < rows ? r0 + rows_per_block : rows;
-    for (long long r = r0 + wave; r < r1; r += kXcThreads / 64) {
-        const float *xr = x + r * (K * K);
-        float fv[K], g[M], gfx[K];
-        const long long tbase = (GATHER && src.gathered) ? static_cast<long long>(static_cast<unsigned>(r) / static_cast<unsigned>(rows_per_cloud)) * n_src : 0;
-#pragma unroll
-        for (int j = 0; j < K; ++j) {
-            const long long srow = (GATHER && src.gathered) ? tbase + idx[r * K + j] : r * K + j;
-            fv[j] = live ? src.base[srow * src.stride] : 0.f;
-        }
-        load_m<M>(grad_out, static_cast<size_t>(r * c + (live ? ch : 0)) * M, g);
-        if (!live) {
-#pragma unroll
-            for (int m = 0; m < M; ++m) g[m] = 0.f;
-        }
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            float a = 0.f;
-#pragma unroll
-            for (int m = 0; m < M; ++m) a = a + g[m] * w[k][m];          // = hf_depthwise_k_grad's dx
-            gfx[k] = a;
-            float t = xr[k * K] * fv[0];                                  // F_X recomputed
-#pragma unroll
-            for (int j = 1; j < K; ++j) t = t + xr[k * K + j] * fv[j];
-#pragma unroll
-            for (int m = 0; m < M; ++m) gw[k][m] = gw[k][m] + t * g[m];   // = hf_depthwise_k_grad's dw
-        }
-        float *gdst = (GATHER && src.gathered) ? (grad_gathered ? grad_gathered + (ch - c0) : nullptr) : (grad_f ? grad_f + ch : nullptr);
-        if (live && gdst) {
-#pragma unroll
-            for (int j = 0; j < K; ++j) {
-                float a = xr[j] * gfx[0];                                  // = hf_xconv_apply_grad's dF (X transposed)
-#pragma unroll
-                for (int k = 1; k < K; ++k) a = a + xr[k * K + j] * gfx[k];
-                gdst[(r * K + j) * src.stride] = a;
-            }
-        }
-    }
-    if (grad_wd) {
-        // the waves of a block meet in LDS first: one global atomic per coefficient and BLOCK (per wave it was 8.4 M atomics on
-        // 2080 addresses for the first encoder layer: 870 us for 140 us of memory traffic)
-        // The waves take turns, wave 0 first: a fixed order of adds (LDS atomics left it to the order the waves arrived in), so with
-        // wd_partial grad_wd is the same bits on every call.  The slots of dead lanes are neither written nor read.
-        __shared__ float red[K * M][64];
-        for (int wv = 0; wv < kXcThreads / 64; ++wv) {
-            if (wave == wv && live) {
-#pragma unroll
-                for (int k = 0; k < K; ++k)
-#pragma unroll
-                    for (int m = 0; m < M; ++m) red[k * M + m][lane] = wv == 0 ? gw[k][m] : red[k * M + m][lane] + gw[k][m];
-            }
-            __syncthreads();
-        }
-        // wd_partial: the row chunks' sums are written out (wd_partial[row chunk][K*c*M]) and added in a fixed order by a second
-        // kernel; else one global atomic per coefficient and block on grad_wd (zero-filled by the entry point)
-        float *mine = wd_partial ? wd_partial + static_cast<size_t>(blockIdx.x) * K * c * M : nullptr;
-        for (int i = threadIdx.x; i < K * M * 64; i += kXcThreads) {
-            const int km = i >> 6, c2 = blockIdx.y * 64 + (i & 63);
-            if (c2 < c) {
-                const size_t e = (static_cast<size_t>(km / M) * c + c2) * M + km % M;
-                if (mine) mine[e] = red[km][i & 63];
-                else atomicAdd(&grad_wd[e], red[km][i & 63]);
-            }
-        }
-    }
-}
-
+// The fused X-transform apply + depthwise kernels (xconv_dw_fwd_kernel, xconv_dw_bwd_fw_kernel) are the templates of xconv_common.h,
+// instantiated below with BN off at HF_XDW_DISPATCH, with and without GATHER.
 // gradient w.r.t. X: dX[r][k][j] = sum_ch dF_X[r][k][ch] * F[r][j][ch] with dF_X rebuilt from grad_out and Wd on the fly;
 // a wave per row.  The body is xc_bwd_x_body of xconv_common.h (shared with xconv_bn_bwd_x_kernel): Wd staged in LDS once per
 // block, scalar row bases with 32-bit lane offsets, the next trip's loads in flight behind the current products, and the 64
@@ -878,9 +720,10 @@ static int xdw_forward(long long rows, int k, int c, int c0, int m, const float 
     int rpb;
     xdw_pair_grid(rows, c, grid, rpb, 8);
     const bool v2 = xdw_v2(c, {f, fts, out});
+    const float *no_bn = nullptr;   // gamma, beta, mean, invstd of the BN = false instantiations
 #define HF_XDW_FWD_V(KK, MM, V)                                                                                        \
-    if (idx) hipLaunchKernelGGL((xconv_dw_fwd_kernel<KK, MM, true, V>), grid, dim3(kXcThreads), 0, st, rows, c, c0, rpb, x, f, fts, idx, n_src, rows_per_cloud, wd, out); \
-    else hipLaunchKernelGGL((xconv_dw_fwd_kernel<KK, MM, false, V>), grid, dim3(kXcThreads), 0, st, rows, c, c0, rpb, x, f, fts, idx, n_src, rows_per_cloud, wd, out);
+    if (idx) hipLaunchKernelGGL((xconv_dw_fwd_kernel<KK, MM, true, V, false>), grid, dim3(kXcThreads), 0, st, rows, c, c0, rpb, x, f, no_bn, no_bn, no_bn, no_bn, fts, idx, n_src, rows_per_cloud, wd, out); \
+    else hipLaunchKernelGGL((xconv_dw_fwd_kernel<KK, MM, false, V, false>), grid, dim3(kXcThreads), 0, st, rows, c, c0, rpb, x, f, no_bn, no_bn, no_bn, no_bn, fts, idx, n_src, rows_per_cloud, wd, out);
 #define HF_XDW_FWD(KK, MM) if (v2) { HF_XDW_FWD_V(KK, MM, true) } else { HF_XDW_FWD_V(KK, MM, false) }
     HF_XDW_DISPATCH(HF_XDW_FWD)
 #undef HF_XDW_FWD
@@ -911,9 +754,11 @@ static int xdw_backward(long long rows, int k, int c, int c0, int m, const float
         dim3 grid;
         int rpb;
         xdw_bwd_grid(rows, c, grid, rpb);
+        const float *no_bn = nullptr;   // gamma, beta, mean, invstd of the BN = false instantiations
+        float *no_sums = nullptr;       // their bn_partial
 #define HF_XDW_BFW(KK, MM)                                                                                             \
-        if (idx) hipLaunchKernelGGL((xconv_dw_bwd_fw_kernel<KK, MM, true>), grid, dim3(kXcThreads), 0, st, rows, c, c0, rpb, x, f, fts, idx, n_src, rows_per_cloud, wd, grad_out, grad_f, grad_gathered, grad_wd, wd_partial); \
-        else hipLaunchKernelGGL((xconv_dw_bwd_fw_kernel<KK, MM, false>), grid, dim3(kXcThreads), 0, st, rows, c, c0, rpb, x, f, fts, idx, n_src, rows_per_cloud, wd, grad_out, grad_f, grad_gathered, grad_wd, wd_partial);
+        if (idx) hipLaunchKernelGGL((xconv_dw_bwd_fw_kernel<KK, MM, true, false>), grid, dim3(kXcThreads), 0, st, rows, c, c0, rpb, x, f, no_bn, no_bn, no_bn, no_bn, fts, idx, n_src, rows_per_cloud, wd, grad_out, grad_f, grad_gathered, grad_wd, wd_partial, no_sums); \
+        else hipLaunchKernelGGL((xconv_dw_bwd_fw_kernel<KK, MM, false, false>), grid, dim3(kXcThreads), 0, st, rows, c, c0, rpb, x, f, no_bn, no_bn, no_bn, no_bn, fts, idx, n_src, rows_per_cloud, wd, grad_out, grad_f, grad_gathered, grad_wd, wd_partial, no_sums);
         HF_XDW_DISPATCH(HF_XDW_BFW)
 #undef HF_XDW_BFW
         if (wd_partial) launch_partial_reduce(k * c * m, static_cast<int>(grid.x), wd_partial, grad_wd, st);
@@ -1003,6 +848,35 @@ size_t hf::xdw_gathered_bytes(int b, int rows_per_cloud, int k, int c1)
     return (sizeof(float) * static_cast<size_t>(b) * rows_per_cloud * k * c1 + 255) & ~static_cast<size_t>(255);
 }
 
+// the plan, the tail and the empty batch of the two gather-mode gradient entries (this file's and xconv_bn.hip's; xconv_common.h)
+XdwGradPlan hf::xdw_grad_plan(int b, int n_src, int rows_per_cloud, int k, int c1, int m, const float *grad_fts, void *workspace)
+{
+    XdwGradPlan plan;
+    plan.direct = grad_fts && (!workspace || xdw_fts_direct(static_cast<long long>(b) * rows_per_cloud, n_src, rows_per_cloud, k, c1, m));
+    if (grad_fts && workspace && HF_DIAG_INT("HF_XDW_FTS_ROUTE", 0) != 0) plan.direct = HF_DIAG_INT("HF_XDW_FTS_ROUTE", 0) == 2;   // 1: staged, 2: direct
+    plan.gathered = (grad_fts && !plan.direct) ? static_cast<float *>(workspace) : nullptr;
+    plan.wd_partial = workspace ? reinterpret_cast<float *>(static_cast<unsigned char *>(workspace) + xdw_gathered_bytes(b, rows_per_cloud, k, c1)) : nullptr;
+    return plan;
+}
+
+int hf::xdw_grad_table(const XdwGradPlan &plan, int b, int n_src, int rows_per_cloud, int k, int c0, int c1, int m, const float *x,
+                       const float *wd, const float *grad_out, const int *offsets, const int *entries, float *grad_fts, hf_stream_t stream)
+{
+    if (plan.gathered) return hf_group_point_grad_gather(b, n_src, c1, rows_per_cloud, k, c1, 0, plan.gathered, offsets, entries, grad_fts, stream);
+    if (plan.direct)
+        return xdw_table_grad(static_cast<long long>(b) * n_src, n_src, rows_per_cloud, k, c0 + c1, c0, m, x, wd, grad_out, offsets, entries, grad_fts,
+                              as_stream(stream));
+    return HF_OK;
+}
+
+int hf::xdw_grad_empty(int b, int n_src, int k, int c0, int c1, int m, float *grad_fts, float *grad_wd, hipStream_t st)
+{
+    int rc = HF_OK;
+    if (grad_wd) rc = hip_status(hipMemsetAsync(grad_wd, 0, sizeof(float) * static_cast<size_t>(k) * (c0 + c1) * m, st));
+    if (rc == HF_OK && grad_fts && b > 0) rc = hip_status(hipMemsetAsync(grad_fts, 0, sizeof(float) * static_cast<size_t>(b) * n_src * c1, st));
+    return rc;
+}
+
 HF_API size_t hf_xconv_depthwise_gather_grad_workspace(int b, int rows_per_cloud, int k, int c0, int c1, int m)
 {
     if (b <= 0 || rows_per_cloud <= 0 || k <= 0 || c0 <= 0 || c1 <= 0 || m <= 0) return 0;
@@ -1025,27 +899,12 @@ HF_API int hf_xconv_depthwise_gather_grad(int b, int n_src, int rows_per_cloud, 
     if (grad_fts && (!offsets || !entries)) return HF_EINVAL;
     if (workspace && workspace_bytes < hf_xconv_depthwise_gather_grad_workspace(b, rows_per_cloud, k, c0, c1, m)) return HF_EWORKSPACE;
     hipStream_t st = as_stream(stream);
-    const long long rows = static_cast<long long>(b) * rows_per_cloud, src_rows = static_cast<long long>(b) * n_src;
-    const int c = c0 + c1;
-    // The table's gradient is rebuilt per table row from grad_out (xconv_dw_bwd_fts_kernel: nothing but the table is written), or,
-    // where xdw_fts_direct says so and a workspace is there, staged: xconv_dw_bwd_fw_kernel writes the gathered block's gradient
-    // (rows x k x c1) into the workspace and hf_group_point_grad_gather sums it per table row.  The partial weight gradients go
-    // through the workspace on both routes.
-    const bool want_fts = grad_fts && src_rows > 0 && rows > 0;
-    bool direct = want_fts && (!workspace || xdw_fts_direct(rows, n_src, rows_per_cloud, k, c1, m));
-    if (want_fts && workspace && HF_DIAG_INT("HF_XDW_FTS_ROUTE", 0) != 0) direct = HF_DIAG_INT("HF_XDW_FTS_ROUTE", 0) == 2;   // 1: staged, 2: direct
-    float *gathered = (want_fts && !direct) ? static_cast<float *>(workspace) : nullptr;
-    float *wd_partial = workspace ? reinterpret_cast<float *>(static_cast<unsigned char *>(workspace) + xdw_gathered_bytes(b, rows_per_cloud, k, c1)) : nullptr;
-    if (grad_fts && src_rows > 0 && rows == 0) {
-        const int rc = hip_status(hipMemsetAsync(grad_fts, 0, sizeof(float) * static_cast<size_t>(src_rows) * c1, st));
+    if (b == 0 || rows_per_cloud == 0) return xdw_grad_empty(b, n_src, k, c0, c1, m, grad_fts, grad_wd, st);
+    const XdwGradPlan plan = xdw_grad_plan(b, n_src, rows_per_cloud, k, c1, m, grad_fts, workspace);
+    if (grad_x || grad_f_delta || grad_wd || plan.gathered) {
+        const int rc = xdw_backward(static_cast<long long>(b) * rows_per_cloud, k, c0 + c1, c0, m, x, f_delta, fts, idx, n_src, rows_per_cloud, wd, grad_out,
+                                    grad_x, grad_f_delta, plan.gathered, grad_wd, st, plan.wd_partial);
         if (rc != HF_OK) return rc;
     }
-    if (grad_x || grad_f_delta || grad_wd || gathered) {
-        const int rc = xdw_backward(rows, k, c, c0, m, x, f_delta, fts, idx, n_src, rows_per_cloud, wd, grad_out, grad_x, grad_f_delta, gathered,
-                                    grad_wd, st, wd_partial);
-        if (rc != HF_OK) return rc;
-    }
-    if (gathered) return hf_group_point_grad_gather(b, n_src, c1, rows_per_cloud, k, c1, 0, gathered, offsets, entries, grad_fts, stream);
-    if (direct) return xdw_table_grad(src_rows, n_src, rows_per_cloud, k, c, c0, m, x, wd, grad_out, offsets, entries, grad_fts, st);
-    return HF_OK;
+    return xdw_grad_table(plan, b, n_src, rows_per_cloud, k, c0, c1, m, x, wd, grad_out, offsets, entries, grad_fts, stream);
 }

@@ -1,6 +1,6 @@
-// xconv_common.h -- what the fused X-Conv kernels of xconv.hip and their BatchNorm-folding twins of xconv_bn.hip share: the device
-// helpers of the channel-pair / lane-per-channel mappings (moved here from xconv.hip as they stood) and the launch geometry and
-// table-gradient launcher that xconv.hip defines.
+// xconv_common.h -- the fused X-Conv kernels that xconv.hip instantiates as they are and xconv_bn.hip with the lifting branch's last
+// BatchNorm folded in (`BN`): the device helpers of the channel-pair / lane-per-channel mappings, the kernel templates of the three
+// passes, and the launch geometry, gradient plan and table-gradient launcher that xconv.hip defines.
 #pragma once
 #include "hf_common.h"
 
@@ -195,10 +195,248 @@ __device__ __forceinline__ XcSource xc_source(int ch, int c, int c0, const float
     return s;
 }
 
-// ---- the two backward kernels: xconv_dw_bwd_x_kernel / xconv_bn_bwd_x_kernel and xconv_dw_bwd_fw_kernel / xconv_bn_bwd_fw_kernel ----
-// Each pair of twins is ONE body (`BN` switches the normalisation on load and the dgamma / dbeta sums on): the folded route and
-// the two-launch route give the same bits because they run the same code.
+// ---- the fused kernels: ONE template per pass, instantiated by xconv.hip (BN off, HF_XDW_DISPATCH, both GATHER) and by xconv_bn.hip
+// (BN on, GATHER on, HF_XBN_DISPATCH).  `BN` switches the normalisation on load and the dgamma / dbeta sums on: the folded route and
+// the two-launch route give the same bits because they run the same code.  A launch with BN off passes null for gamma, beta, mean,
+// invstd (and bn_partial).  The forward and the F / Wd gradient are the __global__ templates themselves -- as inlined bodies behind
+// per-file wrappers the compiler schedules several instantiations differently (K = 12 takes half as many instructions again) --
+// the X gradient is a body (xc_bwd_x_body) behind the two files' wrappers.
+
+// X-transform apply and the depthwise step of the separable convolution in one pass (pointcnn.py:133-140):
+//   out[r][ch*M + m] = sum_k (sum_j X[r][k][j] * F[r][j][ch]) * Wd[k][ch][m]
+// F_X = X x F_* (rows x K x C, the largest tensor of an X-Conv: 1.3 GB for the decoder layers at 131 072 points) is never
+// written: the K products of a (row, channel) stay in registers.  Same multiply / add order as hf_xconv_apply followed by
+// hf_depthwise_k, so the results are bit-identical to the two-kernel route.
+// Mapping: a lane owns one channel pair for the whole kernel (its K x M depthwise weights live in registers, blockIdx.y picks
+// the 128-channel chunk), the four waves of a block walk the rows of a chunk; the row's K x K matrix is wave-uniform.
 //
+// GATHER: F_* = [F_delta | F gathered] (pointcnn.py:124-127 concat of the lifted coordinates with the neighbours' features) is
+// not materialised either: channels below c0 come from `f` = F_delta (rows x K x c0), the others from the feature table
+// `fts` (clouds x n_src rows x c - c0) through the neighbour table `idx` (rows x K, indices inside the row's cloud).  The gathered
+// rows (K x the table, 1.1 GB for the last decoder layers) were written by group_point and read back here; now the table (134 MB,
+// L2 / MALL resident) is read in place.
+// BN: `f` is the lifting chain's pre-activation z1 and F_delta = BN1(elu(z1)) is rebuilt on load with bn_apply_kernel's sequence,
+// a = gamma * invstd; h = a * (elu_stream(z) - mean) + beta (multiply, then add: -ffp-contract=off).
+template <int K, int M, bool GATHER, bool V2, bool BN>
+__global__ __launch_bounds__(kXcThreads) void xconv_dw_fwd_kernel(long long rows, int c, int c0, int rows_per_block,
+                                                                 const float *__restrict__ x, const float *__restrict__ f,
+                                                                 const float *__restrict__ gamma, const float *__restrict__ beta,
+                                                                 const float *__restrict__ mean, const float *__restrict__ invstd,
+                                                                 const float *__restrict__ fts, const int *__restrict__ idx, int n_src,
+                                                                 int rows_per_cloud, const float *__restrict__ wd, float *__restrict__ out)
+{
+    static_assert(GATHER || !BN, "the BatchNorm fold exists on the gather route only");
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
+    const int ch = blockIdx.y * 128 + 2 * lane;
+    const XcPair src = xc_pair(ch, c, c0, f, fts, GATHER);
+    const int cw = src.live ? ch : (c - 1) & ~1;
+    f2 w[K][M];
+#pragma unroll
+    for (int k = 0; k < K; ++k)
+#pragma unroll
+        for (int m = 0; m < M; ++m) w[k][m] = f2{wd[(static_cast<size_t>(k) * c + cw) * M + m], wd[(static_cast<size_t>(k) * c + cw + src.hi) * M + m]};
+    // BN: the pair's BatchNorm constants, loaded once like w (c0 is even: a lifted pair lies below c0 as a whole); a gathered lane
+    // reads channel 0's, computes with them and keeps the raw value by select
+    bool some_lifted = false;   // this block column holds lifted channels
+    f2 ba, bmu, bb;
+    if constexpr (BN) {
+        const int cb = src.gathered ? 0 : cw;
+        some_lifted = static_cast<int>(blockIdx.y) * 128 < c0;
+        ba = f2{gamma[cb] * invstd[cb], gamma[cb + 1] * invstd[cb + 1]};
+        bmu = f2{mean[cb], mean[cb + 1]};
+        bb = f2{beta[cb], beta[cb + 1]};
+    }
+    const unsigned lstride = GATHER ? c0 : c, c1 = c - c0;
+    const long long r0 = static_cast<long long>(blockIdx.x) * rows_per_block;
+    const long long r1 = r0 + rows_per_block < rows ? r0 + rows_per_block : rows;
+    __shared__ float xs[kXcThreads / 64][kXcRows][K * K];
+    XcCloud cl = xc_cloud(r0, rows_per_cloud, n_src);
+    for (long long rb = r0 + wave; rb < r1; rb += 4 * kXcRows) {
+        f2 fv[kXcRows][K];
+        long long rr[kXcRows];
+#pragma unroll
+        for (int i = 0; i < kXcRows; ++i) rr[i] = rb + 4 * i < r1 ? rb + 4 * i : r1 - 1;
+        XcXRows<K> xrow;
+        xrow.load(x, rr, lane);
+#pragma unroll
+        for (int i = 0; i < kXcRows; ++i) {
+            const unsigned tb = GATHER ? xc_tbase(cl, rr[i], rows_per_cloud, n_src) : 0u;
+            xc_gather_row<K, GATHER, V2>(src, rr[i], tb, idx, lstride, c1, fv[i]);
+        }
+        xrow.stage(xs[wave], lane);
+#pragma unroll
+        for (int i = 0; i < kXcRows; ++i) {
+            if (rb + 4 * i >= r1) break;
+            if constexpr (BN) {
+                if (some_lifted) {   // uniform over the block: the columns past the split (most of them) pay nothing
+#pragma unroll
+                    for (int j = 0; j < K; ++j) {
+                        const f2 z = fv[i][j];
+                        const f2 h = ba * (f2{elu_stream(z.x), elu_stream(z.y)} - bmu) + bb;
+                        fv[i][j] = src.gathered ? z : h;
+                    }
+                }
+            }
+            const float *xr = xs[wave][i];
+            f2 o[M];
+#pragma unroll
+            for (int m = 0; m < M; ++m) o[m] = f2{0.f, 0.f};
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+                f2 t = xr[k * K] * fv[i][0];
+#pragma unroll
+                for (int j = 1; j < K; ++j) t = t + xr[k * K + j] * fv[i][j];
+#pragma unroll
+                for (int m = 0; m < M; ++m) o[m] = o[m] + t * w[k][m];
+            }
+            if (src.live) st_pair_m<M, V2>(out + static_cast<size_t>(rr[i] * c + ch) * M, src.hi_live, o);
+        }
+    }
+}
+
+// gradients w.r.t. F and Wd: a lane owns ONE channel (64 per block column, see XcSource); per (row, channel) the gradient of F_X
+// (K values), F_X itself (recomputed) and the K input gradients stay in registers; a lane sums its channel's K x M weight gradients
+// over its rows.
+// GATHER: grad_f is the gradient of F_delta only (rows x K x c0); the gathered channels' gradient is either written to
+// grad_gathered (rows x K x c1, then summed per table row by hf_group_point_grad_gather) or rebuilt per table row by
+// xconv_dw_bwd_fts_kernel.
+// BN: the lifted values are normalised on load, and the two BatchNorm-backward sums of the lifted channels (bn_bwd_reduce_kernel's
+// expressions on the gradient this kernel stores) are formed on the way: a lane owns one channel over all its rows, as it does for
+// the Wd gradient; the four waves meet in LDS in wave order and the block writes bn_partial[blockIdx.x][0][c0] = sum gf,
+// bn_partial[blockIdx.x][1][c0] = sum gf * xhat (xconv_bn_finalize_kernel adds the blocks).  wd_partial is always there: no atomics.
+// amdgpu_waves_per_eu(4) with BN: the grid is four blocks per CU (xdw_bwd_grid), one wave of each per SIMD; with the two sums
+// carried through the row loop the scheduler otherwise trades that residency for up to 190 VGPRs (two or three waves per SIMD);
+// held to 128 the kernels take 96 / 114 / 124 at M = 1 / 2 / 4, nothing spilled.  Without BN the kernel is left unconstrained.
+template <int K, int M, bool GATHER, bool BN>
+__global__ __launch_bounds__(kXcThreads) __attribute__((amdgpu_waves_per_eu(BN ? 4 : 1))) void xconv_dw_bwd_fw_kernel(
+    long long rows, int c, int c0, int rows_per_block, const float *__restrict__ x, const float *__restrict__ f,
+    const float *__restrict__ gamma, const float *__restrict__ beta, const float *__restrict__ mean, const float *__restrict__ invstd,
+    const float *__restrict__ fts, const int *__restrict__ idx, int n_src, int rows_per_cloud, const float *__restrict__ wd,
+    const float *__restrict__ grad_out, float *__restrict__ grad_f, float *__restrict__ grad_gathered, float *__restrict__ grad_wd,
+    float *__restrict__ wd_partial, float *__restrict__ bn_partial)
+{
+    static_assert(GATHER || !BN, "the BatchNorm fold exists on the gather route only");
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
+    const int ch = blockIdx.y * 64 + lane;
+    const bool live = ch < c;
+    const XcSource src = xc_source(live ? ch : blockIdx.y * 64, c, c0, f, fts, GATHER ? idx : nullptr);
+    if (GATHER && src.gathered && !grad_wd && !grad_gathered) return;   // nothing of this chunk is asked for (no partial to write either)
+    bool lifted = false;   // BN: = !src.gathered, uniform over the block; every lane of a lifted chunk is live
+    float bis, ba, bmu, bb, s1 = 0.f, s2 = 0.f;
+    if constexpr (BN) {
+        lifted = static_cast<int>(blockIdx.y) * 64 < c0;
+        const int cb = lifted ? ch : 0;
+        bis = invstd[cb]; ba = gamma[cb] * bis; bmu = mean[cb]; bb = beta[cb];
+    }
+    float w[K][M], gw[K][M];
+#pragma unroll
+    for (int k = 0; k < K; ++k)
+#pragma unroll
+        for (int m = 0; m < M; ++m) { w[k][m] = live ? wd[(static_cast<size_t>(k) * c + ch) * M + m] : 0.f; gw[k][m] = 0.f; }
+    const long long r0 = static_cast<long long>(blockIdx.x) * rows_per_block;
+    const long long r1 = r0 + rows_per_block < rows ? r0 + rows_per_block : rows;
+    for (long long r = r0 + wave; r < r1; r += kXcThreads / 64) {
+        const float *xr = x + r * (K * K);
+        float fv[K], xv[K], g[M], gfx[K];
+        const long long tbase = (GATHER && src.gathered) ? static_cast<long long>(static_cast<unsigned>(r) / static_cast<unsigned>(rows_per_cloud)) * n_src : 0;
+#pragma unroll
+        for (int j = 0; j < K; ++j) {
+            const long long srow = (GATHER && src.gathered) ? tbase + idx[r * K + j] : r * K + j;
+            fv[j] = live ? src.base[srow * src.stride] : 0.f;
+            if constexpr (BN) xv[j] = 0.f;
+        }
+        if constexpr (BN) {
+            if (lifted) {   // a uniform branch behind the loads: z1 -> F_delta, elu(z1) kept for the sums below
+#pragma unroll
+                for (int j = 0; j < K; ++j) {
+                    xv[j] = elu_stream(fv[j]);
+                    fv[j] = ba * (xv[j] - bmu) + bb;
+                }
+            }
+        }
+        load_m<M>(grad_out, static_cast<size_t>(r * c + (live ? ch : 0)) * M, g);
+        if (!live) {
+#pragma unroll
+            for (int m = 0; m < M; ++m) g[m] = 0.f;
+        }
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            float a = 0.f;
+#pragma unroll
+            for (int m = 0; m < M; ++m) a = a + g[m] * w[k][m];          // = hf_depthwise_k_grad's dx
+            gfx[k] = a;
+            float t = xr[k * K] * fv[0];                                  // F_X recomputed
+#pragma unroll
+            for (int j = 1; j < K; ++j) t = t + xr[k * K + j] * fv[j];
+#pragma unroll
+            for (int m = 0; m < M; ++m) gw[k][m] = gw[k][m] + t * g[m];   // = hf_depthwise_k_grad's dw
+        }
+        float *gdst = (GATHER && src.gathered) ? (grad_gathered ? grad_gathered + (ch - c0) : nullptr) : (grad_f ? grad_f + ch : nullptr);
+        if (live && gdst) {
+            float ga[K];
+#pragma unroll
+            for (int j = 0; j < K; ++j) {
+                float a = xr[j] * gfx[0];                                  // = hf_xconv_apply_grad's dF (X transposed)
+#pragma unroll
+                for (int k = 1; k < K; ++k) a = a + xr[k * K + j] * gfx[k];
+                gdst[(r * K + j) * src.stride] = a;
+                ga[j] = a;
+            }
+            if constexpr (BN) {
+                if (lifted) {   // = bn_bwd_reduce_kernel's sums with dh = the value just stored (behind the stores: inside their loop the sums cost 40 VGPRs)
+#pragma unroll
+                    for (int j = 0; j < K; ++j) { s1 += ga[j]; s2 += ga[j] * ((xv[j] - bmu) * bis); }
+                }
+            }
+        }
+    }
+    __shared__ float red[K * M][64];
+    if constexpr (BN) {
+        if (lifted && grad_f) {
+            // the waves take turns, wave 0 first, on two rows of `red` (a fixed order of adds); the Wd reduction below reuses them
+            for (int wv = 0; wv < kXcThreads / 64; ++wv) {
+                if (wave == wv) {
+                    red[0][lane] = wv == 0 ? s1 : red[0][lane] + s1;
+                    red[1][lane] = wv == 0 ? s2 : red[1][lane] + s2;
+                }
+                __syncthreads();
+            }
+            if (wave == 0) {   // the slots it reads are its own: the first writer below is this same thread
+                float *mine = bn_partial + static_cast<size_t>(blockIdx.x) * 2 * c0;
+                mine[ch] = red[0][lane];
+                mine[c0 + ch] = red[1][lane];
+            }
+        }
+    }
+    if (grad_wd) {
+        // the waves of a block meet in LDS first: one sum per coefficient and BLOCK (per wave it was 8.4 M atomics on 2080 addresses
+        // for the first encoder layer: 870 us for 140 us of memory traffic)
+        // The waves take turns, wave 0 first: a fixed order of adds (LDS atomics left it to the order the waves arrived in), so with
+        // wd_partial grad_wd is the same bits on every call.  The slots of dead lanes are neither written nor read.
+        for (int wv = 0; wv < kXcThreads / 64; ++wv) {
+            if (wave == wv && live) {
+#pragma unroll
+                for (int k = 0; k < K; ++k)
+#pragma unroll
+                    for (int m = 0; m < M; ++m) red[k * M + m][lane] = wv == 0 ? gw[k][m] : red[k * M + m][lane] + gw[k][m];
+            }
+            __syncthreads();
+        }
+        // wd_partial (always with BN): the row chunks' sums are written out (wd_partial[row chunk][K*c*M]) and added in a fixed order
+        // by a second kernel; else one global atomic per coefficient and block on grad_wd (zero-filled by the entry point)
+        float *mine = (BN || wd_partial) ? wd_partial + static_cast<size_t>(blockIdx.x) * K * c * M : nullptr;
+        for (int i = threadIdx.x; i < K * M * 64; i += kXcThreads) {
+            const int km = i >> 6, c2 = blockIdx.y * 64 + (i & 63);
+            if (c2 < c) {
+                const size_t e = (static_cast<size_t>(km / M) * c + c2) * M + km % M;
+                if (BN || mine) mine[e] = red[km][i & 63];
+                else atomicAdd(&grad_wd[e], red[km][i & 63]);
+            }
+        }
+    }
+}
+
+// ---- the X gradient: xconv_dw_bwd_x_kernel / xconv_bn_bwd_x_kernel ----
 // Addresses: a row's tensors are reached through wave-uniform 64-bit bases (F + r K stride, grad_out + r c M, the K table rows of
 // the row's neighbours) formed on the scalar side once per row; a lane adds a 32-bit element offset (its channel, plus j * stride
 // inside the row's K x stride block of F), so the loads take their base from scalar registers and no 64-bit product is formed
@@ -530,5 +768,22 @@ size_t xdw_gathered_bytes(int b, int rows_per_cloud, int k, int c1);
 // xconv_dw_bwd_fts_kernel: the table's gradient rebuilt per table row from grad_out
 int xdw_table_grad(long long src_rows, int n_src, int rows_per_cloud, int k, int c, int c0, int m, const float *x, const float *wd,
                    const float *grad_out, const int *offsets, const int *entries, float *grad_fts, hipStream_t st);
+
+// What hf_xconv_depthwise_gather_grad and hf_xconv_depthwise_gather_bn_grad decide alike once rows > 0 (each keeps its argument
+// checks and its launches).  The table's gradient is rebuilt per table row from grad_out (xdw_table_grad: nothing but the table is
+// written), or, where xdw_fts_direct says so and a workspace is there, staged: xconv_dw_bwd_fw_kernel writes the gathered block's
+// gradient (rows x k x c1) into the workspace and hf_group_point_grad_gather sums it per table row.  The partial weight gradients
+// go through the workspace on both routes.
+struct XdwGradPlan {
+    bool direct;         // grad_fts is asked for and rebuilt per table row
+    float *gathered;     // grad_fts is asked for and staged here, at the head of the workspace; else null
+    float *wd_partial;   // behind the staging region; null without a workspace
+};
+XdwGradPlan xdw_grad_plan(int b, int n_src, int rows_per_cloud, int k, int c1, int m, const float *grad_fts, void *workspace);
+// the table's gradient by the plan's route, behind the entry's own launches
+int xdw_grad_table(const XdwGradPlan &plan, int b, int n_src, int rows_per_cloud, int k, int c0, int c1, int m, const float *x,
+                   const float *wd, const float *grad_out, const int *offsets, const int *entries, float *grad_fts, hf_stream_t stream);
+// an empty batch (rows = 0): the weight and table gradients that are asked for are zero
+int xdw_grad_empty(int b, int n_src, int k, int c0, int c1, int m, float *grad_fts, float *grad_wd, hipStream_t st);
 
 }  // namespace hf

@@ -4,7 +4,8 @@ of rpn_multiclass at 8 frames:
   dec5  b 8, 16384 table rows and 16384 rows per cloud, K 8, c0 64, c1 256, M 1
   enc0  the same clouds, c1 1, M 4
 
-Each shape is called once for grad_f + grad_wd (xconv_bn_bwd_fw_kernel, partial_rows_sum / finalize kernels) and once for grad_x
+Each shape is called once for grad_f + grad_wd (xconv_dw_bwd_fw_kernel<K, M, true, true>: the BN = true instantiation, then the
+partial_rows_sum / finalize kernels) and once for grad_x
 (xconv_bn_bwd_x_kernel), ITERS times each after one warm-up call.  Run it
   - under `rocprofv3 --kernel-trace --stats` for per-kernel durations, or
   - under `rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_BUSY_CYCLES SQ_WAVE_CYCLES` (a run of its own, no tracing) for the

@@ -1,6 +1,7 @@
 """Diagnostic: the two routes to the feature table's gradient in hf_xconv_depthwise_gather_grad, per layer shape.
 
-  staged: xconv_dw_bwd_fw_kernel writes the gathered block's gradient (rows x K x c1) into the workspace and
+  staged: xconv_dw_bwd_fw_kernel (here <K, M, true, false>: GATHER on, BN off) writes the gathered block's gradient (rows x K x c1)
+          into the workspace and
           hf_group_point_grad_gather sums it per table row
   direct: xconv_dw_bwd_fts_kernel rebuilds it per table row from grad_out; xconv_dw_bwd_fw_kernel writes nothing for the gathered
           channels

@@ -1,7 +1,8 @@
 """Kernel set of csrc/xconv_bn.hip, on any machine with hipcc: the file is compiled to assembly with the Makefile's flags and its code
-object must hold exactly the three BatchNorm-folding twins at the (K, M) their entry points dispatch (the forward also by V2), plus
-the finalize kernel; none of them may spill a vector register or touch scratch.  Only the kernel-metadata table is read (names, LDS,
-registers, spills, scratch).  Run as a script, the module prints the table committed as profiles/xconv_bn_instantiations.md."""
+object must hold exactly the three fused kernels with the BatchNorm fold on (the templates of xconv_common.h at GATHER = BN = true) at the
+(K, M) their entry points dispatch (the forward also by V2), plus the finalize kernel; none of them may spill a vector register or touch
+scratch.  Only the kernel-metadata table is read (names, LDS, registers, spills, scratch).  Run as a script, the module prints the table
+committed as profiles/xconv_bn_instantiations.md."""
 import os
 import sys
 import tempfile
@@ -17,8 +18,8 @@ XBN_DISPATCH = ((8, 1), (8, 2), (8, 4))        # HF_XBN_DISPATCH of csrc/xconv_b
 def expected():
     want = {("xconv_bn_finalize_kernel", ())}
     for k, m in XBN_DISPATCH:
-        want |= {("xconv_bn_fwd_kernel", (k, m, False)), ("xconv_bn_fwd_kernel", (k, m, True)), ("xconv_bn_bwd_fw_kernel", (k, m)),
-                 ("xconv_bn_bwd_x_kernel", (k, m))}
+        want |= {("xconv_dw_fwd_kernel", (k, m, True, False, True)), ("xconv_dw_fwd_kernel", (k, m, True, True, True)),
+                 ("xconv_dw_bwd_fw_kernel", (k, m, True, True)), ("xconv_bn_bwd_x_kernel", (k, m))}
     return want
 
 
@@ -45,10 +46,13 @@ def test_no_kernel_spills_or_uses_scratch(table):
 
 def test_the_backward_keeps_four_waves_per_simd(table):
     """xdw_bwd_grid launches four blocks per CU, one wave of each per SIMD: 512 VGPRs / 4 = 128 is what the attribute on
-    xconv_bn_bwd_fw_kernel holds the kernel to"""
+    xconv_dw_bwd_fw_kernel<K, M, true, true> holds the kernel to"""
+    seen = 0
     for name, args, f in table:
-        if name == "xconv_bn_bwd_fw_kernel":
-            assert f["vgpr"] <= 128, (args, f["vgpr"])
+        if name == "xconv_dw_bwd_fw_kernel":
+            seen += 1
+            assert args[3] is True and f["vgpr"] <= 128, (args, f["vgpr"])
+    assert seen == len(XBN_DISPATCH)
 
 
 def check_argument_limits():
@@ -97,8 +101,8 @@ def test_one_past_each_argument_limit_is_refused():
 def render(table):
     lines = ["# Kernels and template instantiations of csrc/xconv_bn.hip", "",
              "Compiled for gfx950 with the Makefile's flags (`-O3 -ffp-contract=off`); produced by",
-             "`python tests/test_xconv_bn_instantiations_cpu.py`.  Template arguments: `xconv_bn_fwd_kernel<K, M, V2>`,",
-             "`xconv_bn_bwd_fw_kernel` / `xconv_bn_bwd_x_kernel<K, M>`.  LDS is the static part (`xconv_bn_bwd_x_kernel` takes its own at launch).", "",
+             "`python tests/test_xconv_bn_instantiations_cpu.py`.  Template arguments: `xconv_dw_fwd_kernel<K, M, GATHER, V2, BN>`,",
+             "`xconv_dw_bwd_fw_kernel<K, M, GATHER, BN>`, `xconv_bn_bwd_x_kernel<K, M>`.  LDS is the static part (`xconv_bn_bwd_x_kernel` takes its own at launch).", "",
              "| kernel | template arguments | LDS bytes | VGPRs | spilled VGPRs | spilled SGPRs | scratch bytes |", "|---|---|---:|---:|---:|---:|---:|"]
     for name, args, f in table:
         lines.append("| `%s` | %s | %d | %d | %d | %d | %d |" % (name, ", ".join(str(a).lower() for a in args) or "-", f["lds"], f["vgpr"], f["spill"],

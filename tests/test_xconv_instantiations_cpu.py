@@ -55,7 +55,7 @@ def render(table):
              "Compiled for gfx950 with the Makefile's flags (`-O3 -ffp-contract=off`); produced by",
              "`python tests/test_xconv_instantiations_cpu.py`.  Template arguments: `xconv_apply_kernel<K, TRANSPOSED>`, `xconv_dx_kernel<K>`,",
              "`depthwise_fwd_kernel` / `depthwise_dx_kernel` / `depthwise_dw_kernel<K, M>`, `depthwise_narrow_kernel<K, M, DX>`,",
-             "`xconv_dw_fwd_kernel<K, M, GATHER, V2>`, `xconv_dw_bwd_fw_kernel` / `xconv_dw_bwd_x_kernel<K, M, GATHER>`,",
+             "`xconv_dw_fwd_kernel<K, M, GATHER, V2, BN>`, `xconv_dw_bwd_fw_kernel<K, M, GATHER, BN>`, `xconv_dw_bwd_x_kernel<K, M, GATHER>`,",
              "`xconv_dw_bwd_fts_kernel<K, M, VEC>`.  LDS is the static part (`xconv_dx_kernel`, `xconv_dw_bwd_x_kernel` and",
              "`depthwise_dw_kernel` take theirs at launch).  The last two columns count the cases of `tests/xconv_cases.py` that launch the kernel.", "",
              "| kernel | template arguments | LDS bytes | VGPRs | spilled VGPRs | spilled SGPRs | scratch bytes | exact cases | rounding cases |",

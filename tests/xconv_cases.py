@@ -392,11 +392,11 @@ def instantiations(c):
     s = set()
     if kind == "fwd":
         names = ("f", "fts", "out") if c["gather"] else ("f", "out")
-        s.add(("xconv_dw_fwd_kernel", (k, m, c["gather"], xdw_v2(c["c0"] + c["c1"], aligned(c, *names)))))
+        s.add(("xconv_dw_fwd_kernel", (k, m, c["gather"], xdw_v2(c["c0"] + c["c1"], aligned(c, *names)), False)))    # BN off: xconv.hip
     elif kind == "bwd":
         want, g = c["want"], c["gather"]
         if {"f", "wd"} & set(want) or route(c) == "staged":
-            s.add(("xconv_dw_bwd_fw_kernel", (k, m, g)))
+            s.add(("xconv_dw_bwd_fw_kernel", (k, m, g, False)))
         if "x" in want:
             s.add(("xconv_dw_bwd_x_kernel", (k, m, g)))
         if route(c) == "direct":
