@@ -5,6 +5,7 @@
 #include "hf_common.h"
 
 #include <initializer_list>
+#include <type_traits>
 
 namespace hf {
 
@@ -122,6 +123,17 @@ __device__ __forceinline__ unsigned xc_tbase(XcCloud &cl, long long r, int rows_
     return cl.tbase;
 }
 
+// xc_tbase with its loop kept a loop: left visible, the compiler replaces it by the closed form, a 64-bit division per row
+__device__ __forceinline__ unsigned xc_tbase_step(XcCloud &cl, long long r, int rows_per_cloud, int n_src)
+{
+    while (r >= cl.next) {
+        cl.next += rows_per_cloud;
+        cl.tbase += static_cast<unsigned>(n_src);
+        asm volatile("" : "+s"(cl.tbase));
+    }
+    return cl.tbase;
+}
+
 __device__ __forceinline__ XcCloud xc_cloud(long long r, int rows_per_cloud, int n_src)
 {
     const long long b = r / rows_per_cloud;
@@ -194,6 +206,90 @@ __device__ __forceinline__ XcSource xc_source(int ch, int c, int c0, const float
     else { s.base = fts + (ch - c0); s.stride = c - c0; s.gathered = true; }
     return s;
 }
+
+// a float at a wave-uniform base plus a 32-bit byte offset per lane: the load takes the base from scalar registers
+__device__ __forceinline__ const float *xc_at(const float *base, unsigned byte_off)
+{
+    return reinterpret_cast<const float *>(reinterpret_cast<const char *>(base) + byte_off);
+}
+
+// A wave-uniform row base in global memory, made opaque to the optimiser (two scalar registers pass through an empty asm): left
+// visible, the lane's loop-invariant offset is folded into the tensor's base outside the loop, or into a sum shared by the K
+// accesses of a row, and every access forms a 64-bit address in vector registers.  Opaque, the access takes its base from the
+// scalar pair and the lane's 32-bit offset as it is.
+typedef __attribute__((address_space(1))) float xc_gfloat;
+__device__ __forceinline__ xc_gfloat *xc_sbase(const float *p)
+{
+    const unsigned long long b = reinterpret_cast<unsigned long long>(p);
+    unsigned lo = __builtin_amdgcn_readfirstlane(static_cast<unsigned>(b)), hi = __builtin_amdgcn_readfirstlane(static_cast<unsigned>(b >> 32));
+    asm("" : "+s"(lo), "+s"(hi));
+    return (xc_gfloat *)((static_cast<unsigned long long>(hi) << 32) | lo);
+}
+// a lane's loop-invariant offset as a value of the loop's own (one register move): hoisted out of the loop, its 64-bit extension
+// is all the instruction selector sees, and the scalar-base form of the access is not chosen
+__device__ __forceinline__ unsigned xc_lane_off(unsigned off)
+{
+    asm volatile("" : "+v"(off));
+    return off;
+}
+__device__ __forceinline__ xc_gfloat *xc_gat(xc_gfloat *base, unsigned byte_off)
+{
+    return (xc_gfloat *)((__attribute__((address_space(1))) char *)base + byte_off);
+}
+
+// the M floats of a (row, channel) pair at p; `arg` is the tensor's first element (a kernel argument), whose alignment decides
+// for every (row, channel) pair alike
+template <int M>
+__device__ __forceinline__ void xc_load_m(const float *arg, const float *p, float (&v)[M])
+{
+    if constexpr (M == 4) {
+        if ((reinterpret_cast<uintptr_t>(arg) & 15) == 0) {
+            const float4 t = *reinterpret_cast<const float4 *>(p);
+            v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+            return;
+        }
+    } else if constexpr (M == 2) {
+        if ((reinterpret_cast<uintptr_t>(arg) & 7) == 0) { const float2 t = *reinterpret_cast<const float2 *>(p); v[0] = t.x; v[1] = t.y; return; }
+    }
+#pragma unroll
+    for (int m = 0; m < M; ++m) v[m] = p[m];
+}
+
+// xc_load_m through a global-memory pointer
+template <int M>
+__device__ __forceinline__ void xc_gload_m(const float *arg, xc_gfloat *p, float (&v)[M])
+{
+    typedef float v4 __attribute__((ext_vector_type(4)));
+    if constexpr (M == 4) {
+        if ((reinterpret_cast<uintptr_t>(arg) & 15) == 0) {
+            const v4 t = *(__attribute__((address_space(1))) v4 *)p;
+            v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+            return;
+        }
+    } else if constexpr (M == 2) {
+        if ((reinterpret_cast<uintptr_t>(arg) & 7) == 0) { const f2 t = *(__attribute__((address_space(1))) f2 *)p; v[0] = t.x; v[1] = t.y; return; }
+    }
+#pragma unroll
+    for (int m = 0; m < M; ++m) v[m] = p[m];
+}
+
+// A batch of xconv_dw_bwd_fw_kernel: the operands of a wave's R rows as loaded (X still in registers, one coalesced load per 64
+// coefficients; the lifted values of the BN twin still un-normalised).
+template <int K, int M, int R>
+struct XcFwBatch {
+    static constexpr int Q = (K * K + 63) / 64;
+    float x[R][Q];
+    f2 fv[R][K / 2];   // pairs of neighbours: a packed product takes one half as its broadcast operand
+    float g[R][M];
+};
+// Rows of a wave in flight (the batch): kXcRows wherever 128 VGPRs hold them without a spill (four blocks per CU, one wave of each
+// per SIMD: see xdw_bwd_grid), else one; see profiles/xconv_instantiations.md and profiles/xconv_bn_instantiations.md.
+constexpr int xc_fw_rows(int k, int m, bool bn) { return k * m >= 24 ? 1 : kXcRows; }
+// Where the lane's K x M depthwise weights live during the row loop: in registers, or, where those 2 K M registers (weights and
+// their gradient sums) leave no room, in the block's reduction buffer, idle until the loop ends, read per pair of k
+constexpr bool xc_fw_wd_lds(int k, int m) { return k * m >= 32; }
+// Whether the next batch's loads are issued ahead of the current batch's products (a second XcFwBatch in registers)
+constexpr bool xc_fw_pipe(int k, int m, bool bn) { return k == 4 || k * m <= 8; }
 
 // ---- the fused kernels: ONE template per pass, instantiated by xconv.hip (BN off, HF_XDW_DISPATCH, both GATHER) and by xconv_bn.hip
 // (BN on, GATHER on, HF_XBN_DISPATCH).  `BN` switches the normalisation on load and the dgamma / dbeta sums on: the folded route and
@@ -304,11 +400,19 @@ __global__ __launch_bounds__(kXcThreads) void xconv_dw_fwd_kernel(long long rows
 // expressions on the gradient this kernel stores) are formed on the way: a lane owns one channel over all its rows, as it does for
 // the Wd gradient; the four waves meet in LDS in wave order and the block writes bn_partial[blockIdx.x][0][c0] = sum gf,
 // bn_partial[blockIdx.x][1][c0] = sum gf * xhat (xconv_bn_finalize_kernel adds the blocks).  wd_partial is always there: no atomics.
-// amdgpu_waves_per_eu(4) with BN: the grid is four blocks per CU (xdw_bwd_grid), one wave of each per SIMD; with the two sums
-// carried through the row loop the scheduler otherwise trades that residency for up to 190 VGPRs (two or three waves per SIMD);
-// held to 128 the kernels take 96 / 114 / 124 at M = 1 / 2 / 4, nothing spilled.  Without BN the kernel is left unconstrained.
+// The row loop: wave w of a block takes rows r0 + w + 4 i in ascending order, R of them per batch (xc_fw_rows).  Every load of a batch
+// -- the neighbour indices (scalar, read one batch ahead), the R rows' X (one coalesced load per 64 coefficients), K neighbour
+// values and grad_out -- is issued before the first row's products, through wave-uniform 64-bit row bases with 32-bit lane offsets;
+// where the registers allow (xc_fw_pipe) the NEXT batch's loads are issued before the current batch's products.  A row past the
+// block's end is clamped to the last row (its loads stay valid) and skipped; a lane past the last channel reads the last channel
+// and stores nothing.  X goes from the registers into the wave's own LDS slot and is read back as broadcasts: as scalar operands
+// the 64 coefficients of a row and the 17 pointer arguments did not fit the scalar file, and about 80 lane moves per row carried
+// the spills.  The products run packed on pairs of k (F_X, dF_X, the weight gradient) and pairs of j (the input gradient); every
+// output element keeps the sequence of multiplies and adds it had, so the results are the bits of the one-row-at-a-time form.
+// amdgpu_waves_per_eu(4): the grid is four blocks per CU (xdw_bwd_grid), one wave of each per SIMD, so 128 VGPRs; nothing spills
+// (profiles/xconv_instantiations.md, profiles/xconv_bn_instantiations.md).
 template <int K, int M, bool GATHER, bool BN>
-__global__ __launch_bounds__(kXcThreads) __attribute__((amdgpu_waves_per_eu(BN ? 4 : 1))) void xconv_dw_bwd_fw_kernel(
+__global__ __launch_bounds__(kXcThreads) __attribute__((amdgpu_waves_per_eu(4))) void xconv_dw_bwd_fw_kernel(
     long long rows, int c, int c0, int rows_per_block, const float *__restrict__ x, const float *__restrict__ f,
     const float *__restrict__ gamma, const float *__restrict__ beta, const float *__restrict__ mean, const float *__restrict__ invstd,
     const float *__restrict__ fts, const int *__restrict__ idx, int n_src, int rows_per_cloud, const float *__restrict__ wd,
@@ -316,6 +420,7 @@ __global__ __launch_bounds__(kXcThreads) __attribute__((amdgpu_waves_per_eu(BN ?
     float *__restrict__ wd_partial, float *__restrict__ bn_partial)
 {
     static_assert(GATHER || !BN, "the BatchNorm fold exists on the gather route only");
+    constexpr int R = xc_fw_rows(K, M, BN), Q = XcFwBatch<K, M, R>::Q;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
     const int ch = blockIdx.y * 64 + lane;
     const bool live = ch < c;
@@ -328,69 +433,189 @@ __global__ __launch_bounds__(kXcThreads) __attribute__((amdgpu_waves_per_eu(BN ?
         const int cb = lifted ? ch : 0;
         bis = invstd[cb]; ba = gamma[cb] * bis; bmu = mean[cb]; bb = beta[cb];
     }
-    float w[K][M], gw[K][M];
+    // Packed f32 across PAIRS OF k: the lane keeps its single channel, and {k, k + 1} values of dF_X, F_X and the weight gradient go
+    // through v_pk_mul_f32 / v_pk_add_f32 (each half rounds like the scalar op; every element keeps its own multiply / add sequence).
+    static_assert(K % 2 == 0, "pairs of k");
+    constexpr bool WL = xc_fw_wd_lds(K, M);
+    __shared__ float red[K * M][64];
+    f2 *const wl = reinterpret_cast<f2 *>(&red[0][0]) + lane * M;   // WL: [pair of k][lane][m], the same 64 channels for the four waves
+    f2 w[WL ? 1 : K / 2][M], gw[K / 2][M];
 #pragma unroll
-    for (int k = 0; k < K; ++k)
+    for (int kp = 0; kp < K / 2; ++kp)
 #pragma unroll
-        for (int m = 0; m < M; ++m) { w[k][m] = live ? wd[(static_cast<size_t>(k) * c + ch) * M + m] : 0.f; gw[k][m] = 0.f; }
+        for (int m = 0; m < M; ++m) {
+            const f2 wk = live ? f2{wd[(static_cast<size_t>(2 * kp) * c + ch) * M + m], wd[(static_cast<size_t>(2 * kp + 1) * c + ch) * M + m]} : f2{0.f, 0.f};
+            if constexpr (WL) { if (wave == 0) wl[kp * 64 * M + m] = wk; }
+            else w[kp][m] = wk;
+            gw[kp][m] = f2{0.f, 0.f};
+        }
+    if constexpr (WL) __syncthreads();
     const long long r0 = static_cast<long long>(blockIdx.x) * rows_per_block;
     const long long r1 = r0 + rows_per_block < rows ? r0 + rows_per_block : rows;
-    for (long long r = r0 + wave; r < r1; r += kXcThreads / 64) {
-        const float *xr = x + r * (K * K);
-        float fv[K], xv[K], g[M], gfx[K];
-        const long long tbase = (GATHER && src.gathered) ? static_cast<long long>(static_cast<unsigned>(r) / static_cast<unsigned>(rows_per_cloud)) * n_src : 0;
+    // what a lane adds to the wave-uniform row bases: its channel inside the source's row (a dead lane reads the last channel, which
+    // lies in its chunk, and stores nothing), and its M floats of grad_out
+    const bool gathered = GATHER && static_cast<int>(blockIdx.y) * 64 >= c0;   // = src.gathered, from scalars alone
+    const int cc = live ? ch : c - 1;
+    const unsigned stride = static_cast<unsigned>(GATHER ? (gathered ? c - c0 : c0) : c);   // = src.stride
+    const unsigned foff = static_cast<unsigned>(gathered ? cc - c0 : cc) * 4u, goff = static_cast<unsigned>(cc) * (4u * M);
+    unsigned xoff[Q];   // the lane's coefficients of a row's X: one coalesced load per 64
 #pragma unroll
-        for (int j = 0; j < K; ++j) {
-            const long long srow = (GATHER && src.gathered) ? tbase + idx[r * K + j] : r * K + j;
-            fv[j] = live ? src.base[srow * src.stride] : 0.f;
-            if constexpr (BN) xv[j] = 0.f;
+    for (int q = 0; q < Q; ++q) xoff[q] = static_cast<unsigned>(lane + 64 * q < K * K ? lane + 64 * q : K * K - 1) * 4u;
+    float *const gdst = gathered ? grad_gathered : grad_f;   // wave-uniform: where the K input gradients of a (row, channel) go, if asked for
+    // a row's X in the wave's own LDS slot, twice: [0] with the matrix rows of a pair interleaved ({X[k][j], X[k + 1][j]} adjacent, for
+    // F_X on pairs of k) and [1] as it is ({X[k][j], X[k][j + 1]}, for the transposed product on pairs of j); both are read as broadcasts
+    __shared__ float xs[kXcThreads / 64][R][2][K * K];
+    unsigned xpos[Q];   // where the lane's coefficient goes in the interleaved copy
+#pragma unroll
+    for (int q = 0; q < Q; ++q) {
+        const int e = lane + 64 * q < K * K ? lane + 64 * q : K * K - 1, k = e / K, j = e - k * K;
+        xpos[q] = ((k >> 1) * K + j) * 2 + (k & 1);
+    }
+    auto stage = [&](const float (&xr)[R][Q]) {
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");   // the previous batch's reads are done
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int i = 0; i < R; ++i)
+#pragma unroll
+            for (int q = 0; q < Q; ++q)
+                if (lane + 64 * q < K * K) { xs[wave][i][0][xpos[q]] = xr[i][q]; xs[wave][i][1][lane + 64 * q] = xr[i][q]; }
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+    };
+    XcCloud cl = xc_cloud(r0, rows_per_cloud, n_src);
+    constexpr bool PIPE = xc_fw_pipe(K, M, BN);
+    XcFwBatch<K, M, R> cur, nxt;
+    int nidx[R][K];   // the neighbour indices of the batch whose loads are issued next (wave-uniform)
+    auto clamp_rows = [&](long long rb, long long (&rr)[R]) {
+#pragma unroll
+        for (int i = 0; i < R; ++i) rr[i] = rb + 4 * i < r1 ? rb + 4 * i : r1 - 1;
+    };
+    auto load_idx = [&](long long rb) __attribute__((always_inline)) {
+        if (gathered) {
+            long long rr[R];
+            clamp_rows(rb, rr);
+#pragma unroll
+            for (int i = 0; i < R; ++i)
+#pragma unroll
+                for (int j = 0; j < K; ++j) nidx[i][j] = idx[rr[i] * K + j];
         }
-        if constexpr (BN) {
-            if (lifted) {   // a uniform branch behind the loads: z1 -> F_delta, elu(z1) kept for the sums below
+    };
+    auto issue = [&](long long rb, XcFwBatch<K, M, R> &o) __attribute__((always_inline)) {   // every load of a batch, from nidx = its rows' indices
+        long long rr[R];
+        clamp_rows(rb, rr);
 #pragma unroll
-                for (int j = 0; j < K; ++j) {
-                    xv[j] = elu_stream(fv[j]);
+        for (int i = 0; i < R; ++i) {
+            xc_gfloat *xb = xc_sbase(x + rr[i] * (K * K));
+#pragma unroll
+            for (int q = 0; q < Q; ++q) o.x[i][q] = *xc_gat(xb, xc_lane_off(xoff[q]));
+        }
+#pragma unroll
+        for (int i = 0; i < R; ++i) {
+            const unsigned fo = xc_lane_off(foff);
+            if (gathered) {
+                const unsigned tb = xc_tbase_step(cl, rr[i], rows_per_cloud, n_src);
+#pragma unroll
+                for (int j = 0; j < K; ++j)
+                    o.fv[i][j / 2][j % 2] = *xc_gat(xc_sbase(fts + static_cast<unsigned long long>(tb + static_cast<unsigned>(nidx[i][j])) * stride), fo);
+            } else {
+                const float *fl = f + rr[i] * K * static_cast<long long>(stride);
+#pragma unroll
+                for (int j = 0; j < K; ++j) o.fv[i][j / 2][j % 2] = *xc_gat(xc_sbase(fl + j * static_cast<size_t>(stride)), fo);
+            }
+            xc_gload_m<M>(grad_out, xc_gat(xc_sbase(grad_out + rr[i] * c * static_cast<long long>(M)), xc_lane_off(goff)), o.g[i]);
+        }
+    };
+    // one row's products, a pair of k at a time: dF_X[k], F_X[k] (from the interleaved copy of X) and the weight gradient, and, with
+    // GA, the two terms k, k + 1 of the K input gradients (from the plain copy): ga[j] takes its terms in ascending k
+    auto row = [&](auto ga_tag, const float *xr, long long r, const f2 (&fin)[K / 2], const float (&g)[M]) {
+        constexpr bool GA = decltype(ga_tag)::value;
+        f2 fv[K / 2], xv[K / 2];
+        float ga[K];
+#pragma unroll
+        for (int j = 0; j < K / 2; ++j) fv[j] = fin[j];
+        if constexpr (BN) {
+            if (lifted) {   // z1 -> F_delta, elu(z1) kept for the sums below
+#pragma unroll
+                for (int j = 0; j < K / 2; ++j) {
+                    xv[j] = f2{elu_stream(fv[j].x), elu_stream(fv[j].y)};
                     fv[j] = ba * (xv[j] - bmu) + bb;
                 }
             }
         }
-        load_m<M>(grad_out, static_cast<size_t>(r * c + (live ? ch : 0)) * M, g);
-        if (!live) {
+        const f2 *xp = reinterpret_cast<const f2 *>(xr), *xn = reinterpret_cast<const f2 *>(xr + K * K);
+        f2 gap[K / 2];
 #pragma unroll
-            for (int m = 0; m < M; ++m) g[m] = 0.f;
+        for (int kp = 0; kp < K / 2; ++kp) {
+            f2 a = f2{0.f, 0.f};
+#pragma unroll
+            for (int m = 0; m < M; ++m) a = a + g[m] * (WL ? wl[kp * 64 * M + m] : w[WL ? 0 : kp][m]);   // = hf_depthwise_k_grad's dx
+            f2 t = xp[kp * K] * fv[0].x;                                      // F_X recomputed
+#pragma unroll
+            for (int j = 1; j < K; ++j) t = t + xp[kp * K + j] * fv[j / 2][j % 2];
+#pragma unroll
+            for (int m = 0; m < M; ++m) {
+                gw[kp][m] = gw[kp][m] + t * g[m];                             // = hf_depthwise_k_grad's dw
+                asm volatile("" : "+v"(gw[kp][m]));   // here, not behind the stores below, where the compiler moves it with all of X live
+            }
+            if constexpr (GA) {   // = hf_xconv_apply_grad's dF (X transposed): ga[j] takes its K terms in ascending k
+#pragma unroll
+                for (int jp = 0; jp < K / 2; ++jp) gap[jp] = kp == 0 ? xn[jp] * a.x : gap[jp] + xn[2 * kp * (K / 2) + jp] * a.x;
+#pragma unroll
+                for (int jp = 0; jp < K / 2; ++jp) gap[jp] = gap[jp] + xn[(2 * kp + 1) * (K / 2) + jp] * a.y;
+            }
+            __builtin_amdgcn_sched_barrier(0);   // a pair of k at a time: left free, the scheduler reads all of X ahead (64 registers)
         }
+        if constexpr (GA) {
 #pragma unroll
-        for (int k = 0; k < K; ++k) {
-            float a = 0.f;
+            for (int jp = 0; jp < K / 2; ++jp) { ga[2 * jp] = gap[jp].x; ga[2 * jp + 1] = gap[jp].y; }
+            float *gd = gdst + r * K * static_cast<long long>(stride);
+            // ga is complete here in every lane: left to the compiler, the K x K products move behind `live` and with them all of X
 #pragma unroll
-            for (int m = 0; m < M; ++m) a = a + g[m] * w[k][m];          // = hf_depthwise_k_grad's dx
-            gfx[k] = a;
-            float t = xr[k * K] * fv[0];                                  // F_X recomputed
+            for (int j = 0; j < K; ++j) asm volatile("" : "+v"(ga[j]));
+            const unsigned fo = xc_lane_off(foff);
+            if (live) {
 #pragma unroll
-            for (int j = 1; j < K; ++j) t = t + xr[k * K + j] * fv[j];
-#pragma unroll
-            for (int m = 0; m < M; ++m) gw[k][m] = gw[k][m] + t * g[m];   // = hf_depthwise_k_grad's dw
-        }
-        float *gdst = (GATHER && src.gathered) ? (grad_gathered ? grad_gathered + (ch - c0) : nullptr) : (grad_f ? grad_f + ch : nullptr);
-        if (live && gdst) {
-            float ga[K];
-#pragma unroll
-            for (int j = 0; j < K; ++j) {
-                float a = xr[j] * gfx[0];                                  // = hf_xconv_apply_grad's dF (X transposed)
-#pragma unroll
-                for (int k = 1; k < K; ++k) a = a + xr[k * K + j] * gfx[k];
-                gdst[(r * K + j) * src.stride] = a;
-                ga[j] = a;
+                for (int j = 0; j < K; ++j) *xc_gat(xc_sbase(gd + j * static_cast<size_t>(stride)), fo) = ga[j];
             }
             if constexpr (BN) {
-                if (lifted) {   // = bn_bwd_reduce_kernel's sums with dh = the value just stored (behind the stores: inside their loop the sums cost 40 VGPRs)
+                if (lifted) {   // = bn_bwd_reduce_kernel's sums with dh = the value just stored
 #pragma unroll
-                    for (int j = 0; j < K; ++j) { s1 += ga[j]; s2 += ga[j] * ((xv[j] - bmu) * bis); }
+                    for (int j = 0; j < K; ++j) { s1 += ga[j]; s2 += ga[j] * ((xv[j / 2][j % 2] - bmu) * bis); }
                 }
             }
         }
-    }
-    __shared__ float red[K * M][64];
+    };
+    // the row loop, once with the K input gradients and once without: the choice (wave-uniform) is made here, outside the loop, so
+    // that each form keeps its own schedule
+    auto run = [&](auto ga_tag) __attribute__((always_inline)) {
+        const long long rb0 = r0 + wave;
+        if (rb0 < r1) {
+            load_idx(rb0);
+            if constexpr (PIPE) {
+                issue(rb0, cur);
+                load_idx(rb0 + 4 * R);
+            }
+        }
+        for (long long rb = rb0; rb < r1; rb += 4 * R) {
+            if constexpr (PIPE) {   // the next batch's loads ahead of this batch's products (past the end: the last row again, dropped)
+                issue(rb + 4 * R, nxt);
+                load_idx(rb + 8 * R);
+            } else {
+                issue(rb, cur);
+                load_idx(rb + 4 * R);
+            }
+            stage(cur.x);
+#pragma unroll
+            for (int i = 0; i < R; ++i) {
+                if (rb + 4 * i >= r1) break;
+                row(ga_tag, xs[wave][i][0], rb + 4 * i, cur.fv[i], cur.g[i]);
+            }
+            if constexpr (PIPE) cur = nxt;
+        }
+    };
+    if (gdst) run(std::true_type{});
+    else run(std::false_type{});
+    if constexpr (WL) __syncthreads();   // every wave is done with the weights in `red`
     if constexpr (BN) {
         if (lifted && grad_f) {
             // the waves take turns, wave 0 first, on two rows of `red` (a fixed order of adds); the Wd reduction below reuses them
@@ -418,7 +643,7 @@ __global__ __launch_bounds__(kXcThreads) __attribute__((amdgpu_waves_per_eu(BN ?
 #pragma unroll
                 for (int k = 0; k < K; ++k)
 #pragma unroll
-                    for (int m = 0; m < M; ++m) red[k * M + m][lane] = wv == 0 ? gw[k][m] : red[k * M + m][lane] + gw[k][m];
+                    for (int m = 0; m < M; ++m) red[k * M + m][lane] = wv == 0 ? gw[k / 2][m][k % 2] : red[k * M + m][lane] + gw[k / 2][m][k % 2];
             }
             __syncthreads();
         }
@@ -441,24 +666,6 @@ __global__ __launch_bounds__(kXcThreads) __attribute__((amdgpu_waves_per_eu(BN ?
 // the row's neighbours) formed on the scalar side once per row; a lane adds a 32-bit element offset (its channel, plus j * stride
 // inside the row's K x stride block of F), so the loads take their base from scalar registers and no 64-bit product is formed
 // per element.  The offset inside a row is below K c M, whatever the tensor's size: nothing here depends on xdw_offsets_fit.
-
-// the M floats of a (row, channel) pair at p; `arg` is the tensor's first element (a kernel argument), whose alignment decides
-// for every (row, channel) pair alike
-template <int M>
-__device__ __forceinline__ void xc_load_m(const float *arg, const float *p, float (&v)[M])
-{
-    if constexpr (M == 4) {
-        if ((reinterpret_cast<uintptr_t>(arg) & 15) == 0) {
-            const float4 t = *reinterpret_cast<const float4 *>(p);
-            v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-            return;
-        }
-    } else if constexpr (M == 2) {
-        if ((reinterpret_cast<uintptr_t>(arg) & 7) == 0) { const float2 t = *reinterpret_cast<const float2 *>(p); v[0] = t.x; v[1] = t.y; return; }
-    }
-#pragma unroll
-    for (int m = 0; m < M; ++m) v[m] = p[m];
-}
 
 // first table row of row r's cloud; `next` is the first row of the following cloud.  The division runs only when a wave's rows
 // cross into another cloud (rows ascend per wave, by any stride).
@@ -547,12 +754,6 @@ __device__ __forceinline__ void xc_store_dx(float (&acc)[KK], int lane, float *_
         xc_lane_fold<KK, OFF, 16>(acc, lane);
         if ((lane & 3) == 0) dst[OFF + (lane >> 2)] = acc[OFF];
     }
-}
-
-// a float at a wave-uniform base plus a 32-bit byte offset per lane: the load takes the base from scalar registers
-__device__ __forceinline__ const float *xc_at(const float *base, unsigned byte_off)
-{
-    return reinterpret_cast<const float *>(reinterpret_cast<const char *>(base) + byte_off);
 }
 
 // LDS of xconv_*_bwd_x_kernel.  The block's K c M coefficients of Wd are staged once, as [trip][k M + m][64 lanes]: a trip reads its
