@@ -33,4 +33,14 @@ __all__ = [
     "three_nn", "three_interpolate", "project_gather", "rect_to_image",
     "compute_bev_iou", "bev_iou", "oriented_nms", "oriented_nms_batched", "nms_mask",
     "pc_crop_and_sample", "crop_and_resize",
+    "validate_rpn", "validate_rcnn",
 ]
+
+
+def __getattr__(name):
+    # validate.py imports the trainers and loaders: loaded on first use, and `python -m heterofusionrcnn_amd.validate` stays
+    # the first import of that module
+    if name in ("validate_rpn", "validate_rcnn"):
+        from . import validate
+        return getattr(validate, name)
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -127,6 +127,9 @@ _SIGNATURES = {
     "hf_rcnn_targets_workspace": [_i, _i, _i],
     "hf_rcnn_proposal_targets": [_i, _i, _i, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _i, _f, _f, _i, _i] + [_vp] * 6 + [_sz, _vp],
     "hf_box3d_iou_matrix": [_i, _i, _i] + [_vp] * 5 + [_vp],
+    "hf_proposal_stats_workspace": [_i, _i, _i],
+    "hf_proposal_stats": [_i, _i, _i] + [_vp] * 11 + [_vp, _sz, _vp],
+    "hf_argmax_accuracy": [ctypes.c_longlong, _i, _i, _vp, _vp, _vp, _vp],
     "hf_bin_box_decode": [ctypes.c_longlong, _i] + [_vp] * 13 + [_f, _f, _vp, _vp],
     "hf_bin_box_encode": [ctypes.c_longlong, _i, _i] + [_vp] * 7 + [_f, _f, _f, _f] + [_vp] * 8 + [_vp],
     "hf_bin_head_decode": [ctypes.c_longlong, _i, _i, _i, _i] + [_vp] * 6 + [_f, _f, _vp, _vp, _vp],
@@ -169,6 +172,7 @@ _RESTYPES = {
     "hf_rpn_loss_workspace": _sz,
     "hf_rcnn_loss_workspace": _sz,
     "hf_rcnn_targets_workspace": _sz,
+    "hf_proposal_stats_workspace": _sz,
     "hf_oriented_nms_workspace": _sz,
     "hf_bn_workspace": _sz,
     "hf_three_nn_workspace": _sz,

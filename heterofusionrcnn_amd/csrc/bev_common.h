@@ -55,6 +55,14 @@ __device__ __forceinline__ bool in_box2d(const float *box, float ac, float as_ne
     return rx > box[0] - MARGIN && rx < box[2] + MARGIN && ry > box[1] - MARGIN && ry < box[3] + MARGIN;
 }
 
+// iou_bev(box_a, box_b, s_overlap), bev_iou_g.cu:208-215, for two [x1, y1, x2, y2, angle] boxes
+__device__ __forceinline__ float iou_from_overlap(const float *a, const float *b, float s)
+{
+    const float sa = (a[2] - a[0]) * (a[3] - a[1]);
+    const float sb = (b[2] - b[0]) * (b[3] - b[1]);
+    return s / fmaxf(sa + sb - s, kIouEps);
+}
+
 // rotate_around_center, bev_iou_g.cu:92-96
 __device__ __forceinline__ Pt rot_center(Pt c, float ac, float as, Pt p)
 {

@@ -187,13 +187,7 @@ __device__ float box_overlap_group(const BoxPre &pa, const BoxPre &pb, ClipScrat
     return fabsf(area) / 2.0f;
 }
 
-// iou_bev(box_a, box_b, s_overlap), bev_iou_g.cu:208-215
-__device__ __forceinline__ float iou_from_overlap(const float *a, const float *b, float s)
-{
-    const float sa = (a[2] - a[0]) * (a[3] - a[1]);
-    const float sb = (b[2] - b[0]) * (b[3] - b[1]);
-    return s / fmaxf(sa + sb - s, kIouEps);
-}
+// iou_from_overlap (iou_bev, bev_iou_g.cu:208-215) lives in bev_common.h, shared with box3d_common.h.
 
 // ---------------------------------------------------------------- 64 x 64 pair tiles
 

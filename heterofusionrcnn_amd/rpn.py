@@ -484,7 +484,8 @@ class RpnModel(nn.Module):
         ind = keep[:, :post_nms_size].long()
         return {"proposals": torch.gather(top_b, 1, ind.unsqueeze(-1).expand(-1, -1, 7)), "proposal_scores": torch.gather(top_s, 1, ind),
                 "num_before_padding": torch.clamp(num, max=post_nms_size), "rpn_fts": fused, "fg_mask": fg_mask, "point_scores": scores,
-                "pre_nms_boxes": top_b, "pre_nms_scores": top_s, "keep": keep, "num_kept": num}
+                "pre_nms_boxes": top_b, "pre_nms_scores": top_s, "keep": keep, "num_kept": num,
+                "seg_logits": seg_logits, "head": head}     # what forward() returns: validate.py takes its loss from them
 
     def loss(self, xyz, seg_logits, head, label_cls, label_reg, fused=None):
         """fused (default: on the device in fp32): the two-pass HIP loss; else the op-by-op torch form it is tested against"""

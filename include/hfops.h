@@ -613,6 +613,35 @@ int hf_rcnn_proposal_targets(int b, int m, int g, const float *proposals, const 
  * j >= gt_count[f] are 0.  Limits as hf_rcnn_proposal_targets: b <= 1024, 1 <= m <= 512, g <= 128. */
 int hf_box3d_iou_matrix(int b, int m, int g, const float *proposals, const int *proposal_count, const float *gt,
                         const int *gt_count, float *iou, hf_stream_t stream);
+/* The proposal statistics of a validation run (hf/core/evaluator.py:984-1064): compute_iou.box3d_iou_tf, then
+ * box_util.compute_recall_iou (hf/core/box_util.py:131-174), per frame.  proposals (b, m, 7), gt (b, g, 8) [box, cls] as
+ * hf_box3d_iou_matrix, proposal_count / gt_count (b) the valid rows / columns.  Every valid pair is clipped once; from that
+ * BEV overlap come
+ *   iou3d (b, m, g), optional (NULL: not written): bit for bit hf_box3d_iou_matrix, zeros in the padding;
+ *   iou2d (b, m, g), optional: the BEV IoU, bit for bit hf_compute_bev_iou of the two boxes3d_to_bev rows, zeros in the padding;
+ *   best_iou3d, best_iou2d (b, m): the row maxima over the valid GT; best_gt (b, m) int32: the FIRST argmax of the 3D row
+ *     (np.argmax: an all-zero row gives 0); 0 / 0 / -1 for rows >= proposal_count and in frames with gt_count 0;
+ *   counts (b, 4) int32: proposal_count, gt_count (both clamped to [0, m] / [0, g]), the GT whose column maximum of the 3D IoU
+ *     over the valid proposals is > 0.5, the same for > 0.7 (strict, as the reference);
+ *   sums (b, 3) fp64: sum of best_iou2d, sum of best_iou3d, sum of |ry of the proposal - ry of gt[best_gt]| (the difference in
+ *     fp32), each over the valid proposals, accumulated in fp64 in a fixed order.
+ * Deviation from the reference: a frame with gt_count 0 contributes 0 to all three sums; the reference's angle term of such
+ * a frame is sum |ry| against an all-zero box.
+ * Every output element is written by the call (nothing needs zeroing before); no floating-point atomics: two calls give the
+ * same bits.  Two launches: (frame, tile of 256 pairs) workgroups, then one workgroup per frame.  g = 0 is legal with gt NULL.
+ * Limits as hf_box3d_iou_matrix: b <= 1024, 1 <= m <= 512, g <= 128; outside them HF_EINVAL, nothing launched.
+ * workspace: hf_proposal_stats_workspace(b, m, g) bytes (0 for arguments outside the limits, and when b * g is 0). */
+size_t hf_proposal_stats_workspace(int b, int m, int g);
+int hf_proposal_stats(int b, int m, int g, const float *proposals, const int *proposal_count, const float *gt,
+                      const int *gt_count, float *iou3d, float *iou2d, float *best_iou3d, float *best_iou2d, int *best_gt,
+                      int *counts, double *sums, void *workspace, size_t workspace_bytes, hf_stream_t stream);
+/* calculate_cls_accuracy (hf/core/evaluator.py:917-932) as counts: logits (rows, c) fp32, target (rows) int32 ->
+ * correct (groups) int32, per group of rows / groups consecutive rows the number of rows whose first argmax equals
+ * max(target, 0) (a negative target is the reference's all-zero one-hot row, whose argmax is 0).  correct is cleared by the
+ * call.  Finite logits are the caller's contract.  Limits: rows >= 0, 2 <= c <= 8, groups >= 1, rows divisible by groups;
+ * otherwise HF_EINVAL. */
+int hf_argmax_accuracy(long long rows, int c, int groups, const float *logits, const int *target, int *correct,
+                       hf_stream_t stream);
 /* hf/core/bin_based_box3d_encoder.py:9-139 (tf_decode) for `rows` reference points x k classes: rows = B*p in the RPN
  * (ref_theta NULL = the constant 0), the RoI count in the RCNN.  Per (row, class) inputs are (rows, k[, 3]) arrays;
  * ss / deltas (k,) the per-class XZ search range and bin length; boxes (rows, k, 7) = [x, y, z, l, w, h, ry]. */
