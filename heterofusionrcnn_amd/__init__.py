@@ -26,6 +26,7 @@ from .interpolate import three_interpolate, three_nn  # noqa: E402
 from .fusion import project_gather, rect_to_image  # noqa: E402
 from .bev_iou import bev_iou, compute_bev_iou, nms_mask, oriented_nms, oriented_nms_batched  # noqa: E402
 from .cropping import crop_and_resize, pc_crop_and_sample  # noqa: E402
+from .determinism import deterministic  # noqa: E402
 
 __all__ = [
     "farthest_point_sample", "gather_point", "prob_sample",
@@ -33,7 +34,7 @@ __all__ = [
     "three_nn", "three_interpolate", "project_gather", "rect_to_image",
     "compute_bev_iou", "bev_iou", "oriented_nms", "oriented_nms_batched", "nms_mask",
     "pc_crop_and_sample", "crop_and_resize",
-    "validate_rpn", "validate_rcnn",
+    "validate_rpn", "validate_rcnn", "deterministic",
 ]
 
 

@@ -143,6 +143,8 @@ _SIGNATURES = {
     "hf_depthwise_k_grad_ws": [ctypes.c_longlong, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
     "hf_xconv_depthwise": [ctypes.c_longlong, _i, _i, _i, _vp, _vp, _vp, _vp, _vp],
     "hf_xconv_depthwise_grad": [ctypes.c_longlong, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "hf_xconv_depthwise_grad_workspace": [ctypes.c_longlong, _i, _i, _i],
+    "hf_xconv_depthwise_grad_ws": [ctypes.c_longlong, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
     "hf_xconv_depthwise_gather": [_i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "hf_xconv_depthwise_gather_grad": [_i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                        _vp, _sz, _vp],
@@ -181,6 +183,7 @@ _RESTYPES = {
     "hf_linear_bf16_wgrad_workspace": _sz,
     "hf_linear_bn_fwd_workspace": _sz,
     "hf_linear_bn_bwd_workspace": _sz,
+    "hf_xconv_depthwise_grad_workspace": _sz,
     "hf_xconv_depthwise_gather_grad_workspace": _sz,
     "hf_xconv_depthwise_gather_bn_grad_workspace": _sz,
     "hf_lift_elu_bn_fwd_workspace": _sz,

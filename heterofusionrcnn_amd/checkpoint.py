@@ -159,6 +159,9 @@ def add_run_arguments(ap, saved):
     ap.add_argument("--workers", type=int, default=8, help="host threads that read and decode the files")
     ap.add_argument("--lr", type=float, default=1e-3)
     ap.add_argument("--no-graph", action="store_true", help="eager steps instead of the captured hipGraph")
+    ap.add_argument("--deterministic", action="store_true",
+                    help="bit-reproducible training: every route whose sum has no fixed order is refused; the configurations that fuse the "
+                         "image (train_rcnn, train_rpn --config rpn_multiclass) do not run under it")
 
 
 def add_train_op_arguments(ap, config_file):

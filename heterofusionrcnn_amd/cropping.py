@@ -5,6 +5,7 @@ import torch
 
 from . import _lib
 from ._lib import check, dev_tensor, ptr, require, stream_ptr
+from .determinism import refuse_unordered
 
 
 def pc_crop_and_sample(pts, fts, intensities, mask, boxes, box_ind, resize):
@@ -62,6 +63,7 @@ def pc_crop_and_sample_grad_fts(fts, box_ind, crop_ind, grad_crop_fts):
             "PcCropAndSampleGradFts expects box_ind, crop_ind and grad_crop_fts has same shape(0)")
     require(crop_ind.shape[1] == grad_crop_fts.shape[1],
             "PcCropAndSampleGradFts expects crop_ind and grad_crop_fts has same shape(1)")
+    refuse_unordered("pc_crop_and_sample_grad_fts", "atomic adds into the feature table")
     box_ind = dev_tensor(box_ind, torch.int32, "box_ind")
     crop_ind = dev_tensor(crop_ind, torch.int32, "crop_ind")
     grad_crop_fts = dev_tensor(grad_crop_fts.detach(), torch.float32, "grad_crop_fts")

@@ -792,6 +792,26 @@ HF_API int hf_xconv_depthwise_grad(long long rows, int k, int c, int m, const fl
     return xdw_backward(rows, k, c, c, m, x, f, nullptr, nullptr, 0, 1, wd, grad_out, grad_x, grad_f, nullptr, grad_wd, as_stream(stream));
 }
 
+// one row of k * c * m partial weight sums per row chunk of the F / Wd gradient kernel
+HF_API size_t hf_xconv_depthwise_grad_workspace(long long rows, int k, int c, int m)
+{
+    if (rows <= 0 || k <= 0 || c <= 0 || m <= 0) return 0;
+    dim3 grid;
+    int rpb;
+    xdw_bwd_grid(rows, c, grid, rpb);
+    return sizeof(float) * static_cast<size_t>(grid.x) * k * c * m;
+}
+
+HF_API int hf_xconv_depthwise_grad_ws(long long rows, int k, int c, int m, const float *x, const float *f, const float *wd,
+                                      const float *grad_out, float *grad_x, float *grad_f, float *grad_wd, void *workspace,
+                                      size_t workspace_bytes, hf_stream_t stream)
+{
+    if (rows < 0 || c <= 0 || !x || !f || !wd || !grad_out || (!grad_x && !grad_f && !grad_wd)) return HF_EINVAL;
+    if (grad_wd && rows > 0 && (!workspace || workspace_bytes < hf_xconv_depthwise_grad_workspace(rows, k, c, m))) return HF_EWORKSPACE;
+    return xdw_backward(rows, k, c, c, m, x, f, nullptr, nullptr, 0, 1, wd, grad_out, grad_x, grad_f, nullptr, grad_wd, as_stream(stream),
+                        grad_wd ? static_cast<float *>(workspace) : nullptr);
+}
+
 HF_API int hf_xconv_depthwise_gather(int b, int n_src, int rows_per_cloud, int k, int c0, int c1, int m, const float *x,
                                      const float *f_delta, const float *fts, const int *idx, const float *wd, float *out,
                                      hf_stream_t stream)

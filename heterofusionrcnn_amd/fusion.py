@@ -9,6 +9,7 @@ import torch
 
 from . import _lib
 from ._lib import check, dev_tensor, ptr, require, stream_ptr
+from .determinism import refuse_unordered
 
 
 def rect_to_image(pts3d, calib):
@@ -56,6 +57,8 @@ def project_gather(pts3d, calib, img_fts, return_pixels=False):
     pts3d = dev_tensor(pts3d.detach(), torch.float32, "pts3d")
     calib = dev_tensor(calib.detach(), torch.float32, "calib")
     img_fts = dev_tensor(img_fts, torch.float32, "img_fts")
+    if img_fts.requires_grad and torch.is_grad_enabled():
+        refuse_unordered("project_gather", "the gradient of the image features is an atomic scatter: many points fall on one pixel")
     out, pix = _ProjectGather.apply(img_fts, pts3d, calib)
     return (out, pix) if return_pixels else out
 
@@ -153,6 +156,8 @@ def project_boxes_to_image(boxes_3d, calib, image_hw):
         b, n, _ = boxes_3d.shape
         box, norm, _ = _roi_image_boxes(boxes_3d, calib, image_hw, True, True, False)
         return box.view(b, n, 4), norm.view(b, n, 4)
+    if boxes_3d.is_cuda and wants_grad:
+        refuse_unordered("project_boxes_to_image", "the tensor form on device tensors with a gradient")
     return _project_boxes_to_image_tensor(boxes_3d, calib, image_hw)
 
 
@@ -210,8 +215,12 @@ def image_crop_and_resize(img_fts, boxes_norm_yxyx, box_ind, crop_size, extrapol
     if _on_device_f32(img_fts, boxes_norm_yxyx) and box_ind.is_cuda:
         require(img_fts.dim() == 4 and boxes_norm_yxyx.dim() == 2 and boxes_norm_yxyx.shape[1] == 4
                 and box_ind.shape == boxes_norm_yxyx.shape[:1], "image_crop_and_resize expects (B,H,W,C), (N,4) boxes and (N) box_ind")
+        if img_fts.requires_grad and torch.is_grad_enabled():
+            refuse_unordered("image_crop_and_resize", "the gradient of the image features is an atomic scatter: RoIs overlap")
         return _CropAndResize.apply(img_fts.contiguous(), boxes_norm_yxyx.detach().contiguous(),
                                     box_ind.detach().to(torch.int32).contiguous(), int(crop_size), float(extrapolation_value))
+    if img_fts.is_cuda and img_fts.requires_grad and torch.is_grad_enabled():
+        refuse_unordered("image_crop_and_resize", "the tensor form on device tensors: its index gradient adds atomically")
     return _image_crop_and_resize_tensor(img_fts, boxes_norm_yxyx, box_ind, crop_size, extrapolation_value)
 
 

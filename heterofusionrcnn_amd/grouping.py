@@ -3,6 +3,7 @@ import torch
 
 from . import _lib
 from ._lib import check, dev_tensor, ptr, require, stream_ptr
+from .determinism import record, refuse_unordered
 
 
 BALL_QUERY_VARIANTS = {"auto": 0, "cell": 1, "bruteforce": 2, "sorted": 3}   # HF_BQ_* of include/hfops.h
@@ -51,10 +52,11 @@ def gather_rows_into(points, idx, out, col):
           "group_point_into")
 
 
-def gather_rows_grad(grad_out, col, idx, n, c, inverse=None):
+def gather_rows_grad(grad_out, col, idx, n, c, inverse=None, ctx=None):
     """the gradient of that gather w.r.t. points, (B,N,C), read in place from columns col.. of grad_out (B,M,K,width) contiguous:
     by the inverse index (offsets, entries) = index_inverse(idx, N) where it came with the geometry -- every row written once,
-    no atomics -- else scattered with atomics into a zero-filled target"""
+    no atomics -- else scattered with atomics into a zero-filled target (ctx: the calling Function's, whose forward recorded the
+    deterministic mode: under it the scatter is refused)"""
     b, m, ns = idx.shape
     width = grad_out.shape[-1]
     g = torch.empty((b, n, c), dtype=torch.float32, device=grad_out.device)
@@ -63,6 +65,8 @@ def gather_rows_grad(grad_out, col, idx, n, c, inverse=None):
         check(_lib.lib().hf_group_point_grad_gather(b, n, c, m, ns, width, col, ptr(grad_out), ptr(offsets), ptr(entries), ptr(g),
                                                     stream_ptr()), "group_point_grad_gather")
     else:
+        if ctx is not None:
+            refuse_unordered("gather_rows_grad", "no inverse index: n = %d, index_inverse takes up to %d targets" % (n, INVERSE_MAX_TARGETS), ctx)
         check(_lib.lib().hf_group_point_grad_from(b, n, c, m, ns, width, col, ptr(grad_out), ptr(idx), ptr(g), stream_ptr()),
               "group_point_grad_from")
     return g
@@ -76,6 +80,7 @@ class _GroupPoint(torch.autograd.Function):
         out = torch.empty((b, m, ns, c), dtype=torch.float32, device=points.device)
         # dense rows: hf_group_point also has the form for power-of-two widths, which the column-slice entry does not take
         check(_lib.lib().hf_group_point(b, n, c, m, ns, ptr(points), ptr(idx), ptr(out), stream_ptr()), "group_point")
+        record(ctx)
         ctx.save_for_backward(idx)
         ctx.shape = (b, n, c)
         return out
@@ -84,7 +89,7 @@ class _GroupPoint(torch.autograd.Function):
     def backward(ctx, grad_out):
         (idx,) = ctx.saved_tensors
         b, n, c = ctx.shape
-        return gather_rows_grad(grad_out.contiguous(), 0, idx, n, c), None
+        return gather_rows_grad(grad_out.contiguous(), 0, idx, n, c, ctx=ctx), None
 
 
 def group_point(points, idx):
@@ -127,6 +132,7 @@ class _ConcatGroup(torch.autograd.Function):
         out = torch.empty((b, m, ns, ch + c), dtype=torch.float32, device=points.device)
         out[..., :ch].copy_(head)
         gather_rows_into(points, idx, out, ch)
+        record(ctx)
         ctx.save_for_backward(idx, *([offsets, entries] if offsets is not None else []))
         ctx.shape = (b, n, c, ch)
         return out
@@ -138,7 +144,7 @@ class _ConcatGroup(torch.autograd.Function):
         grad_out = grad_out.contiguous()
         g = None
         if ctx.needs_input_grad[1]:   # with the inverse index of the geometry: gather, every row written once
-            g = gather_rows_grad(grad_out, ch, idx, n, c, ctx.saved_tensors[1:] or None)
+            g = gather_rows_grad(grad_out, ch, idx, n, c, ctx.saved_tensors[1:] or None, ctx=ctx)
         return (grad_out[..., :ch] if ctx.needs_input_grad[0] else None), g, None, None, None
 
 

@@ -3,6 +3,7 @@ import torch
 
 from . import _lib
 from ._lib import check, dev_tensor, ptr, require, stream_ptr
+from .determinism import refuse_unordered
 
 
 def three_nn(xyz1, xyz2):
@@ -180,6 +181,9 @@ def three_interpolate(points, idx, weight, inverse=None):
                 "ThreeInterpolate expects the inverse of this idx: offsets (b,m+1), entries (b,3n)")
         return _ThreeInterpolateInv.apply(points, idx, weight, dev_tensor(offsets, torch.int32, "offsets"),
                                           dev_tensor(entries, torch.int32, "entries"))
+    if points.requires_grad and torch.is_grad_enabled():
+        refuse_unordered("three_interpolate", "no inverse index: m = %d, three_nn_inverse takes up to %d known points"
+                         % (points.shape[1], INVERSE_MAX_KNOWN))
     return _ThreeInterpolate.apply(points, idx, weight)
 
 
@@ -201,6 +205,7 @@ def three_interpolate_channel_first(points, idx, weight):
 def three_interpolate_channel_first_grad(points_shape, idx, weight, grad_out):
     """ThreeInterpolateGrad op (tf_interpolate.cpp:39-48): grad_out (B,C,N) -> grad_points (B,C,M)."""
     b, c, m = points_shape
+    refuse_unordered("three_interpolate_channel_first_grad", "atomic adds into the known points")
     idx = dev_tensor(idx, torch.int32, "idx")
     weight = dev_tensor(weight.detach(), torch.float32, "weight")
     grad_out = dev_tensor(grad_out.detach(), torch.float32, "grad_out")

@@ -15,6 +15,7 @@ from . import _dense_kernels as _k
 from . import _lib
 from ._dense_kernels import _STATS_GENERATION, Running, running_stats_written  # noqa: F401  (re-exported: the counter lives there)
 from ._lib import check, ptr, stream_ptr
+from .determinism import record as record_deterministic
 from .grouping import gather_rows_grad
 
 
@@ -546,6 +547,7 @@ class _GatherLinear(torch.autograd.Function):
         c, n_src = (points.shape[2], points.shape[1]) if points is not None else (0, 1)
         z, mean, invstd = _k.linear_bn_fwd_gather(points, idx, gxyz, _gather_weight(weight, c, xyz_first), bias, bn, update_running)
         ctx.save_for_backward(idx, gxyz, weight, *([points] if points is not None else []))
+        record_deterministic(ctx)
         ctx.dims = (b, m, k, c, n_src, weight.shape[0], xyz_first)
         ctx.mark_non_differentiable(mean, invstd)
         return z, mean, invstd
@@ -561,7 +563,7 @@ class _GatherLinear(torch.autograd.Function):
         if points is not None and ctx.needs_input_grad[0]:
             wf = (weight[:, 3:3 + c] if xyz_first else weight[:, :c]).contiguous()
             dg = dz @ wf                                               # (rows, c): the gradient of the gathered features
-            dpoints = gather_rows_grad(dg, 0, idx, n_src, c)
+            dpoints = gather_rows_grad(dg, 0, idx, n_src, c, ctx=ctx)
         # the bias feeds a BatchNorm: its gradient is exactly zero (see _SharedMLPChain.backward)
         return dpoints, None, None, dw, torch.zeros((cout,), dtype=torch.float32, device=dz.device), None, None, None
 

@@ -31,6 +31,7 @@ import torch.nn.functional as F
 
 from . import _lib
 from ._lib import check, ptr, require, stream_ptr
+from .determinism import record, refuse_unordered
 from .grouping import INVERSE_MAX_TARGETS, concat_group, gather_rows_grad, gather_rows_into, group_point, index_inverse, knn_point
 from .sampling import farthest_point_sample, gather_point
 from . import _dense_kernels as _k
@@ -189,6 +190,7 @@ class _BNConcatGroup(torch.autograd.Function):
         out = torch.empty((b, m, ns, width), dtype=torch.float32, device=z.device)
         _, mean, invstd = _k.bn_fwd_train(z, gamma, beta, _k.Running(running_mean, running_var, eps, momentum), mode, out=out, ld=width)
         gather_rows_into(points, idx, out, ch)
+        record(ctx)
         ctx.save_for_backward(z, gamma, beta, mean, invstd, idx, *([offsets, entries] if offsets is not None else []))
         ctx.meta = (b, n, c, m, ns, ch, mode)
         return out
@@ -202,7 +204,7 @@ class _BNConcatGroup(torch.autograd.Function):
         dz, dgamma, dbeta, _ = _k.bn_bwd(z, go, gamma, beta, mean, invstd, mode, ld=width)
         g = None
         if ctx.needs_input_grad[8]:
-            g = gather_rows_grad(go, ch, idx, n, c, ctx.saved_tensors[6:] or None)
+            g = gather_rows_grad(go, ch, idx, n, c, ctx.saved_tensors[6:] or None, ctx=ctx)
         return dz, dgamma, dbeta, None, None, None, None, None, g, None, None, None
 
 
@@ -324,6 +326,7 @@ class _XConvDepthwise(torch.autograd.Function):
         check(_lib.lib().hf_xconv_depthwise(f2.shape[0], k, c, m, ptr(x2), ptr(f2), ptr(w), ptr(out), stream_ptr()),
               "xconv_depthwise")
         ctx.save_for_backward(x2, f2, w)
+        record(ctx)
         ctx.shapes = (tuple(x.shape), tuple(f.shape))
         return out.reshape(*f.shape[:-2], c * m)
 
@@ -335,8 +338,16 @@ class _XConvDepthwise(torch.autograd.Function):
         gx = torch.empty_like(x2) if ctx.needs_input_grad[0] else None
         gf = torch.empty_like(f2) if ctx.needs_input_grad[1] else None
         gw = torch.empty_like(w) if ctx.needs_input_grad[2] else None
-        check(_lib.lib().hf_xconv_depthwise_grad(f2.shape[0], k, c, m, ptr(x2), ptr(f2), ptr(w), ptr(go), ptr(gx), ptr(gf),
-                                                 ptr(gw), stream_ptr()), "xconv_depthwise_grad")
+        L = _lib.lib()
+        if gw is not None and ctx.hf_deterministic and f2.shape[0] > 0:
+            # deterministic mode (as the forward recorded it): the row chunks' partial weight gradients meet in a workspace in a fixed order, not in atomics
+            nbytes = L.hf_xconv_depthwise_grad_workspace(f2.shape[0], k, c, m)
+            ws = torch.empty((nbytes // 4,), dtype=torch.float32, device=go.device)
+            check(L.hf_xconv_depthwise_grad_ws(f2.shape[0], k, c, m, ptr(x2), ptr(f2), ptr(w), ptr(go), ptr(gx), ptr(gf), ptr(gw), ptr(ws),
+                                               nbytes, stream_ptr()), "xconv_depthwise_grad_ws")
+        else:
+            check(L.hf_xconv_depthwise_grad(f2.shape[0], k, c, m, ptr(x2), ptr(f2), ptr(w), ptr(go), ptr(gx), ptr(gf), ptr(gw), stream_ptr()),
+                  "xconv_depthwise_grad")
         sx, sf = ctx.shapes
         return (gx.reshape(sx) if gx is not None else None), (gf.reshape(sf) if gf is not None else None), gw
 
@@ -439,6 +450,8 @@ FOLD_LIFT_BN = True
 def xconv_depthwise_gather(x, f_delta, fts, idx, wd, inverse=None, use_workspace=True):
     """xconv_depthwise(x, [f_delta | fts[idx]], wd) without the concatenation in memory.  x (B,P,K,K), f_delta (B,P,K,C0),
     fts (B,N,C1), idx (B,P,K) int32, wd (K, C0+C1, M); inverse = index_inverse(idx, N) when fts needs a gradient"""
+    if not use_workspace and torch.is_grad_enabled() and (fts.requires_grad or wd.requires_grad):
+        refuse_unordered("xconv_depthwise_gather", "use_workspace=False: atomic sums of the feature and weight gradients")
     off, ent = inverse if inverse is not None else (None, None)
     return _XConvDepthwiseGather.apply(x, f_delta, fts, idx, off, ent, wd, use_workspace)
 

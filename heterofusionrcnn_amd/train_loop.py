@@ -13,16 +13,26 @@ import time
 import torch
 
 from . import checkpoint as ckpt_mod
+from .determinism import deterministic as deterministic_mode, is_deterministic
 from .graph_step import TrainStep
 from .optim import MultiTensorAdam
 from .pipeline import GeometryPrefetcher
 
 
 def run(stage, steps, seed, save, log_every, lr, graph, log, clip_norm, lr_decay, tf_epsilon, check_numerics, checkpoint_dir,
-        checkpoint_every, max_checkpoints, resume, precision):
+        checkpoint_every, max_checkpoints, resume, precision, deterministic=False):
     """-> (list of the per-step losses of this run, floats read at the end; stage.finish(the loader's final status, log))
 
-    The arguments are train_rpn.train's, which documents them; the caller runs under mlp.training_precision(precision)."""
+    The arguments are train_rpn.train's, which documents them; the caller runs under mlp.training_precision(precision).  deterministic: the
+    whole run -- the capture and every step -- is inside determinism.deterministic(True): no route whose sum has no fixed
+    order runs; two runs from one state then give the same bits ("Reproducible training")."""
+    with deterministic_mode(deterministic or is_deterministic()):       # a caller's own scope stays on
+        return _run(stage, steps, seed, save, log_every, lr, graph, log, clip_norm, lr_decay, tf_epsilon, check_numerics, checkpoint_dir,
+                    checkpoint_every, max_checkpoints, resume, precision)
+
+
+def _run(stage, steps, seed, save, log_every, lr, graph, log, clip_norm, lr_decay, tf_epsilon, check_numerics, checkpoint_dir,
+         checkpoint_every, max_checkpoints, resume, precision):
     settings = ckpt_mod.train_op_settings(lr, lr_decay, clip_norm, tf_epsilon, precision)
     ck = None
     if resume:

@@ -14,6 +14,7 @@ import sys
 
 from . import checkpoint as ckpt_mod
 from . import train_loop
+from .determinism import IMAGE_CONFIGS_REFUSED, is_deterministic, refuse_image_config
 from .inference import ImgVggPyr
 from .mlp import under_training_precision
 from .rcnn import RcnnConfig, RcnnModel
@@ -62,13 +63,17 @@ class RcnnStage:
 def train(dataset_dir, handoff_dir, split="train", steps=100, batch=2, seed=0, save=None, log_every=10, workers=8, lr=1e-3,
           graph=True, img_conv=None, aug_list=None, log=print, clip_norm=0.0, lr_decay=None, tf_epsilon=False, check_numerics=False,
           checkpoint_dir=None, checkpoint_every=ckpt_mod.CHECKPOINT_INTERVAL, max_checkpoints=None, resume=False,
-          precision="fp32"):
+          precision="fp32", deterministic=False):
     """-> (list of the per-step losses of this run, read at the end; the trainer)
-    The train-op, checkpoint, resume and precision keywords are train_rpn.train's (`steps` is the final global step when resuming)."""
+    The train-op, checkpoint, resume, precision and deterministic keywords are train_rpn.train's (`steps` is the final global step when resuming);
+    the RCNN fuses the image, so deterministic=True is refused before anything is built."""
+    if deterministic or is_deterministic():
+        refuse_image_config("train_rcnn")
     stage = RcnnStage(img_conv, dataset_dir=dataset_dir, handoff_dir=handoff_dir, split=split, batch=batch, seed=seed, aug_list=aug_list,
                       workers=workers)
     return train_loop.run(stage, steps, seed, save, log_every, lr, graph, log, clip_norm, lr_decay, tf_epsilon, check_numerics,
-                          checkpoint_dir, checkpoint_every, max_checkpoints, resume, precision)
+                          checkpoint_dir, checkpoint_every, max_checkpoints, resume, precision,
+                          deterministic=deterministic)
 
 
 def build_parser():
@@ -83,9 +88,12 @@ def build_parser():
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    ap = build_parser()
+    args = ap.parse_args(argv)
+    if args.deterministic:
+        ap.error("--deterministic: " + IMAGE_CONFIGS_REFUSED)
     losses, _ = train(args.dataset_dir, args.handoff_dir, args.split, args.steps, args.batch, args.seed, args.save, args.log_every,
-                      args.workers, graph=not args.no_graph, **ckpt_mod.train_op_kwargs(args))
+                      args.workers, graph=not args.no_graph, deterministic=args.deterministic, **ckpt_mod.train_op_kwargs(args))
     if losses:
         print("done: %d steps, first loss %.5f, last loss %.5f" % (len(losses), losses[0], losses[-1]))
     else:

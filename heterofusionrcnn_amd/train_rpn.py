@@ -17,6 +17,7 @@ import sys
 from . import checkpoint as ckpt_mod
 from . import rpn as rpn_mod
 from . import train_loop
+from .determinism import IMAGE_CONFIGS_REFUSED, is_deterministic, refuse_image_config
 from .graph_step import rpn_loss_parts
 from .inference import CLASSES, ImgVggPyr
 from .kitti_data import KittiRpnBatches
@@ -76,17 +77,22 @@ class RpnStage:
 def train(dataset_dir, split="train", steps=100, batch=8, config="rpn_multiclass", seed=0, save=None, log_every=10, workers=8,
           lr=1e-3, graph=True, img_conv=None, num_points=16384, log=print, clip_norm=0.0, lr_decay=None, tf_epsilon=False,
           check_numerics=False, checkpoint_dir=None, checkpoint_every=ckpt_mod.CHECKPOINT_INTERVAL, max_checkpoints=None, resume=False,
-          precision="fp32"):
+          precision="fp32", deterministic=False):
     """-> (list of the per-step losses of this run, floats read at the end; the loader status)
     clip_norm / lr_decay / tf_epsilon: optim.MultiTensorAdam's (ckpt_mod.reference_train_op() holds the reference's values);
     check_numerics: a NaN / Inf loss raises FloatingPointError at the next log point (always before a checkpoint is written);
     checkpoint_dir: a checkpoint every checkpoint_every global steps, the newest max_checkpoints kept; resume: continue from the
     newest checkpoint there, `steps` then being the final global step.  precision "bf16": the wide dense layers train on the bf16
-    matrix cores (the whole call runs under mlp.training_precision); a checkpoint resumes only at the precision it was written at."""
+    matrix cores (the whole call runs under mlp.training_precision); a checkpoint resumes only at the precision it was written at.
+    deterministic: the run is inside determinism.deterministic(True) (bit-reproducible: train_loop.run); rpn_multiclass_points only:
+    the config that fuses the image is refused before anything is built."""
+    if (deterministic or is_deterministic()) and config == "rpn_multiclass":
+        refuse_image_config("train_rpn, config rpn_multiclass")
     stage = RpnStage(config, img_conv, dataset_dir=dataset_dir, split=split, classes=CLASSES, batch=batch, num_points=num_points,
                      seed=seed, workers=workers)
     return train_loop.run(stage, steps, seed, save, log_every, lr, graph, log, clip_norm, lr_decay, tf_epsilon, check_numerics,
-                          checkpoint_dir, checkpoint_every, max_checkpoints, resume, precision)
+                          checkpoint_dir, checkpoint_every, max_checkpoints, resume, precision,
+                          deterministic=deterministic)
 
 
 def build_parser():
@@ -100,9 +106,12 @@ def build_parser():
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    ap = build_parser()
+    args = ap.parse_args(argv)
+    if args.deterministic and args.config == "rpn_multiclass":
+        ap.error("--deterministic with --config rpn_multiclass: " + IMAGE_CONFIGS_REFUSED)
     losses, st = train(args.dataset_dir, args.split, args.steps, args.batch, args.config, args.seed, args.save, args.log_every,
-                       args.workers, graph=not args.no_graph, **ckpt_mod.train_op_kwargs(args))
+                       args.workers, graph=not args.no_graph, deterministic=args.deterministic, **ckpt_mod.train_op_kwargs(args))
     if losses:
         print("done: %d steps, first loss %.5f, last loss %.5f, status %s" % (len(losses), losses[0], losses[-1], st))
     else:

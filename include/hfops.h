@@ -690,6 +690,14 @@ int hf_xconv_depthwise_grad(long long rows, int k, int c, int m, const float *x,
                             const float *grad_out, float *grad_x, float *grad_f, float *grad_wd, hf_stream_t stream);
 int hf_depthwise_k_grad(long long rows, int k, int c, int m, const float *x, const float *w, const float *grad_y,
                         float *grad_x, float *grad_w, hf_stream_t stream);
+/* hf_xconv_depthwise_grad with the row chunks' partial weight gradients written to a workspace (hf_xconv_depthwise_grad_workspace
+ * bytes: one row of k c m floats per row chunk) and added in a fixed order, as hf_xconv_depthwise_gather_grad does with its
+ * workspace: no atomics, two calls give the same bits of grad_wd; grad_x and grad_f as before.  HF_EWORKSPACE: grad_wd is asked for
+ * and the workspace is missing or too small. */
+size_t hf_xconv_depthwise_grad_workspace(long long rows, int k, int c, int m);
+int hf_xconv_depthwise_grad_ws(long long rows, int k, int c, int m, const float *x, const float *f, const float *wd,
+                               const float *grad_out, float *grad_x, float *grad_f, float *grad_wd, void *workspace,
+                               size_t workspace_bytes, hf_stream_t stream);
 /* the same with a workspace (hf_depthwise_k_grad_workspace bytes): the row chunks' partial weight gradients are written out and
  * added in a fixed order instead of meeting in atomics on the same k*c*m addresses -- deterministic (the row slots of a block
  * meet in a fixed order too: the same bits on every call), and 4x faster for the 8-channel layers of the X-transform where those
