@@ -31,9 +31,14 @@ namespace hf {
 // instructions instead of the ~600 x 8 lanes of the clip.  For an edge direction u of box P (side length L along u, L' across it),
 // A n B lies inside P n {x : proj_u(x) in proj_u(other box)}: a rectangle of area (overlap of the two projections) x L' -- and
 // inside the intersection of P's two such slabs, the rectangle (overlap along u) x (overlap along u').  The
-// smallest of these six bounds (per box: two slabs and their product), padded by the same kind of slack as the other filters, bounds the reference's
-// overlap from above; iou is increasing in the overlap, so `bound / (sa + sb - bound) < 0.98 thresh` means the reference's
-// `iou > thresh` (bev_iou_g.cu:208-215, :283) is false and the mask bit is 0 either way.  At the RPN's threshold of 0.8 this
+// smallest of these six bounds (per box: two slabs and their product), padded by the same kind of slack as the other filters, bounds the TRUE
+// overlap from above; iou is increasing in the overlap, so `bound / (sa + sb - bound) < 0.98 thresh` means the true iou is below the
+// threshold and the mask bit is 0.  That is also what the reference's `iou > thresh` (bev_iou_g.cu:208-215, :283) says wherever its
+// own overlap is right -- boxes in generic position, where its clip stays within ~6e-5 of an fp64 clip.  It is NOT a bound on the
+// reference's value: on parallel-edged boxes (equal headings) and at coordinates of a kilometre and more the reference's clip now and
+// then gains or loses a polygon vertex and returns an overlap far from the true one, above it as well as below, and there this mask can
+// differ from the reference's -- exactly where the reference's own IoU is off (profiles/bev_cases.md, the equal-heading family;
+// tests/test_bev_abi.py compares the masks on every other pair).  At the RPN's threshold of 0.8 this
 // removes nearly every pair that survived the separating-axis test (two boxes that merely touch); at 0.01 it removes nothing
 // and costs ~40 instructions per surviving pair.  Degenerate boxes (a side <= 0, NaN / inf anywhere) compare false: full path.
 __device__ __forceinline__ bool iou_surely_below(const BoxPre &a, const BoxPre &b, float thresh)

@@ -643,9 +643,9 @@ def ref_image(c, t=None, call=0, stats=None, noise=None):
 
 
 # ================================================================================================ 3D IoU
-def ref_iou3d(a, b):
-    """float64 3D IoU with a Sutherland-Hodgman clip of the two rotated BEV rectangles (corners as bev_iou's rotate_around_center),
-    times the height overlap, over max(va + vb - o3, 1e-7)"""
+def ref_bev_overlap(a, b):
+    """float64 area of the intersection of the BEV rectangles of two (x, y, z, dx, dz, dy, ry) boxes: a Sutherland-Hodgman clip
+    (corners as bev_iou's rotate_around_center)"""
     def corners(x):
         c, s = np.cos(x[6]), np.sin(x[6])
         out = []
@@ -683,7 +683,12 @@ def ref_iou3d(a, b):
         if not poly:
             break
         poly = clip(poly, cb[i], cb[(i + 1) % 4])
-    inter = area(poly) if len(poly) >= 3 else 0.0
+    return area(poly) if len(poly) >= 3 else 0.0
+
+
+def ref_iou3d(a, b):
+    """float64 3D IoU: the BEV overlap of ref_bev_overlap times the height overlap, over max(va + vb - o3, 1e-7)"""
+    inter = ref_bev_overlap(a, b)
     oh = max(min(a[1], b[1]) - max(a[1] - a[5], b[1] - b[5]), 0.0)
     o3 = inter * oh
     return o3 / max(a[3] * a[4] * a[5] + b[3] * b[4] * b[5] - o3, 1e-7)
