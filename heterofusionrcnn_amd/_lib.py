@@ -113,9 +113,13 @@ _SIGNATURES = {
     "hf_linear_bf16_wgrad": [ctypes.c_longlong, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp],
     "hf_project_gather": [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     "hf_project_gather_grad": [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
+    "hf_project_gather_grad_ordered_workspace": [_i, _i, _i, _i, _i],
+    "hf_project_gather_grad_ordered": [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp],
     "hf_roi_image_boxes": [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     "hf_crop_and_resize": [_i, _i, _i, _i, ctypes.c_longlong, _i, _i, _vp, _vp, _vp, _f, _vp, _vp],
     "hf_crop_and_resize_grad": [_i, _i, _i, _i, ctypes.c_longlong, _i, _i, _vp, _vp, _vp, _vp, _vp],
+    "hf_crop_and_resize_grad_ordered_workspace": [_i, _i, _i, _i, ctypes.c_longlong, _i, _i],
+    "hf_crop_and_resize_grad_ordered": [_i, _i, _i, _i, ctypes.c_longlong, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
     "hf_fuse_concat": [ctypes.c_longlong, _i, _i, _vp, _vp, _vp, _vp, _vp],
     "hf_fuse_concat_grad": [ctypes.c_longlong, _i, _i, _vp, _vp, _vp, _vp, _vp],
     "hf_rpn_loss_workspace": [],
@@ -193,6 +197,8 @@ _RESTYPES = {
     "hf_kitti_eval_workspace": _sz,
     "hf_rpn_batch_points_workspace": _sz,
     "hf_rpn_batch_image_workspace": _sz,
+    "hf_project_gather_grad_ordered_workspace": _sz,
+    "hf_crop_and_resize_grad_ordered_workspace": _sz,
     "hf_version": ctypes.c_char_p,
     "hf_strerror": ctypes.c_char_p,
 }

@@ -162,6 +162,9 @@ def add_run_arguments(ap, saved):
     ap.add_argument("--deterministic", action="store_true",
                     help="bit-reproducible training: every route whose sum has no fixed order is refused; the configurations that fuse the "
                          "image (train_rcnn, train_rpn --config rpn_multiclass) do not run under it")
+    ap.add_argument("--deterministic-image", action="store_true",
+                    help="bit-reproducible training of every configuration: --deterministic, and the image-feature gradients (project_gather, "
+                         "image_crop_and_resize) summed in a fixed order instead of by fp32 atomics")
 
 
 def add_train_op_arguments(ap, config_file):
@@ -178,6 +181,11 @@ def add_train_op_arguments(ap, config_file):
     ap.add_argument("--precision", choices=("fp32", "bf16"), default="fp32",
                     help="bf16: the wide dense layers train on the bf16 matrix cores (fp32 accumulation, tensors, master weights and "
                          "Adam; a checkpoint resumes only at the precision it was written at)")
+
+
+def deterministic_level(args):
+    """the `deterministic` keyword of train() from the parsed flags: False, True, or "image" (--deterministic-image implies the mode)"""
+    return "image" if args.deterministic_image else bool(args.deterministic)
 
 
 def train_op_kwargs(args, world=1):

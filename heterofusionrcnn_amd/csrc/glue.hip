@@ -4,12 +4,16 @@
 //                    hf/core/models/rpn_model.py:227-235 (int cast, tf.gather_nd of the image feature map).  One
 //                    pass: the (B,P,2) pixel tensor, its int cast, the (B,P,3) index tensor and the gather become
 //                    one kernel that reads 12 B of coordinates and C floats of features per point.
+//                    Its gradient w.r.t. the image: an fp32 atomic per point and channel (project_gather_grad), or every
+//                    pixel's rows added in point order (project_gather_grad_ordered: ProjectGatherEntries on ordered_scatter.h).
 //   bin_box_decode / bin_box_encode   hf/core/bin_based_box3d_encoder.py:9-269: ~20 TensorFlow ops (tile, stack,
 //                    2x2 matmul, mod, where, clip, floor ...) per call as one element-wise kernel each.
 // Arithmetic: fp32, no contraction, expressions in the order the oracle (oracle/hf_oracle.c) writes them.
+#include <limits.h>
 #include <math.h>
 
 #include "hf_common.h"
+#include "ordered_scatter.h"
 
 namespace hf {
 
@@ -70,6 +74,29 @@ __global__ void project_gather_grad_kernel(int p, int h, int w, int c, long long
         atomicAdd(grad_img + ((bb * h + v) * w + u) * c + l, grad_out[e]);
     }
 }
+
+// the entries of project_gather_grad for ordered_scatter.h: entry e = bb * p + point, its term the row grad_out[e, :]
+struct ProjectGatherEntries {
+    int p, h, w, c;
+    const float *grad_out;
+    const int *pix;
+    __device__ __forceinline__ int key(int e) const
+    {
+        const int u = pix[e * 2ll], v = pix[e * 2ll + 1];
+        if (u < 0 || u >= w || v < 0 || v >= h) return -1;
+        return ((e / p) * h + v) * w + u;
+    }
+    template <int VEC> __device__ __forceinline__ void terms(int e, int ch, float *v) const
+    {
+        const float *row = grad_out + static_cast<long long>(e) * c + ch;
+        if constexpr (VEC == 4) {
+            const float4 q = *reinterpret_cast<const float4 *>(row);
+            v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+        } else {
+            v[0] = row[0];
+        }
+    }
+};
 
 __global__ void bin_box_decode_kernel(long long rows, int k, const float *__restrict__ ref_pts,
                                       const float *__restrict__ ref_theta, const int *__restrict__ bin_x,
@@ -603,6 +630,38 @@ HF_API int hf_project_gather_grad(int b, int p, int h, int w, int c, const float
     hipLaunchKernelGGL(project_gather_grad_kernel, dim3(glue_grid(nrows * c, 256)), dim3(256), 0, st, p, h, w, c, nrows,
                        grad_out, pix, grad_img);
     return launch_status();
+}
+
+// b * h * w and b * p as ints, or false
+static bool project_grad_ordered_sizes(int b, int p, int h, int w, int c, int *targets, int *entries)
+{
+    if (b < 0 || p < 0 || h <= 0 || w <= 0 || c <= 0) return false;
+    const long long t = static_cast<long long>(b) * h, e = static_cast<long long>(b) * p;
+    if (t > INT_MAX || t * w > INT_MAX || e > INT_MAX) return false;
+    *targets = static_cast<int>(t * w);
+    *entries = static_cast<int>(e);
+    return true;
+}
+
+HF_API size_t hf_project_gather_grad_ordered_workspace(int b, int p, int h, int w, int c)
+{
+    int targets, entries;
+    if (!project_grad_ordered_sizes(b, p, h, w, c, &targets, &entries) || targets == 0) return 0;
+    return os_layout(targets, entries).total;
+}
+
+HF_API int hf_project_gather_grad_ordered(int b, int p, int h, int w, int c, const float *grad_out, const int *pix,
+                                          float *grad_img, void *workspace, size_t workspace_bytes, hf_stream_t stream)
+{
+    int targets, entries;
+    if (!project_grad_ordered_sizes(b, p, h, w, c, &targets, &entries)) return HF_EINVAL;
+    if (b == 0) return HF_OK;
+    if (!grad_img || (entries > 0 && (!grad_out || !pix))) return HF_EINVAL;
+    if (!workspace || reinterpret_cast<uintptr_t>(workspace) % 16 != 0 || workspace_bytes < os_layout(targets, entries).total)
+        return HF_EINVAL;
+    const ProjectGatherEntries f = { p, h, w, c, grad_out, pix };
+    const bool vec4 = c % 4 == 0 && (reinterpret_cast<uintptr_t>(grad_out) | reinterpret_cast<uintptr_t>(grad_img)) % 16 == 0;
+    return launch_ordered_scatter(f, targets, entries, c, vec4, grad_img, workspace, as_stream(stream));
 }
 
 HF_API int hf_fuse_concat(long long rows, int c1, int c2, const float *a, const float *b, const float *masks, float *out,

@@ -12,13 +12,16 @@
 //                         zero_fill_kernel.  Not hipMemsetAsync: a captured memset node of a small map (245 760 bytes) wrote the
 //                         zeros on the first replay of its graph and a 16-byte pattern of stale words on every later one, for
 //                         hf_project_gather_grad's memset just the same; a kernel node replays what it was given.
-// Both crop kernels form the sample coordinates with the same function, so both directions take the same in-range decisions
+//   crop_and_resize_grad_ordered  the same gradient with every pixel's shares added in ascending (sample, tap) order, no fp atomics:
+//                         CropGradEntries on the machine of ordered_scatter.h; it writes every row of the map itself.
+// All crop kernels form the sample coordinates with the same function, so both directions and both forms take the same in-range decisions
 // and nothing is saved between them.  No address is formed from a coordinate or a box index that failed its test.
 // Arithmetic: fp32, no contraction, correctly rounded division; expressions in the order of fusion.py's tensor form.
 #include <limits.h>
 #include <math.h>
 
 #include "hf_common.h"
+#include "ordered_scatter.h"
 
 namespace hf {
 
@@ -172,6 +175,45 @@ __global__ __launch_bounds__(256) void crop_and_resize_grad_kernel(int b, int h,
     }
 }
 
+// the entries of crop_and_resize_grad for ordered_scatter.h: entry e = sample * 4 + tap, taps tl, tr, bl, br; the sample
+// coordinates from crop_sample and the shares in the arithmetic of crop_and_resize_grad_kernel
+struct CropGradEntries {
+    int b, h, w, c, crop_h, crop_w;
+    const float *grad_out, *boxes;
+    const int *box_ind;
+    __device__ __forceinline__ CropSample sample(int smp) const
+    {
+        const int ri = smp / crop_w, j = smp - ri * crop_w;
+        const int r = ri / crop_h, i = ri - r * crop_h;
+        return crop_sample(b, h, w, c, crop_h, crop_w, r, i, j, boxes, box_ind);
+    }
+    __device__ __forceinline__ int key(int e) const
+    {
+        const int smp = e >> 2, tap = e & 3;
+        const CropSample s = sample(smp);
+        if (!s.ok) return -1;
+        const int bi = box_ind[smp / (crop_w * crop_h)];
+        return (bi * h + (tap & 2 ? s.yb : s.y0)) * w + (tap & 1 ? s.xb : s.x0);
+    }
+    // of an entry whose key is a target (the sample is in range): dy = dbot : dtop, then the share of the tap's column
+    template <int VEC> __device__ __forceinline__ void terms(int e, int ch, float *v) const
+    {
+        const int smp = e >> 2, tap = e & 3;
+        const CropSample s = sample(smp);
+        const float wy = tap & 2 ? s.ly : 1.0f - s.ly, wx = tap & 1 ? s.lx : 1.0f - s.lx;
+        const float *row = grad_out + static_cast<long long>(smp) * c + ch;
+        float g[VEC];
+        if constexpr (VEC == 4) {
+            const float4 q = *reinterpret_cast<const float4 *>(row);
+            g[0] = q.x; g[1] = q.y; g[2] = q.z; g[3] = q.w;
+        } else {
+            g[0] = row[0];
+        }
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) v[i] = wx * (wy * g[i]);
+    }
+};
+
 // 16-byte stores over the aligned body, dword stores over what is left in front of it and behind it
 __global__ __launch_bounds__(256) void zero_fill_kernel(float *__restrict__ p, long long head, long long nvec, long long total)
 {
@@ -209,6 +251,17 @@ static int crop_args(int b, int h, int w, int c, long long n, int crop_h, int cr
     if (b < 0 || n < 0 || h < 1 || w < 1 || c < 1 || crop_h < 1 || crop_w < 1) return HF_EINVAL;
     if (!elements(b, h, w, c, img_elems) || !elements(n, crop_h, crop_w, c, out_elems)) return HF_EINVAL;
     return HF_OK;
+}
+
+// b * h * w and n * crop_h * crop_w * 4 as ints, or false
+static bool crop_grad_ordered_sizes(int b, int h, int w, int c, long long n, int crop_h, int crop_w, int *targets, int *entries)
+{
+    long long img_elems, out_elems, t, e;
+    if (crop_args(b, h, w, c, n, crop_h, crop_w, &img_elems, &out_elems) != HF_OK) return false;
+    if (!elements(b, h, w, 1, &t) || !elements(n, crop_h, crop_w, 4, &e) || t > INT_MAX || e > INT_MAX) return false;
+    *targets = static_cast<int>(t);
+    *entries = static_cast<int>(e);
+    return true;
 }
 
 }  // namespace hf
@@ -262,4 +315,26 @@ HF_API int hf_crop_and_resize_grad(int b, int h, int w, int c, long long n, int 
     hipLaunchKernelGGL(crop_and_resize_grad_kernel, dim3(grid_for(out_elems, 256)), dim3(256), 0, st, b, h, w, c,
                        n * crop_h * crop_w, crop_h, crop_w, grad_out, boxes_yxyx, box_ind, grad_img);
     return launch_status();
+}
+
+HF_API size_t hf_crop_and_resize_grad_ordered_workspace(int b, int h, int w, int c, long long n, int crop_h, int crop_w)
+{
+    int targets, entries;
+    if (!crop_grad_ordered_sizes(b, h, w, c, n, crop_h, crop_w, &targets, &entries) || targets == 0) return 0;
+    return os_layout(targets, entries).total;
+}
+
+HF_API int hf_crop_and_resize_grad_ordered(int b, int h, int w, int c, long long n, int crop_h, int crop_w, const float *grad_out,
+                                           const float *boxes_yxyx, const int *box_ind, float *grad_img, void *workspace,
+                                           size_t workspace_bytes, hf_stream_t stream)
+{
+    int targets, entries;
+    if (!crop_grad_ordered_sizes(b, h, w, c, n, crop_h, crop_w, &targets, &entries)) return HF_EINVAL;
+    if (b == 0) return HF_OK;
+    if (!grad_img || (entries > 0 && (!grad_out || !boxes_yxyx || !box_ind))) return HF_EINVAL;
+    if (!workspace || reinterpret_cast<uintptr_t>(workspace) % 16 != 0 || workspace_bytes < os_layout(targets, entries).total)
+        return HF_EINVAL;
+    const CropGradEntries f = { b, h, w, c, crop_h, crop_w, grad_out, boxes_yxyx, box_ind };
+    const bool vec4 = c % 4 == 0 && (reinterpret_cast<uintptr_t>(grad_out) | reinterpret_cast<uintptr_t>(grad_img)) % 16 == 0;
+    return launch_ordered_scatter(f, targets, entries, c, vec4, grad_img, workspace, as_stream(stream));
 }

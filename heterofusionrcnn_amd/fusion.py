@@ -9,6 +9,7 @@ import torch
 
 from . import _lib
 from ._lib import check, dev_tensor, ptr, require, stream_ptr
+from . import determinism
 from .determinism import refuse_unordered
 
 
@@ -22,9 +23,26 @@ def rect_to_image(pts3d, calib):
     return pix[..., :2] / pix[..., 2:3]
 
 
+def _image_grad_route(op, why, ordered_grad):
+    """where the forward of an image op is recorded with a gradient wanted: True = its backward takes the ordered form.
+    ordered_grad None follows the mode (level "image": ordered; level True: refused; off: the atomics), True asks for the ordered
+    form whatever the mode, False for the atomic one, which either level refuses."""
+    if ordered_grad is None:
+        ordered_grad = determinism.covers_image()
+    if not ordered_grad:
+        refuse_unordered(op, why)
+    return bool(ordered_grad)
+
+
+def _workspace(nbytes, device):
+    """caller-owned scratch of a C-ABI call: torch.empty, so that under capture it comes from the graph's pool (allocations are
+    aligned far beyond the 16 bytes the entries ask for)"""
+    return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=device)
+
+
 class _ProjectGather(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, img_fts, pts3d, calib):
+    def forward(ctx, img_fts, pts3d, calib, ordered):
         b, h, w, c = img_fts.shape
         p = pts3d.shape[1]
         out = torch.empty((b, p, c), dtype=torch.float32, device=img_fts.device)
@@ -33,6 +51,7 @@ class _ProjectGather(torch.autograd.Function):
                                            stream_ptr()), "project_gather")
         ctx.save_for_backward(pix)
         ctx.shape = (b, p, h, w, c)
+        ctx.ordered = ordered
         ctx.mark_non_differentiable(pix)
         return out, pix
 
@@ -42,24 +61,33 @@ class _ProjectGather(torch.autograd.Function):
         b, p, h, w, c = ctx.shape
         grad_out = grad_out.contiguous()
         g = torch.empty((b, h, w, c), dtype=torch.float32, device=grad_out.device)
-        check(_lib.lib().hf_project_gather_grad(b, p, h, w, c, ptr(grad_out), ptr(pix), ptr(g), stream_ptr()),
-              "project_gather_grad")
-        return g, None, None
+        if ctx.ordered:
+            ws = _workspace(_lib.lib().hf_project_gather_grad_ordered_workspace(b, p, h, w, c), grad_out.device)
+            check(_lib.lib().hf_project_gather_grad_ordered(b, p, h, w, c, ptr(grad_out), ptr(pix), ptr(g), ptr(ws), ws.numel(),
+                                                            stream_ptr()), "project_gather_grad_ordered")
+        else:
+            check(_lib.lib().hf_project_gather_grad(b, p, h, w, c, ptr(grad_out), ptr(pix), ptr(g), stream_ptr()),
+                  "project_gather_grad")
+        return g, None, None, None
 
 
-def project_gather(pts3d, calib, img_fts, return_pixels=False):
+def project_gather(pts3d, calib, img_fts, return_pixels=False, ordered_grad=None):
     """pts3d (B,P,3), calib (B,3,4), img_fts (B,H,W,C) -> (B,P,C): the image features under the projected points
     (rpn_model.py:227-235).  Gradient w.r.t. img_fts only (pixel indices are integers).  return_pixels also returns
-    the int32 (B,P,2) [u, v] pixel of every point."""
+    the int32 (B,P,2) [u, v] pixel of every point.  ordered_grad: the form of that gradient, chosen here where the forward is
+    recorded -- None follows heterofusionrcnn_amd.deterministic (off: fp32 atomics; True: refused; "image": ordered), True takes
+    hf_project_gather_grad_ordered (every pixel's rows added in point order, bit-reproducible) whatever the mode, False the atomics."""
     require(pts3d.dim() == 3 and pts3d.shape[2] == 3, "project_gather expects (B,P,3) points")
     require(img_fts.dim() == 4 and img_fts.shape[0] == pts3d.shape[0], "project_gather expects (B,H,W,C) image features")
     require(calib.shape == (pts3d.shape[0], 3, 4), "project_gather expects (B,3,4) calib")
     pts3d = dev_tensor(pts3d.detach(), torch.float32, "pts3d")
     calib = dev_tensor(calib.detach(), torch.float32, "calib")
     img_fts = dev_tensor(img_fts, torch.float32, "img_fts")
+    ordered = False
     if img_fts.requires_grad and torch.is_grad_enabled():
-        refuse_unordered("project_gather", "the gradient of the image features is an atomic scatter: many points fall on one pixel")
-    out, pix = _ProjectGather.apply(img_fts, pts3d, calib)
+        ordered = _image_grad_route("project_gather", "the gradient of the image features is an atomic scatter: many points fall on one pixel",
+                                    ordered_grad)
+    out, pix = _ProjectGather.apply(img_fts, pts3d, calib, ordered)
     return (out, pix) if return_pixels else out
 
 
@@ -183,7 +211,7 @@ class _CropAndResize(torch.autograd.Function):
     """hf_crop_and_resize (+ grad): gradient w.r.t. the image only; the backward recomputes the sample coordinates"""
 
     @staticmethod
-    def forward(ctx, img_fts, boxes, box_ind, crop, extrapolation):
+    def forward(ctx, img_fts, boxes, box_ind, crop, extrapolation, ordered):
         b, h, w, c = img_fts.shape
         n = boxes.shape[0]
         out = torch.empty((n, crop, crop, c), dtype=torch.float32, device=img_fts.device)
@@ -191,6 +219,7 @@ class _CropAndResize(torch.autograd.Function):
                                             ptr(out), stream_ptr()), "crop_and_resize")
         ctx.save_for_backward(boxes, box_ind)
         ctx.dims = (b, h, w, c, n, crop)
+        ctx.ordered = ordered
         return out
 
     @staticmethod
@@ -199,26 +228,36 @@ class _CropAndResize(torch.autograd.Function):
         b, h, w, c, n, crop = ctx.dims
         grad_out = grad_out.contiguous()
         g = torch.empty((b, h, w, c), dtype=torch.float32, device=grad_out.device)
-        check(_lib.lib().hf_crop_and_resize_grad(b, h, w, c, n, crop, crop, ptr(grad_out), ptr(boxes), ptr(box_ind), ptr(g),
-                                                 stream_ptr()), "crop_and_resize_grad")
-        return g, None, None, None, None
+        if ctx.ordered:
+            ws = _workspace(_lib.lib().hf_crop_and_resize_grad_ordered_workspace(b, h, w, c, n, crop, crop), grad_out.device)
+            check(_lib.lib().hf_crop_and_resize_grad_ordered(b, h, w, c, n, crop, crop, ptr(grad_out), ptr(boxes), ptr(box_ind),
+                                                             ptr(g), ptr(ws), ws.numel(), stream_ptr()), "crop_and_resize_grad_ordered")
+        else:
+            check(_lib.lib().hf_crop_and_resize_grad(b, h, w, c, n, crop, crop, ptr(grad_out), ptr(boxes), ptr(box_ind), ptr(g),
+                                                     stream_ptr()), "crop_and_resize_grad")
+        return g, None, None, None, None, None
 
 
-def image_crop_and_resize(img_fts, boxes_norm_yxyx, box_ind, crop_size, extrapolation_value=0.0):
+def image_crop_and_resize(img_fts, boxes_norm_yxyx, box_ind, crop_size, extrapolation_value=0.0, ordered_grad=None):
     """tf.image.crop_and_resize (bilinear) as the RCNN uses it on the image feature map (rcnn_model.py:494-500): img_fts
     (B,H,W,C), boxes (N,4) [y1,x1,y2,x2] normalised, box_ind (N) -> (N,crop,crop,C).  Sample i of a crop sits at
     y1 (H-1) + i (y2-y1)(H-1)/(crop-1); a sample outside [0, H-1] x [0, W-1] takes the extrapolation value.
     fp32 tensors on the device: one HIP kernel each way (csrc/roi_image.hip), gradient w.r.t. img_fts only, and a row whose
     rectangle is not finite adds nothing to it.  Host tensors and other dtypes: the tensor form below.  TensorFlow is not
     importable here: parity unpinned beyond the documented formula (tests/test_rcnn.py checks the tensor form against a
-    loop, tests/roi_image_cases.py restates it for the kernels)."""
+    loop, tests/roi_image_cases.py restates it for the kernels).  ordered_grad, for the kernels: the form of the gradient, chosen
+    here where the forward is recorded -- None follows heterofusionrcnn_amd.deterministic (off: fp32 atomics; True: refused;
+    "image": ordered), True takes hf_crop_and_resize_grad_ordered (every pixel's shares added in sample and tap order,
+    bit-reproducible) whatever the mode, False the atomics.  The tensor form on device tensors is refused under both levels."""
     if _on_device_f32(img_fts, boxes_norm_yxyx) and box_ind.is_cuda:
         require(img_fts.dim() == 4 and boxes_norm_yxyx.dim() == 2 and boxes_norm_yxyx.shape[1] == 4
                 and box_ind.shape == boxes_norm_yxyx.shape[:1], "image_crop_and_resize expects (B,H,W,C), (N,4) boxes and (N) box_ind")
+        ordered = False
         if img_fts.requires_grad and torch.is_grad_enabled():
-            refuse_unordered("image_crop_and_resize", "the gradient of the image features is an atomic scatter: RoIs overlap")
+            ordered = _image_grad_route("image_crop_and_resize", "the gradient of the image features is an atomic scatter: RoIs overlap",
+                                        ordered_grad)
         return _CropAndResize.apply(img_fts.contiguous(), boxes_norm_yxyx.detach().contiguous(),
-                                    box_ind.detach().to(torch.int32).contiguous(), int(crop_size), float(extrapolation_value))
+                                    box_ind.detach().to(torch.int32).contiguous(), int(crop_size), float(extrapolation_value), ordered)
     if img_fts.is_cuda and img_fts.requires_grad and torch.is_grad_enabled():
         refuse_unordered("image_crop_and_resize", "the tensor form on device tensors: its index gradient adds atomically")
     return _image_crop_and_resize_tensor(img_fts, boxes_norm_yxyx, box_ind, crop_size, extrapolation_value)

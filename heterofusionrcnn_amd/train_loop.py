@@ -13,7 +13,7 @@ import time
 import torch
 
 from . import checkpoint as ckpt_mod
-from .determinism import deterministic as deterministic_mode, is_deterministic
+from .determinism import as_level, deterministic as deterministic_mode, level
 from .graph_step import TrainStep
 from .optim import MultiTensorAdam
 from .pipeline import GeometryPrefetcher
@@ -24,9 +24,9 @@ def run(stage, steps, seed, save, log_every, lr, graph, log, clip_norm, lr_decay
     """-> (list of the per-step losses of this run, floats read at the end; stage.finish(the loader's final status, log))
 
     The arguments are train_rpn.train's, which documents them; the caller runs under mlp.training_precision(precision).  deterministic: the
-    whole run -- the capture and every step -- is inside determinism.deterministic(True): no route whose sum has no fixed
-    order runs; two runs from one state then give the same bits ("Reproducible training")."""
-    with deterministic_mode(deterministic or is_deterministic()):       # a caller's own scope stays on
+    whole run -- the capture and every step -- is inside determinism.deterministic(deterministic), True or "image": no route whose sum has
+    no fixed order runs; two runs from one state then give the same bits ("Reproducible training")."""
+    with deterministic_mode(as_level(deterministic) or level()):       # the level as asked for; a caller's own scope stays on
         return _run(stage, steps, seed, save, log_every, lr, graph, log, clip_norm, lr_decay, tf_epsilon, check_numerics, checkpoint_dir,
                     checkpoint_every, max_checkpoints, resume, precision)
 

@@ -14,7 +14,7 @@ import sys
 
 from . import checkpoint as ckpt_mod
 from . import train_loop
-from .determinism import IMAGE_CONFIGS_REFUSED, is_deterministic, refuse_image_config
+from .determinism import IMAGE_CONFIGS_REFUSED, as_level, level, refuse_image_config
 from .inference import ImgVggPyr
 from .mlp import under_training_precision
 from .rcnn import RcnnConfig, RcnnModel
@@ -66,8 +66,8 @@ def train(dataset_dir, handoff_dir, split="train", steps=100, batch=2, seed=0, s
           precision="fp32", deterministic=False):
     """-> (list of the per-step losses of this run, read at the end; the trainer)
     The train-op, checkpoint, resume, precision and deterministic keywords are train_rpn.train's (`steps` is the final global step when resuming);
-    the RCNN fuses the image, so deterministic=True is refused before anything is built."""
-    if deterministic or is_deterministic():
+    the RCNN fuses the image, so deterministic=True is refused before anything is built and deterministic="image" is the level it trains at."""
+    if (as_level(deterministic) or level()) is True:
         refuse_image_config("train_rcnn")
     stage = RcnnStage(img_conv, dataset_dir=dataset_dir, handoff_dir=handoff_dir, split=split, batch=batch, seed=seed, aug_list=aug_list,
                       workers=workers)
@@ -90,10 +90,10 @@ def build_parser():
 def main(argv=None):
     ap = build_parser()
     args = ap.parse_args(argv)
-    if args.deterministic:
+    if args.deterministic and not args.deterministic_image:
         ap.error("--deterministic: " + IMAGE_CONFIGS_REFUSED)
     losses, _ = train(args.dataset_dir, args.handoff_dir, args.split, args.steps, args.batch, args.seed, args.save, args.log_every,
-                      args.workers, graph=not args.no_graph, deterministic=args.deterministic, **ckpt_mod.train_op_kwargs(args))
+                      args.workers, graph=not args.no_graph, deterministic=ckpt_mod.deterministic_level(args), **ckpt_mod.train_op_kwargs(args))
     if losses:
         print("done: %d steps, first loss %.5f, last loss %.5f" % (len(losses), losses[0], losses[-1]))
     else:

@@ -17,7 +17,7 @@ import sys
 from . import checkpoint as ckpt_mod
 from . import rpn as rpn_mod
 from . import train_loop
-from .determinism import IMAGE_CONFIGS_REFUSED, is_deterministic, refuse_image_config
+from .determinism import IMAGE_CONFIGS_REFUSED, as_level, level, refuse_image_config
 from .graph_step import rpn_loss_parts
 from .inference import CLASSES, ImgVggPyr
 from .kitti_data import KittiRpnBatches
@@ -84,9 +84,10 @@ def train(dataset_dir, split="train", steps=100, batch=8, config="rpn_multiclass
     checkpoint_dir: a checkpoint every checkpoint_every global steps, the newest max_checkpoints kept; resume: continue from the
     newest checkpoint there, `steps` then being the final global step.  precision "bf16": the wide dense layers train on the bf16
     matrix cores (the whole call runs under mlp.training_precision); a checkpoint resumes only at the precision it was written at.
-    deterministic: the run is inside determinism.deterministic(True) (bit-reproducible: train_loop.run); rpn_multiclass_points only:
-    the config that fuses the image is refused before anything is built."""
-    if (deterministic or is_deterministic()) and config == "rpn_multiclass":
+    deterministic: True or "image", the run is inside determinism.deterministic at that level (bit-reproducible: train_loop.run).  True
+    trains rpn_multiclass_points only: the config that fuses the image is refused before anything is built.  "image" trains every
+    config, the image-feature gradients in their ordered form."""
+    if (as_level(deterministic) or level()) is True and config == "rpn_multiclass":
         refuse_image_config("train_rpn, config rpn_multiclass")
     stage = RpnStage(config, img_conv, dataset_dir=dataset_dir, split=split, classes=CLASSES, batch=batch, num_points=num_points,
                      seed=seed, workers=workers)
@@ -108,10 +109,10 @@ def build_parser():
 def main(argv=None):
     ap = build_parser()
     args = ap.parse_args(argv)
-    if args.deterministic and args.config == "rpn_multiclass":
+    if args.deterministic and not args.deterministic_image and args.config == "rpn_multiclass":
         ap.error("--deterministic with --config rpn_multiclass: " + IMAGE_CONFIGS_REFUSED)
     losses, st = train(args.dataset_dir, args.split, args.steps, args.batch, args.config, args.seed, args.save, args.log_every,
-                       args.workers, graph=not args.no_graph, deterministic=args.deterministic, **ckpt_mod.train_op_kwargs(args))
+                       args.workers, graph=not args.no_graph, deterministic=ckpt_mod.deterministic_level(args), **ckpt_mod.train_op_kwargs(args))
     if losses:
         print("done: %d steps, first loss %.5f, last loss %.5f, status %s" % (len(losses), losses[0], losses[-1], st))
     else:

@@ -497,6 +497,33 @@ int hf_project_gather(int b, int p, int h, int w, int c, const float *pts, const
                       int *pix, hf_stream_t stream);
 int hf_project_gather_grad(int b, int p, int h, int w, int c, const float *grad_out, const int *pix, float *grad_img,
                            hf_stream_t stream);
+/* The two image-feature gradients in ORDERED form (csrc/ordered_scatter.h): the same sums as hf_project_gather_grad and
+ * hf_crop_and_resize_grad, with the order of every sum fixed, so that the result is bit-reproducible.  Both are one operation:
+ * E entries in a fixed order, each with a target row key[e] of the (b*h*w, c) map or none and a term of c floats;
+ *   grad_img[t] = sum over { e : key[e] == t } of term[e], added in ASCENDING e, in fp32, from +0.0f, one rounding per add:
+ * bit for bit what `for e in range(E): if valid[e]: g[key[e]] += term[e]` gives on a zero-filled float32 array.  A target
+ * that no entry names becomes +0.0f; every element of grad_img is written by the call (it need not be initialised).
+ *   project_gather   entry e = bb*p + point; valid when the saved pix [u,v] lies in [0,w) x [0,h); key = (bb*h + v)*w + u;
+ *                    term = grad_out[e, :].
+ *   crop_and_resize  entry e = ((r*crop_h + i)*crop_w + j)*4 + tap, taps in the order tl, tr, bl, br; valid exactly where
+ *                    hf_crop_and_resize_grad adds (sample inside the image, box finite, box_ind in [0,b); box_ind need not be
+ *                    sorted); terms as there, fp32 without contraction: dtop = (1-ly) g, dbot = ly g; tl = (1-lx) dtop,
+ *                    tr = lx dtop, bl = (1-lx) dbot, br = lx dbot.  Where floor == ceil two taps of a sample name one pixel:
+ *                    both are entries, in tap order.
+ * No floating-point atomics; integer atomics only for counts and for slot claims that are sorted afterwards.  No workgroup
+ * waits on another.  `workspace`: caller-owned, hf_*_grad_ordered_workspace(shapes) bytes, 16-byte aligned; its counters are
+ * zeroed by a kernel on the stream, so the calls can be captured and replayed.  Lists of any length are sorted by a workgroup
+ * in O(n log^2 n / 1024): all entries of a frame on one pixel stay in the milliseconds.
+ * b == 0 returns HF_OK; p == 0 / n == 0 with a non-empty map writes zeros.  HF_EINVAL: a negative size, h, w, c or crop < 1,
+ * b*h*w or E beyond INT_MAX, a NULL required pointer of a non-empty tensor, a workspace that is NULL, misaligned or smaller
+ * than asked for.  The workspace functions return 0 for shapes the entries reject and for b == 0. */
+size_t hf_project_gather_grad_ordered_workspace(int b, int p, int h, int w, int c);
+int hf_project_gather_grad_ordered(int b, int p, int h, int w, int c, const float *grad_out, const int *pix, float *grad_img,
+                                   void *workspace, size_t workspace_bytes, hf_stream_t stream);
+size_t hf_crop_and_resize_grad_ordered_workspace(int b, int h, int w, int c, long long n, int crop_h, int crop_w);
+int hf_crop_and_resize_grad_ordered(int b, int h, int w, int c, long long n, int crop_h, int crop_w, const float *grad_out,
+                                    const float *boxes_yxyx, const int *box_ind, float *grad_img, void *workspace,
+                                    size_t workspace_bytes, hf_stream_t stream);
 /* The image half of the second stage's RoI pooling (hf/core/models/rcnn_model.py:433-454, 494-501), csrc/roi_image.hip.
  * hf_roi_image_boxes: hf/core/projection.py:35-96 (tf_project_to_image_space).  boxes3d (b,n,7) [x,y,z,l,w,h,ry], y at the
  * bottom; calib (b,3,4) P2; h, w the image size the rectangle is normalised by.  The eight corners times P2, divided by depth,

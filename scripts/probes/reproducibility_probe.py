@@ -6,6 +6,9 @@ mode, and a small-width RpnModel on synthetic points (widths of 32: no layer mee
 every X-Conv takes the dense fused form).  For every stage the JSON lists the tensors whose bits differ (none = the step repeats), or the refusal the mode raised.
 
   python scripts/probes/reproducibility_probe.py [--out profiles/reproducibility_probe.json] [--repeats 3]
+
+--level image: only the two stages that fuse the image, rpn_multiclass and train_rcnn, under determinism.deterministic("image") (the
+image-feature gradients in their ordered form), written to profiles/reproducibility_probe_image.json.
 """
 import argparse
 import copy
@@ -142,9 +145,13 @@ def image_pyramid(repeats):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "reproducibility_probe.json"))
+    ap.add_argument("--out", default=None)
     ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--level", choices=("true", "image"), default="true", help="image: the stages that fuse the image under that level")
     args = ap.parse_args()
+    image = args.level == "image"
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "reproducibility_probe_image.json" if image else "reproducibility_probe.json")
     from heterofusionrcnn_amd import export_rpn, train_rcnn, train_rpn
     from heterofusionrcnn_amd.inference import CLASSES
     tmp = tempfile.mkdtemp()
@@ -153,28 +160,30 @@ def main():
         data_dir, hand = os.path.join(tmp, "kitti"), os.path.join(tmp, "handoff")
         os.makedirs(data_dir)
         make_dataset(data_dir)
-        bad, n = image_pyramid(args.repeats)
-        result["ImgVggPyr alone (2,360,1200,3), forward + backward, mode on"] = {"tensors": n, "differ": bad}
-        print("ImgVggPyr:", n, "tensors,", len(bad), "differ", bad)
-        for mode in (True, False):
-            bad, n = small_width(args.repeats, mode)
-            result["small-width RpnModel on points (dense fused X-Conv layers), mode %s" % ("on" if mode else "off")] = {"tensors": n, "differ": bad}
-            print("small-width mode", mode, ":", n, "tensors,", len(bad), "differ", bad[:8])
-        loader = dict(dataset_dir=data_dir, split="train", batch=2, seed=1, workers=2)
-        for config in ("rpn_multiclass_points", "rpn_multiclass"):
+        if not image:
+            bad, n = image_pyramid(args.repeats)
+            result["ImgVggPyr alone (2,360,1200,3), forward + backward, mode on"] = {"tensors": n, "differ": bad}
+            print("ImgVggPyr:", n, "tensors,", len(bad), "differ", bad)
             for mode in (True, False):
+                bad, n = small_width(args.repeats, mode)
+                result["small-width RpnModel on points (dense fused X-Conv layers), mode %s" % ("on" if mode else "off")] = {"tensors": n, "differ": bad}
+                print("small-width mode", mode, ":", n, "tensors,", len(bad), "differ", bad[:8])
+        loader = dict(dataset_dir=data_dir, split="train", batch=2, seed=1, workers=2)
+        label = lambda mode: "level image" if mode == "image" else "mode %s" % ("on" if mode else "off")
+        for config in (("rpn_multiclass",) if image else ("rpn_multiclass_points", "rpn_multiclass")):
+            for mode in (("image",) if image else (True, False)):
                 stage = train_rpn.RpnStage(config, IMG_CONV, classes=CLASSES, num_points=16384, **loader)
                 bad, n = step_gradients(stage, args.repeats, mode)
-                result["%s step, mode %s" % (config, "on" if mode else "off")] = {"tensors": n, "differ": bad}
+                result["%s step, %s" % (config, label(mode))] = {"tensors": n, "differ": bad}
                 print(config, "mode", mode, ":", n, "tensors,", bad if isinstance(bad, str) else "%d differ %s" % (len(bad), bad[:8]))
         model_path = os.path.join(hand, "rpn.pt")
         os.makedirs(hand)
         train_rpn.train(data_dir, "train", steps=2, batch=2, seed=1, log_every=0, workers=2, img_conv=IMG_CONV, save=model_path)
         export_rpn.export(data_dir, model_path, hand, "train", batch=2, img_conv=IMG_CONV, workers=2, log=None)
-        for mode in (True, False):
+        for mode in (("image",) if image else (True, False)):
             stage = train_rcnn.RcnnStage(IMG_CONV, handoff_dir=hand, aug_list=None, **loader)
             bad, n = step_gradients(stage, args.repeats, mode)
-            result["train_rcnn step, mode %s" % ("on" if mode else "off")] = {"tensors": n, "differ": bad}
+            result["train_rcnn step, %s" % label(mode)] = {"tensors": n, "differ": bad}
             print("train_rcnn mode", mode, ":", n, "tensors,", bad if isinstance(bad, str) else "%d differ %s" % (len(bad), bad[:8]))
     finally:
         shutil.rmtree(tmp, ignore_errors=True)
