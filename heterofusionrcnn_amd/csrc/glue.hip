@@ -621,12 +621,12 @@ HF_API int hf_project_gather_grad(int b, int p, int h, int w, int c, const float
 {
     if (b < 0 || p < 0 || h <= 0 || w <= 0 || c <= 0 || (b > 0 && !grad_img)) return HF_EINVAL;
     if (b == 0) return HF_OK;
+    const long long nrows = static_cast<long long>(b) * p;
+    if (nrows > 0 && (!grad_out || !pix)) return HF_EINVAL;  // refused before grad_img is touched
     hipStream_t st = as_stream(stream);
     int rc = hip_status(hipMemsetAsync(grad_img, 0, sizeof(float) * static_cast<size_t>(b) * h * w * c, st));
     if (rc != HF_OK) return rc;
-    const long long nrows = static_cast<long long>(b) * p;
     if (nrows == 0) return HF_OK;
-    if (!grad_out || !pix) return HF_EINVAL;
     hipLaunchKernelGGL(project_gather_grad_kernel, dim3(glue_grid(nrows * c, 256)), dim3(256), 0, st, p, h, w, c, nrows,
                        grad_out, pix, grad_img);
     return launch_status();

@@ -492,7 +492,9 @@ int hf_linear_bn_bwd(long long rows, int cout, int cin, const float *dy_or_dz, c
  * the 3x4 P2 matrix, divide by depth) + hf/core/models/rpn_model.py:227-235 (tf.cast to int32, tf.gather_nd of the
  * image feature map at [b, v, u]).  pts (b,p,3), calib (b,3,4), img (b,h,w,c) -> out (b,p,c); a pixel outside the
  * image gives zeros (tf.gather_nd on GPU).  pix (b,p,2) [u,v], optional, is what the gradient needs.
- * hf_project_gather_grad: grad_img (b,h,w,c), zero-filled here, += grad_out rows at their pixels. */
+ * A quotient outside (-2^31, 2^31) or NaN has no int cast: pix = (-1, -1), a zero row.
+ * hf_project_gather_grad: grad_img (b,h,w,c), zero-filled here, += grad_out rows at their pixels; a NULL grad_out or
+ * pix with b * p > 0 is HF_EINVAL before grad_img is touched. */
 int hf_project_gather(int b, int p, int h, int w, int c, const float *pts, const float *calib, const float *img, float *out,
                       int *pix, hf_stream_t stream);
 int hf_project_gather_grad(int b, int p, int h, int w, int c, const float *grad_out, const int *pix, float *grad_img,
