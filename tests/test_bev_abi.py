@@ -20,10 +20,11 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import bev_cases as bc  # noqa: E402
+from abi_harness import Workspace, abi, dev, host  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-GUARD, GUARD_BYTE = 256, 0xA5
+DEV = "cuda"
 TOL = 1e-5                     # test_ops_gpu.TOL: device against the fp32 oracle
 MASK_FILL = 0x5A5A5A5A5A5A5A5A
 
@@ -34,19 +35,6 @@ assert sorted(NMS_IDS) == sorted(bc.nms_case_ids())
 _id = lambda p: "%s-%g" % p
 
 
-def _abi():
-    from heterofusionrcnn_amd import _lib
-    return _lib, _lib.lib()
-
-
-def dev(a):
-    return torch.from_numpy(np.array(a)).cuda()          # a copy: the shared case inputs are read-only
-
-
-def host(t):
-    return t.detach().cpu().numpy()
-
-
 def record(**kw):
     print("\n" + json.dumps(kw))
     if os.environ.get("BEV_CASES_OUT"):
@@ -54,29 +42,14 @@ def record(**kw):
             f.write(json.dumps(kw) + "\n")
 
 
-class Workspace:
-    """exactly nbytes between two guards"""
-
-    def __init__(self, nbytes):
-        self.nbytes = int(nbytes)
-        self.buf = torch.full((self.nbytes + 2 * GUARD,), GUARD_BYTE, dtype=torch.uint8, device="cuda")
-        assert self.buf.data_ptr() % 256 == 0
-        self.p = ctypes.c_void_p(self.buf.data_ptr() + GUARD)
-
-    def check(self, what):
-        torch.cuda.synchronize()
-        assert bool((self.buf[:GUARD] == GUARD_BYTE).all()), "%s: the guard below the workspace was written" % what
-        assert bool((self.buf[GUARD + self.nbytes:] == GUARD_BYTE).all()), "%s: the guard above the workspace was written" % what
-
-
 def run_nms(boxes_dev, frames, n, thresh, batched):
     """one call into fresh, sentinel-filled buffers -> (keep (frames, n), num_kept (frames,)) on the host, seconds"""
-    _lib, L = _abi()
+    _lib, L = abi()
     nbytes = frames * L.hf_oriented_nms_workspace(n)
     assert L.hf_oriented_nms_workspace(n) >= 8 * n * ((n + 63) // 64)
     keep = torch.full((frames, n), bc.SENT_I, dtype=torch.int32, device="cuda")
     num = torch.full((frames,), bc.SENT_I, dtype=torch.int32, device="cuda")
-    ws = Workspace(nbytes)
+    ws = Workspace(DEV, nbytes)
     args = (_lib.ptr(boxes_dev), n, thresh, _lib.ptr(keep), _lib.ptr(num))
     call = (lambda *tail: L.hf_oriented_nms_batched(frames, *args, *tail)) if batched else (lambda *tail: L.hf_oriented_nms(*args, *tail))
     # one byte short: refused before anything is launched (nothing written)
@@ -103,7 +76,7 @@ def check_keep(keep, num, want_keep, want_kept, what):
 
 # ------------------------------------------------------------------------------------------------ bad arguments: no launch
 def test_bad_arguments_are_refused_before_any_launch():
-    _lib, L = _abi()
+    _lib, L = abi()
     one, big = ctypes.c_void_p(4096), 1 << 60           # never dereferenced: the checks come first
     EINVAL, EWS = bc.HF_EINVAL, bc.HF_EWORKSPACE
     nms = lambda n, t, keep=one, boxes=one, ws=one, nbytes=big: L.hf_oriented_nms(boxes, n, t, keep, one, ws, nbytes, None)
@@ -140,7 +113,7 @@ def test_bad_arguments_are_refused_before_any_launch():
 def test_oriented_nms(case):
     name, thresh = case
     fx, m = bc.nms_fixture(name), bc.nms_model(name, thresh)
-    boxes = dev(fx["boxes"])
+    boxes = dev(DEV, fx["boxes"])
     what = "%s at %g (%s)" % (name, thresh, m["regime"])
     keep, num, seconds = run_nms(boxes, 1, m["n"], thresh, batched=False)
     check_keep(keep[0], num[0], m["keep"], m["kept"], what)
@@ -153,7 +126,7 @@ def test_oriented_nms(case):
 def test_oriented_nms_batched_frames_take_different_forms():
     frames = bc.batch_frames()
     n = len(frames[0][0])
-    boxes = dev(np.stack([b for b, _ in frames]))
+    boxes = dev(DEV, np.stack([b for b, _ in frames]))
     for again in range(2):
         keep, num, _ = run_nms(boxes, len(frames), n, bc.BATCH_THRESH, batched=True)
         for f, (_, m) in enumerate(frames):
@@ -163,12 +136,12 @@ def test_oriented_nms_batched_frames_take_different_forms():
 
 # ------------------------------------------------------------------------------------------------ hf_nms_mask
 def run_mask(boxes, thresh):
-    _lib, L = _abi()
+    _lib, L = abi()
     n = len(boxes)
     cb = (n + 63) // 64
     guarded = torch.full((n * cb + 64,), MASK_FILL, dtype=torch.int64, device="cuda")
     out = guarded[32:32 + n * cb]
-    _lib.check(L.hf_nms_mask(_lib.ptr(dev(boxes)), ctypes.c_void_p(out.data_ptr()), n, thresh, _lib.stream_ptr()), "nms_mask")
+    _lib.check(L.hf_nms_mask(_lib.ptr(dev(DEV, boxes)), ctypes.c_void_p(out.data_ptr()), n, thresh, _lib.stream_ptr()), "nms_mask")
     torch.cuda.synchronize()
     assert bool((guarded[:32] == MASK_FILL).all()) and bool((guarded[32 + n * cb:] == MASK_FILL).all()), "written outside the mask"
     return host(out).view(np.uint64).reshape(n, cb)
@@ -205,7 +178,7 @@ def bound(oracle_mod):
 
 
 def run_iou(a, b, with_ov, with_iou):
-    _lib, L = _abi()
+    _lib, L = abi()
     na, nb = len(a), len(b)
     outs = [torch.full((na * nb + 8,), float("nan"), dtype=torch.float32, device="cuda") if use else None for use in (with_ov, with_iou)]
     views = [o[4:4 + na * nb] if o is not None else None for o in outs]           # 16 bytes in: still aligned
@@ -220,7 +193,7 @@ def run_iou(a, b, with_ov, with_iou):
 @pytest.mark.parametrize("name", bc.iou_case_ids())
 def test_compute_bev_iou(oracle_mod, name):
     c = bc.iou_case(name)
-    a, b = dev(c["a"]), dev(c["b"])
+    a, b = dev(DEV, c["a"]), dev(DEV, c["b"])
     ov_d, iou_d = run_iou(a, b, True, True)
     ov, iou = host(ov_d), host(iou_d)
     assert not np.isnan(ov).any() and not np.isnan(iou).any(), "%d / %d elements never written" % (int(np.isnan(ov).sum()), int(np.isnan(iou).sum()))
@@ -253,7 +226,7 @@ def test_compute_bev_iou_slab_walk(oracle_mod):
     """more row tiles than one grid holds: planted rows on both sides of the slab boundary, zeros everywhere else"""
     c = bc.iou_case("slab")
     na, nb = bc.SLAB_SHAPE
-    a, b = torch.from_numpy(bc.slab_rows()).cuda(), dev(c["b"])
+    a, b = torch.from_numpy(bc.slab_rows()).cuda(), dev(DEV, c["b"])
     planted = torch.tensor(bc.SLAB_PLANTED, device="cuda")
     bd = bound(oracle_mod)
     want_iou, want_ov = c["iou"].reshape(len(bc.SLAB_PLANTED), nb), c["ov"].reshape(len(bc.SLAB_PLANTED), nb)

@@ -19,101 +19,21 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import bn_cases as bc  # noqa: E402
-from test_gemm_abi import same  # noqa: E402
+from abi_harness import RATIOS, Arena, abi, call, parity_report, place, same, twice, within  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
-SENTINEL = 12345.0
-GUARD = 64
 EPS = bc.EPS
 U = bc.U
-RATIOS = {}             # (entry point output, family) -> worst |got - ref64| / bound of the session
 ELU_SEEN = {}
 
 
-def _abi():
-    from heterofusionrcnn_amd import _lib
-    return _lib, _lib.lib()
-
-
-def call(status, name):
-    _lib, _ = _abi()
-    _lib.check(status, name)
-
-
-@pytest.fixture(scope="module", autouse=True)
-def parity_report():
-    """BN_PARITY_OUT=<file>: the worst ratios of the session as JSON (the source of profiles/bn_parity.md)"""
-    yield
-    path = os.environ.get("BN_PARITY_OUT")
-    if path:
-        with open(path, "w") as f:
-            json.dump({"ratios": {"%s|%s" % k: v for k, v in sorted(RATIOS.items())}, "elu": ELU_SEEN}, f, indent=1)
-
-
-def within(got, want64, bound, name, family="round"):
-    diff = (got.double() - want64).abs()
-    bound = bound.expand_as(diff) if bound.shape != diff.shape else bound
-    ratio = float((diff / bound.clamp(min=1e-300)).max()) if diff.numel() else 0.0
-    print("%s [%s]: max |got - ref64| / bound = %.3g" % (name, family, ratio))
-    RATIOS[(name, family)] = max(RATIOS.get((name, family), 0.0), ratio)
-    ok = diff <= bound          # a NaN fails
-    assert bool(ok.all()), "%s: %d of %d elements outside c u M, worst ratio %.3g" % (name, int((~ok).sum()), got.numel(), ratio)
-
-
-class Arena:
-    """outputs as slices of sentinel-filled buffers; ld > columns: a column slice of wider rows whose other columns must keep the sentinel"""
-
-    def __init__(self):
-        self.slots = []
-
-    def out(self, shape, ld=0, init=None, off=False, dtype=torch.float32):
-        rows, cols = (shape[0], shape[1]) if len(shape) == 2 else (1, shape[0])
-        ld = ld or cols
-        start = GUARD + (1 if off else 0)
-        buf = torch.full((start + rows * ld + GUARD,), SENTINEL if dtype == torch.float32 else 0x5a, device=DEV, dtype=dtype)
-        wide = buf[start:start + rows * ld].view(rows, ld)
-        view = wide[:, :cols] if len(shape) == 2 else wide[0, :cols]
-        if init is not None:
-            view.copy_(init)
-        self.slots.append((buf, start, rows, ld, cols))
-        return view
-
-    def check(self):
-        if DEV == "cuda":
-            torch.cuda.synchronize()
-        for buf, start, rows, ld, cols in self.slots:
-            s = SENTINEL if buf.dtype == torch.float32 else 0x5a
-            assert bool((buf[:start] == s).all()) and bool((buf[start + rows * ld:] == s).all()), "write outside an output"
-            if ld > cols:
-                assert bool((buf[start:start + rows * ld].view(rows, ld)[:, cols:] == s).all()), "write into the gap columns of a strided output"
-
-    def untouched(self):
-        """every output still holds the sentinel: nothing was launched"""
-        self.check()
-        for buf, start, rows, ld, cols in self.slots:
-            s = SENTINEL if buf.dtype == torch.float32 else 0x5a
-            assert bool((buf == s).all()), "an output was written by a call that must be rejected"
-
-
-def place(t, off=False, ld=0):
-    """the tensor on the device at a 16-byte boundary (off: one float past one); ld: as a column slice of NaN-filled wider rows"""
-    if t is None:
-        return None
-    o = 1 if off else 0
-    if ld:
-        buf = torch.full((t.shape[0] * ld + 8,), float("nan"), dtype=t.dtype, device=DEV)
-        view = buf[o:o + t.shape[0] * ld].view(t.shape[0], ld)[:, :t.shape[1]]
-    else:
-        buf = torch.empty(t.numel() + 8, dtype=t.dtype, device=DEV)
-        view = buf[o:o + t.numel()].view(t.shape)
-    view.copy_(t)
-    return view
+parity_report = parity_report("BN_PARITY_OUT", ("hf_bn", "hf_narrow_linear_dx", "mean/std"), elu=ELU_SEEN)        # the source of profiles/bn_parity.md
 
 
 def workspace(a, rows, c):
-    _, L = _abi()
+    _, L = abi()
     nbytes = L.hf_bn_workspace(rows, c)
     assert nbytes == 4 * 2 * c * bc.BN_MAX_BLOCKS
     return a.out((nbytes // 4,)), nbytes
@@ -135,15 +55,6 @@ def running_init(d, c, ch):
     if is_exact(c):
         return d.ints((ch,), -8, 8) / 4, d.ints((ch,), 0, 8) / 4
     return d.normal((ch,)), d.uniform((ch,), 0.5, 1.5)
-
-
-def twice(run, c, t):
-    """every case is called twice: same bits (the header promises fixed-order reductions)"""
-    first, second = run(c, t), run(c, t)
-    for k in first:
-        if first[k] is not None:
-            assert torch.equal(first[k], second[k]), "%s differs between two calls" % k
-    return first
 
 
 # ------------------------------------------------------------------------------------------------------- statistics, forward
@@ -178,11 +89,11 @@ def stats_inputs(c):
 
 
 def run_stats(c, t, mom=None):
-    _lib, L = _abi()
+    _lib, L = abi()
     ptr, sp = _lib.ptr, _lib.stream_ptr()
     rows, ch = c["rows"], c["c"]
-    a = Arena()
-    x = place(t["x"])
+    a = Arena(DEV)
+    x = place(DEV, t["x"])
     mean, invstd, rm, rv = a.out((ch,)), a.out((ch,)), a.out((ch,), init=t["rm"]), a.out((ch,), init=t["rv"])
     ws, nbytes = workspace(a, rows, ch)
     call(L.hf_bn_stats(rows, ch, ptr(x), EPS, momentum(c) if mom is None else mom, ptr(rm), ptr(rv), ptr(mean), ptr(invstd), ptr(ws), nbytes, sp), "hf_bn_stats")
@@ -220,11 +131,11 @@ def train_inputs(c):
 
 
 def run_train(c, t):
-    _lib, L = _abi()
+    _lib, L = abi()
     ptr, sp = _lib.ptr, _lib.stream_ptr()
     rows, ch, ld = c["rows"], c["c"], c["ld"]
-    a = Arena()
-    x, gamma, beta = place(t["x"]), place(t["gamma"]), place(t["beta"])
+    a = Arena(DEV)
+    x, gamma, beta = place(DEV, t["x"]), place(DEV, t["gamma"]), place(DEV, t["beta"])
     y = a.out((rows, ch), ld=ld)
     mean, invstd, rm, rv = a.out((ch,)), a.out((ch,)), a.out((ch,), init=t["rm"]), a.out((ch,), init=t["rv"])
     ws, nbytes = workspace(a, rows, ch)
@@ -258,12 +169,12 @@ def eval_inputs(c):
 
 
 def run_eval(c, t):
-    _lib, L = _abi()
+    _lib, L = abi()
     ptr, sp = _lib.ptr, _lib.stream_ptr()
     rows, ch = c["rows"], c["c"]
-    a = Arena()
-    x = place(t["x"])
-    bn = [place(v) for v in t["bn"]]
+    a = Arena(DEV)
+    x = place(DEV, t["x"])
+    bn = [place(DEV, v) for v in t["bn"]]
     y = a.out((rows, ch))
     call(L.hf_bn_relu_fwd_eval(rows, ch, ptr(x), ptr(bn[0]), ptr(bn[1]), ptr(bn[2]), ptr(bn[3]), c["relu"], ptr(y), sp), "hf_bn_relu_fwd_eval")
     a.check()
@@ -300,12 +211,12 @@ def bwd_inputs(c):
 
 
 def run_bwd(c, t):
-    _lib, L = _abi()
+    _lib, L = abi()
     ptr, sp = _lib.ptr, _lib.stream_ptr()
     rows, ch, ld = c["rows"], c["c"], c["ld"]
-    a = Arena()
-    x, dy = place(t["x"]), place(t["dy"], ld=ld)
-    bn = [place(v) for v in t["bn"]]
+    a = Arena(DEV)
+    x, dy = place(DEV, t["x"]), place(DEV, t["dy"], ld=ld)
+    bn = [place(DEV, v) for v in t["bn"]]
     dx, dgamma, dbeta = a.out((rows, ch)), a.out((ch,)), a.out((ch,))
     colsum = a.out((ch,)) if c["colsum"] else None
     ws, nbytes = workspace(a, rows, ch)
@@ -350,12 +261,12 @@ def test_bn_relu_bwd(c):
 
 
 def run_bwd_dx(c, t):
-    _lib, L = _abi()
+    _lib, L = abi()
     ptr, sp = _lib.ptr, _lib.stream_ptr()
     rows, ch = c["rows"], c["c"]
-    a = Arena()
-    x, dy, dgamma, dbeta = place(t["x"]), place(t["dy"]), place(t["dgamma"]), place(t["dbeta"])
-    bn = [place(v) for v in t["bn"]]
+    a = Arena(DEV)
+    x, dy, dgamma, dbeta = place(DEV, t["x"]), place(DEV, t["dy"]), place(DEV, t["dgamma"]), place(DEV, t["dbeta"])
+    bn = [place(DEV, v) for v in t["bn"]]
     dx = a.out((rows, ch))
     call(L.hf_bn_relu_bwd_dx(rows, ch, ptr(x), ptr(dy), ptr(bn[0]), ptr(bn[1]), ptr(bn[2]), ptr(bn[3]), ptr(dgamma), ptr(dbeta), c["relu"], ptr(dx), sp),
          "hf_bn_relu_bwd_dx")
@@ -399,12 +310,12 @@ def _i64(v):
 
 def run_drop(c, t):
     """two consecutive forward calls on one layer state, then the backward pass with the seed the second call returned"""
-    _lib, L = _abi()
+    _lib, L = abi()
     ptr, sp = _lib.ptr, _lib.stream_ptr()
     rows, ch, relu, rate, salt = c["rows"], c["c"], c["relu"], c["rate"], c["salt"]
-    a = Arena()
-    x, gamma, beta, dy = place(t["x"]), place(t["gamma"]), place(t["beta"]), place(t["dy"])
-    bn = [place(v) for v in t["bn"]]
+    a = Arena(DEV)
+    x, gamma, beta, dy = place(DEV, t["x"]), place(DEV, t["gamma"]), place(DEV, t["beta"]), place(DEV, t["dy"])
+    bn = [place(DEV, v) for v in t["bn"]]
     state = torch.tensor([_i64(STATE0 + ch), CALLS_BEFORE], dtype=torch.int64, device=DEV)
     out = {}
     for n in (1, 2):
@@ -511,13 +422,13 @@ def pool_reference(c, z, gamma, beta, mean, invstd):
 
 
 def run_pool(c, t):
-    _lib, L = _abi()
+    _lib, L = abi()
     ptr, sp = _lib.ptr, _lib.stream_ptr()
     g, k, ch, tr = c["groups"], c["k"], c["c"], c["training"]
-    a = Arena()
-    z, dp = place(t["z"]), place(t["dp"])
-    bn = [place(v) for v in t["bn"]]
-    gamma, beta = (place(t["gamma"]), place(t["beta"])) if tr else (bn[0], bn[1])
+    a = Arena(DEV)
+    z, dp = place(DEV, t["z"]), place(DEV, t["dp"])
+    bn = [place(DEV, v) for v in t["bn"]]
+    gamma, beta = (place(DEV, t["gamma"]), place(DEV, t["beta"])) if tr else (bn[0], bn[1])
     pooled, argmax = a.out((g, ch)), a.out((g, ch), dtype=torch.uint8)
     ws, nbytes = workspace(a, g * k, ch)
     if tr:
@@ -529,7 +440,7 @@ def run_pool(c, t):
     a.check()
     # backward: the statistics are plain inputs; it runs on the given ones and on the reference's arg-max under them
     _, _, idx = pool_reference(c, t["z"], *t["bn"])
-    am = place(idx.to(torch.uint8))
+    am = place(DEV, idx.to(torch.uint8))
     dz, dgamma, dbeta = a.out((g * k, ch)), a.out((ch,)), a.out((ch,))
     colsum = a.out((ch,)) if c["colsum"] else None
     ws2, nbytes = workspace(a, g * k, ch)
@@ -573,10 +484,10 @@ def narrow_inputs(c):
 
 
 def run_narrow(c, t):
-    _lib, L = _abi()
+    _lib, L = abi()
     ptr, sp = _lib.ptr, _lib.stream_ptr()
-    a = Arena()
-    g, w = place(t["g"]), place(t["w"])
+    a = Arena(DEV)
+    g, w = place(DEV, t["g"]), place(DEV, t["w"])
     dx = a.out((c["rows"], c["cin"]))
     call(L.hf_narrow_linear_dx(c["rows"], c["cin"], c["cout"], ptr(g), ptr(w), ptr(dx), sp), "hf_narrow_linear_dx")
     a.check()
@@ -622,14 +533,14 @@ def test_elu_constant_covers_the_hardware_exponential():
 def test_bad_arguments_are_rejected_before_anything_is_launched():
     """completes test_mlp_entry_points_reject_bad_arguments: every call below returns HF_EINVAL (HF_EWORKSPACE for the short
     workspace) and leaves every output buffer at the sentinel"""
-    _lib, L = _abi()
+    _lib, L = abi()
     ptr, sp = _lib.ptr, _lib.stream_ptr()
     EINVAL, EWS = _lib.HF_EINVAL, _lib.HF_EWORKSPACE
     rows, ch = 64, 8
-    a = Arena()
-    x = place(torch.ones(rows, ch))
-    xo = place(torch.ones(rows, ch), off=True)
-    v = place(torch.ones(ch))
+    a = Arena(DEV)
+    x = place(DEV, torch.ones(rows, ch))
+    xo = place(DEV, torch.ones(rows, ch), off=True)
+    v = place(DEV, torch.ones(ch))
     y, yo, wide = a.out((rows, ch)), a.out((rows, ch), off=True), a.out((rows, ch), ld=ch + 2)
     o1, o2, o3 = a.out((ch,)), a.out((ch,)), a.out((ch,))
     am = a.out((rows, ch), dtype=torch.uint8)
@@ -677,19 +588,19 @@ def test_channel_limits_are_rejected_before_anything_is_launched():
     """include/hfops.h: c <= 4096, and c <= 1024 where c % 4 != 0 (a workgroup then has c threads per row).  One past each limit is
     HF_EINVAL with every output untouched; the limit itself is served (1023: the widest scalar-width row; 4096) and checked against fp64 by
     the cases (1500, 1023) and (7, 4096) / (12803, 4096) above"""
-    _lib, L = _abi()
+    _lib, L = abi()
     ptr, sp = _lib.ptr, _lib.stream_ptr()
     EINVAL = _lib.HF_EINVAL
     rows = 8
     for ch, want in ((1023, 0), (1024, 0), (1025, EINVAL), (2047, EINVAL), (4095, EINVAL), (4096, 0), (4097, EINVAL), (4100, EINVAL)):
         assert bc.launch_limit_ok(ch) == (want == 0)
-        a = Arena()
-        x = place(torch.ones(rows, ch))
-        v, z0 = place(torch.ones(ch)), place(torch.zeros(ch))
-        g4 = place(torch.ones(rows, 4))
+        a = Arena(DEV)
+        x = place(DEV, torch.ones(rows, ch))
+        v, z0 = place(DEV, torch.ones(ch)), place(DEV, torch.zeros(ch))
+        g4 = place(DEV, torch.ones(rows, 4))
         y, o1, o2, o3 = a.out((rows, ch)), a.out((ch,)), a.out((ch,)), a.out((ch,))
         pooled, am = a.out((rows // 4, ch)), a.out((rows // 4, ch), dtype=torch.uint8)
-        am0, dp = place(torch.zeros(rows // 4, ch, dtype=torch.uint8)), place(torch.ones(rows // 4, ch))
+        am0, dp = place(DEV, torch.zeros(rows // 4, ch, dtype=torch.uint8)), place(DEV, torch.ones(rows // 4, ch))
         state, seed = a.out((2,), dtype=torch.int64), a.out((1,), dtype=torch.int64)
         n = 4 * 2 * ch * bc.BN_MAX_BLOCKS
         ws = a.out((n // 4,))

@@ -11,7 +11,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import bn_cases as bc  # noqa: E402
-from test_gemm_instantiations_cpu import compile_to_assembly, kernel_table  # noqa: E402
+from kernel_asm import compile_to_assembly, kernel_table  # noqa: E402
 
 MAX_THREADS = 1024
 LDS_PER_WORKGROUP = 64 * 1024

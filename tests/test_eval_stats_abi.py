@@ -14,42 +14,11 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import eval_stats_cases as ec  # noqa: E402
+from abi_harness import Workspace, abi, dev, filled, host, same_array  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-GUARD, GUARD_BYTE = 256, 0xA5
-
-
-def _abi():
-    from heterofusionrcnn_amd import _lib
-    return _lib, _lib.lib()
-
-
-def dev(a):
-    return torch.from_numpy(np.array(a)).cuda()          # a copy: the shared case inputs are read-only
-
-
-def host(t):
-    return t.detach().cpu().numpy()
-
-
-def filled(shape, dtype):
-    return torch.full(shape, float("nan") if dtype.is_floating_point else ec.SENT_I, dtype=dtype, device="cuda")
-
-
-class Workspace:
-    """exactly nbytes between two guards"""
-
-    def __init__(self, nbytes):
-        self.nbytes = int(nbytes)
-        self.buf = torch.full((self.nbytes + 2 * GUARD,), GUARD_BYTE, dtype=torch.uint8, device="cuda")
-        assert self.buf.data_ptr() % 256 == 0
-        self.p = ctypes.c_void_p(self.buf.data_ptr() + GUARD)
-
-    def check(self, what):
-        torch.cuda.synchronize()
-        assert bool((self.buf[:GUARD] == GUARD_BYTE).all()), "%s: the guard below the workspace was written" % what
-        assert bool((self.buf[GUARD + self.nbytes:] == GUARD_BYTE).all()), "%s: the guard above the workspace was written" % what
+DEV = "cuda"
 
 
 def written(got, what, c):
@@ -62,25 +31,21 @@ def written(got, what, c):
 
 
 def same(got, want, what, c):
-    got, want = written(got, what, c), np.asarray(want)
-    assert got.shape == want.shape and got.dtype == want.dtype, (what, got.shape, want.shape, got.dtype, want.dtype)
-    if not np.array_equal(got, want):
-        bad = np.argwhere(got != want)
-        raise AssertionError("%s of %s: %d of %d elements differ, the first at %s: got %r, want %r"
-                             % (what, ec.case_id(c), len(bad), got.size, tuple(bad[0]), got[tuple(bad[0])], want[tuple(bad[0])]))
+    same_array(got, want, what, ec.case_id(c), unwritten=ec.SENT_I)
 
 
 def _call(L, _lib, c, ins, with_matrices):
     b, m, g = c["b"], c["m"], c["g"]
     props, pc, gt, gc = ins
-    out = {"best_iou3d": filled((b, m), torch.float32), "best_iou2d": filled((b, m), torch.float32), "best_gt": filled((b, m), torch.int32),
-           "counts": filled((b, 4), torch.int32), "sums": filled((b, 3), torch.float64)}
+    out = {"best_iou3d": filled(DEV, (b, m), torch.float32, ec.SENT_I), "best_iou2d": filled(DEV, (b, m), torch.float32, ec.SENT_I),
+           "best_gt": filled(DEV, (b, m), torch.int32, ec.SENT_I),
+           "counts": filled(DEV, (b, 4), torch.int32, ec.SENT_I), "sums": filled(DEV, (b, 3), torch.float64, ec.SENT_I)}
     if with_matrices:
-        out["iou3d"], out["iou2d"] = filled((b, m, g), torch.float32), filled((b, m, g), torch.float32)
+        out["iou3d"], out["iou2d"] = filled(DEV, (b, m, g), torch.float32, ec.SENT_I), filled(DEV, (b, m, g), torch.float32, ec.SENT_I)
     nbytes = L.hf_proposal_stats_workspace(b, m, g)
     pad = lambda v: (v + 255) & ~255
     assert nbytes == 2 * pad(4 * b * m * g)
-    ws = Workspace(nbytes)
+    ws = Workspace(DEV, nbytes)
     _lib.check(L.hf_proposal_stats(b, m, g, _lib.ptr(props), _lib.ptr(pc), _lib.ptr(gt) if g > 0 else None, _lib.ptr(gc),
                                    _lib.ptr(out.get("iou3d")), _lib.ptr(out.get("iou2d")), _lib.ptr(out["best_iou3d"]),
                                    _lib.ptr(out["best_iou2d"]), _lib.ptr(out["best_gt"]), _lib.ptr(out["counts"]), _lib.ptr(out["sums"]),
@@ -99,8 +64,8 @@ def _existing_matrices(t, c):
     iou2 = np.zeros((b, m, g), np.float32)
     if g == 0:
         return iou3, iou2
-    props, gt = dev(t["proposals"]), dev(t["gt"])
-    iou3 = host(box3d_iou_matrix(props, dev(t["proposal_count"]), gt, dev(t["gt_count"])))
+    props, gt = dev(DEV, t["proposals"]), dev(DEV, t["gt"])
+    iou3 = host(box3d_iou_matrix(props, dev(DEV, t["proposal_count"]), gt, dev(DEV, t["gt_count"])))
     for f, fr in enumerate(c["frames"]):
         n, ng = fr["n"], fr["ng"]
         if n and ng:
@@ -111,10 +76,10 @@ def _existing_matrices(t, c):
 
 @pytest.mark.parametrize("c", ec.PROPOSAL_CASES, ids=ec.case_id)
 def test_proposal_stats(c):
-    _lib, L = _abi()
+    _lib, L = abi()
     t = ec.make_proposal_inputs(c)
     b, m, g = c["b"], c["m"], c["g"]
-    ins = [dev(t[k]) for k in ("proposals", "proposal_count", "gt", "gt_count")]
+    ins = [dev(DEV, t[k]) for k in ("proposals", "proposal_count", "gt", "gt_count")]
     out = _call(L, _lib, c, ins, True)
     iou3, iou2 = _existing_matrices(t, c)
     same(out["iou3d"], iou3, "iou3d against hf_box3d_iou_matrix", c)
@@ -146,12 +111,12 @@ def test_proposal_stats(c):
 def test_proposal_stats_wrapper_writes_table_rows():
     """validate.proposal_stats into rows of a larger table equals the forced call"""
     from heterofusionrcnn_amd import validate
-    _lib, L = _abi()
+    _lib, L = abi()
     c = next(x for x in ec.PROPOSAL_CASES if x["name"] == "m63_g3_empty_frame_between")
     t = ec.make_proposal_inputs(c)
-    ins = [dev(t[k]) for k in ("proposals", "proposal_count", "gt", "gt_count")]
+    ins = [dev(DEV, t[k]) for k in ("proposals", "proposal_count", "gt", "gt_count")]
     want = _call(L, _lib, c, ins, True)
-    counts, sums = filled((7, 4), torch.int32), filled((7, 3), torch.float64)
+    counts, sums = filled(DEV, (7, 4), torch.int32, ec.SENT_I), filled(DEV, (7, 3), torch.float64, ec.SENT_I)
     got = validate.proposal_stats(*ins, counts=counts[2:5], sums=sums[2:5], matrices=True)
     for k in want:
         assert host(want[k]).tobytes() == host(got[k]).tobytes(), k
@@ -162,12 +127,12 @@ def test_proposal_stats_wrapper_writes_table_rows():
 @pytest.mark.parametrize("case", ec.ACCURACY_CASES, ids=ec.case_id)
 def test_argmax_accuracy(case):
     from heterofusionrcnn_amd import validate
-    _lib, L = _abi()
+    _lib, L = abi()
     rpg, groups, c = case
     logits, target = ec.make_accuracy_inputs(case)
     want = ec.ref_argmax_accuracy(logits, target, groups)
-    lg, tg = dev(logits), dev(target)
-    table = filled((groups + 2,), torch.int32)
+    lg, tg = dev(DEV, logits), dev(DEV, target)
+    table = filled(DEV, (groups + 2,), torch.int32, ec.SENT_I)
     out = table[1:1 + groups]
     _lib.check(L.hf_argmax_accuracy(rpg * groups, c, groups, _lib.ptr(lg), _lib.ptr(tg), ctypes.c_void_p(out.data_ptr()), _lib.stream_ptr()),
                "argmax_accuracy")

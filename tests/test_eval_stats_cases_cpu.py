@@ -9,6 +9,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import eval_stats_cases as ec  # noqa: E402
+from abi_harness import abi  # noqa: E402
 
 
 def test_the_cases_cover_what_the_kernels_branch_on():
@@ -98,13 +99,8 @@ def test_accuracy_restatement_and_cases():
             assert got[0] == rpg and got[1] == 0
 
 
-def _abi():
-    from heterofusionrcnn_amd import _lib
-    return _lib, _lib.lib()
-
-
 def test_proposal_stats_rejects_arguments_outside_the_limits():
-    _lib, L = _abi()
+    _lib, L = abi()
     one = ctypes.c_void_p(256)                # never dereferenced: the checks come first
     call = lambda b, m, g: L.hf_proposal_stats(b, m, g, one, one, one, one, None, None, one, one, one, one, one, one, 1 << 40, None)
     for b, m, g in ((-1, 1, 1), (ec.MAX_B + 1, 1, 1), (1, 0, 1), (1, -3, 1), (1, ec.MAX_M + 1, 1), (1, 1, -1), (1, 1, ec.MAX_G + 1)):
@@ -123,7 +119,7 @@ def test_proposal_stats_rejects_arguments_outside_the_limits():
 
 
 def test_argmax_accuracy_rejects_arguments_outside_the_limits():
-    _lib, L = _abi()
+    _lib, L = abi()
     one = ctypes.c_void_p(256)
     for rows, c, groups in ((8, 1, 1), (8, 9, 1), (8, 0, 1), (8, 4, 0), (8, 4, -1), (8, 4, 3), (-4, 4, 1)):
         assert L.hf_argmax_accuracy(rows, c, groups, one, one, one, None) == _lib.HF_EINVAL, (rows, c, groups)

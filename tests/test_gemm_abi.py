@@ -15,77 +15,14 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import gemm_cases as gc  # noqa: E402
+from abi_harness import Arena, abi, call, place, same, within  # noqa: E402
+from gemm_runs import UNSET, lift_inputs, run_lift_bwd  # noqa: E402,F401  (test_gemm_cases_cpu.py replaces run_lift_bwd here)
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
-SENTINEL = 12345.0
-GUARD = 64          # floats either side of an output: 256 bytes, keeps the slice's 16-byte alignment
 EPS, MOMENTUM = 1e-3, 0.1
 TWO24 = float(2 ** 24)
-
-
-def _abi():
-    from heterofusionrcnn_amd import _lib
-    assert "HF_GEMM_ROUNDS" not in os.environ, "gemm_cases.resident_grid restates the product library's two rounds"
-    return _lib, _lib.lib()
-
-
-class Arena:
-    """outputs as slices of sentinel-filled buffers"""
-
-    def __init__(self):
-        self.slots = []
-
-    def out(self, shape, off=False, init=None):
-        n = 1
-        for s in shape:
-            n *= s
-        start = GUARD + (1 if off else 0)
-        buf = torch.full((start + n + GUARD,), SENTINEL, device=DEV)
-        view = buf[start:start + n].view(shape)
-        if init is not None:
-            view.copy_(init)
-        self.slots.append((buf, start, n))
-        return view
-
-    def check(self):
-        torch.cuda.synchronize()
-        for buf, start, n in self.slots:
-            assert bool((buf[:start] == SENTINEL).all()) and bool((buf[start + n:] == SENTINEL).all()), "write outside an output"
-
-
-def place(t, off=False):
-    """the tensor on the device, at a 16-byte boundary or (off) one float past one"""
-    if t is None:
-        return None
-    buf = torch.empty(t.numel() + 8, dtype=t.dtype, device=DEV)
-    view = buf[(1 if off else 0):(1 if off else 0) + t.numel()].view(t.shape)
-    view.copy_(t)
-    assert view.data_ptr() % 16 == (4 if off else 0)
-    return view
-
-
-def same(got, want64, name):
-    want = want64.float()
-    if not torch.equal(got, want):
-        bad = (got != want) | torch.isnan(got)
-        idx = bad.nonzero()[0].tolist()
-        raise AssertionError("%s: %d of %d elements differ from the fp64 reference, first at %s: %r != %r" % (
-            name, int(bad.sum()), got.numel(), idx, float(got[tuple(idx)]), float(want[tuple(idx)])))
-
-
-def within(got, want64, bound, name):
-    diff = (got.double() - want64).abs()
-    ratio = float((diff / bound.clamp(min=1e-300)).max()) if diff.numel() else 0.0
-    print("%s: max |got - ref64| / bound = %.3g" % (name, ratio))
-    ok = diff <= bound          # a NaN fails
-    assert bool(ok.all()), "%s: %d of %d elements outside c u M, worst ratio %.3g" % (name, int((~ok).sum()), got.numel(), ratio)
-
-
-def call(status, name):
-    _lib, _ = _abi()
-    _lib.check(status, name)
 
 
 # ------------------------------------------------------------------------------------------------------- forward
@@ -113,13 +50,13 @@ def fwd_inputs(c):
 
 
 def run_fwd(c, t):
-    _lib, L = _abi()
+    _lib, L = abi(UNSET)
     ptr, sp = _lib.ptr, _lib.stream_ptr()
     rows, cin, cout, mis = c["rows"], c["cin"], c["cout"], c["misalign"]
-    a = Arena()
-    x, w = place(t["x"], mis == "x"), place(t["w"], mis == "weight")
-    bias = place(t["bias"])
-    bn = [place(v) for v in t["bn"]] if t["bn"] else [None] * 4
+    a = Arena(DEV)
+    x, w = place(DEV, t["x"], mis == "x"), place(DEV, t["w"], mis == "weight")
+    bias = place(DEV, t["bias"])
+    bn = [place(DEV, v) for v in t["bn"]] if t["bn"] else [None] * 4
     z, mean, invstd = a.out((rows, cout)), a.out((cout,)), a.out((cout,))
     xact = a.out((rows, cin), off=mis == "x_act") if c["xact"] else None
     rm = a.out((cout,), init=t["rm"]) if c["running"] in (1, 2) else None
@@ -212,15 +149,15 @@ def bwd_inputs(c):
 
 
 def run_bwd(c, t):
-    _lib, L = _abi()
+    _lib, L = abi(UNSET)
     ptr, sp = _lib.ptr, _lib.stream_ptr()
     rows, cout, cin, form, mis = c["rows"], c["cout"], c["cin"], c["form"], c["misalign"]
     from_dy, sums = form.startswith("dy"), form.endswith("sums")
-    a = Arena()
-    dy, wt, z = place(t["dy"], mis == "dy"), place(t["wt"], mis == "weight_t"), place(t["z"], mis == "z")
-    bn = [place(v) for v in t["bn"]] if t["bn"] else [None] * 4
-    pbn = [place(v) for v in t["pbn"]] if t["pbn"] else [None] * 4
-    dgamma, dbeta, zprev = place(t["dgamma"]), place(t["dbeta"]), place(t["zprev"])
+    a = Arena(DEV)
+    dy, wt, z = place(DEV, t["dy"], mis == "dy"), place(DEV, t["wt"], mis == "weight_t"), place(DEV, t["z"], mis == "z")
+    bn = [place(DEV, v) for v in t["bn"]] if t["bn"] else [None] * 4
+    pbn = [place(DEV, v) for v in t["pbn"]] if t["pbn"] else [None] * 4
+    dgamma, dbeta, zprev = place(DEV, t["dgamma"]), place(DEV, t["dbeta"]), place(DEV, t["zprev"])
     dx = a.out((rows, cin)) if "dx" in form else None
     dz_out = a.out((rows, cout), off=mis == "dz_out") if from_dy else None
     pdg, pdb = (a.out((cin,)), a.out((cin,))) if sums else (None, None)
@@ -281,12 +218,12 @@ def wgrad_inputs(c):
 
 
 def run_wgrad(c, t, short_by=0):
-    _lib, L = _abi()
+    _lib, L = abi(UNSET)
     ptr, sp = _lib.ptr, _lib.stream_ptr()
     rows, cout, cin, mis = c["rows"], c["cout"], c["cin"], c["misalign"]
-    a = Arena()
-    gz, x = place(t["g"], mis == "grad_z"), place(t["x"], mis == "x")
-    bn = [place(v) for v in t["bn"]] if t["bn"] else [None] * 4
+    a = Arena(DEV)
+    gz, x = place(DEV, t["g"], mis == "grad_z"), place(DEV, t["x"], mis == "x")
+    bn = [place(DEV, v) for v in t["bn"]] if t["bn"] else [None] * 4
     dw = a.out((cout, cin))
     nbytes = L.hf_linear_wgrad_workspace(rows, cout, cin)
     assert nbytes == 4 * gc.wgrad_plan(rows, cout, cin)[3] * cout * cin
@@ -329,12 +266,12 @@ def gather_inputs(c):
 
 
 def run_gather_fwd(c, t):
-    _lib, L = _abi()
+    _lib, L = abi(UNSET)
     ptr, sp = _lib.ptr, _lib.stream_ptr()
     rows, cout, mis = t["rows"], c["cout"], c["misalign"]
-    a = Arena()
-    points, idx, gxyz = place(t["points"], mis == "points"), place(t["idx"]), place(t["gxyz"])
-    w, bias = place(t["w"], mis == "weight"), place(t["bias"])
+    a = Arena(DEV)
+    points, idx, gxyz = place(DEV, t["points"], mis == "points"), place(DEV, t["idx"]), place(DEV, t["gxyz"])
+    w, bias = place(DEV, t["w"], mis == "weight"), place(DEV, t["bias"])
     z, mean, invstd = a.out((rows, cout)), a.out((cout,)), a.out((cout,))
     nbytes = L.hf_linear_bn_fwd_workspace(cout)
     ws = a.out((nbytes // 4,))
@@ -345,11 +282,11 @@ def run_gather_fwd(c, t):
 
 
 def run_gather_wgrad(c, t):
-    _lib, L = _abi()
+    _lib, L = abi(UNSET)
     ptr, sp = _lib.ptr, _lib.stream_ptr()
     rows, cout, cin, mis = t["rows"], c["cout"], t["cin"], c["misalign"]
-    a = Arena()
-    points, idx, gxyz, gz = place(t["points"], mis == "points"), place(t["idx"]), place(t["gxyz"]), place(t["g"], mis == "grad_z")
+    a = Arena(DEV)
+    points, idx, gxyz, gz = place(DEV, t["points"], mis == "points"), place(DEV, t["idx"]), place(DEV, t["gxyz"]), place(DEV, t["g"], mis == "grad_z")
     dw = a.out((cout, cin))
     nbytes = L.hf_linear_wgrad_workspace(rows, cout, cin)
     ws = a.out((nbytes // 4,))
@@ -383,29 +320,13 @@ def test_linear_wgrad_gather(c):
 
 
 # ------------------------------------------------------------------------------------------------------- lifting family
-def lift_inputs(c):
-    g = gc.generator(c)
-    rows, c0, c1, exact = c["rows"], c["c0"], c["c1"], c["family"] == "exact"
-    if exact:       # non-negative x3 W0^T, gamma0 = invstd0 = 1, y0 >= 0; eval_bn: W1 >= 0 too, so that the epilogue's ELU is the identity
-        t = dict(x3=gc.ints(g, (rows, 3), 0, 2), w0=gc.ints(g, (c0, 3), 0, 2), bn0=gc.bn_consts(g, c0, True, nonneg=True),
-                 w1=gc.ints(g, (c1, c0), 0 if c["kind"] != "lift_eval" else -2, 2), bn1=gc.bn_consts(g, c1, True), dz1=gc.ints(g, (rows, c1), -2, 2))
-    else:
-        t = dict(x3=torch.randn(rows, 3, generator=g) * 0.5, w0=torch.randn(c0, 3, generator=g), bn0=gc.bn_consts(g, c0, False),
-                 w1=torch.randn(c1, c0, generator=g) * 0.3, bn1=gc.bn_consts(g, c1, False), dz1=torch.randn(rows, c1, generator=g))
-    for k in ("rm0", "rm1"):
-        t[k] = torch.randn(c0 if k == "rm0" else c1, generator=g)
-    for k in ("rv0", "rv1"):
-        t[k] = torch.rand(c0 if k == "rv0" else c1, generator=g) + 0.5
-    return t
-
-
 def run_lift_eval(c, t, w1_off=False):
-    _lib, L = _abi()
+    _lib, L = abi(UNSET)
     ptr, sp = _lib.ptr, _lib.stream_ptr()
     rows, c0, c1 = c["rows"], c["c0"], c["c1"]
-    a = Arena()
-    x3, w0, w1 = place(t["x3"]), place(t["w0"]), place(t["w1"], w1_off)
-    bn0, bn1 = [place(v) for v in t["bn0"]], [place(v) for v in t["bn1"]]
+    a = Arena(DEV)
+    x3, w0, w1 = place(DEV, t["x3"]), place(DEV, t["w0"]), place(DEV, t["w1"], w1_off)
+    bn0, bn1 = [place(DEV, v) for v in t["bn0"]], [place(DEV, v) for v in t["bn1"]]
     out = a.out((rows, c1))
     nbytes = L.hf_lift_elu_bn_fwd_workspace(c0, c1)
     ws = a.out((nbytes // 4,))
@@ -438,11 +359,11 @@ def test_lift_elu_fwd_eval(c):
 
 
 def run_lift_train(c, t):
-    _lib, L = _abi()
+    _lib, L = abi(UNSET)
     ptr, sp = _lib.ptr, _lib.stream_ptr()
     rows, c0, c1 = c["rows"], c["c0"], c["c1"]
-    a = Arena()
-    x3, w0, w1, g0, b0 = place(t["x3"]), place(t["w0"]), place(t["w1"]), place(t["bn0"][0]), place(t["bn0"][1])
+    a = Arena(DEV)
+    x3, w0, w1, g0, b0 = place(DEV, t["x3"]), place(DEV, t["w0"]), place(DEV, t["w1"]), place(DEV, t["bn0"][0]), place(DEV, t["bn0"][1])
     z1 = a.out((rows, c1))
     mean0, invstd0, mean1, invstd1 = a.out((c0,)), a.out((c0,)), a.out((c1,)), a.out((c1,))
     rm0, rv0, rm1, rv1 = a.out((c0,), init=t["rm0"]), a.out((c0,), init=t["rv0"]), a.out((c1,), init=t["rm1"]), a.out((c1,), init=t["rv1"])
@@ -477,23 +398,6 @@ def check_lift_train(c, t, got):
 def test_lift_elu_bn_fwd(c):
     t = lift_inputs(c)
     check_lift_train(c, t, run_lift_train(c, t))
-
-
-def run_lift_bwd(c, t, stats):
-    _lib, L = _abi()
-    ptr, sp = _lib.ptr, _lib.stream_ptr()
-    rows, c0, c1, mis = c["rows"], c["c0"], c["c1"], c["misalign"]
-    a = Arena()
-    x3, w0, g0, b0 = place(t["x3"]), place(t["w0"]), place(t["bn0"][0]), place(t["bn0"][1])
-    mean0, invstd0 = place(stats[0]), place(stats[1])
-    dz1, w1t = place(t["dz1"], mis == "dz1"), place(t["w1"].t().contiguous(), mis == "w1_t")
-    gw0t, gw1, dg0, db0 = a.out((3, c0)), a.out((c1, c0)), a.out((c0,)), a.out((c0,))
-    nbytes = L.hf_lift_elu_bn_bwd_workspace(rows, c0, c1)
-    ws = a.out((nbytes // 4,))
-    call(L.hf_lift_elu_bn_bwd(rows, c0, c1, ptr(x3), ptr(w0), ptr(g0), ptr(b0), ptr(mean0), ptr(invstd0), ptr(dz1), ptr(w1t), ptr(gw0t), ptr(gw1),
-                              ptr(dg0), ptr(db0), ptr(ws), nbytes, sp), "hf_lift_elu_bn_bwd")
-    a.check()
-    return dict(grad_w0_t=gw0t, grad_w1=gw1, dgamma0=dg0, dbeta0=db0)
 
 
 @pytest.mark.parametrize("c", gc.sweep_cases("lift_bwd"), ids=gc.case_id)
@@ -571,7 +475,7 @@ def test_two_calls_give_the_same_bits(c):
 def test_limits_are_rejected_before_anything_is_launched():
     """completes test_mlp_entry_points_reject_bad_arguments: one past each documented limit of include/hfops.h is HF_EINVAL, the limit
     itself is accepted by the same call"""
-    _lib, L = _abi()
+    _lib, L = abi(UNSET)
     sp = _lib.stream_ptr()
     EINVAL, EWS = _lib.HF_EINVAL, _lib.HF_EWORKSPACE
     buf = torch.zeros(32 * 16384, device=DEV)

@@ -16,10 +16,12 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import geometry_cases as gc  # noqa: E402
+from abi_harness import dev, host, same_array  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 IDX_SENTINEL = -7
+DEV = "cuda"
 
 
 @pytest.fixture(scope="module")
@@ -29,21 +31,8 @@ def hf():
     return m
 
 
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def host(t):
-    return t.detach().cpu().numpy()
-
-
 def same(got, want, what, c):
-    got = host(got)
-    assert got.shape == want.shape and got.dtype == want.dtype, (what, got.shape, want.shape, got.dtype, want.dtype)
-    if not np.array_equal(got, want):
-        bad = np.argwhere(got != want)
-        raise AssertionError("%s of %s: %d of %d elements differ, the first at %s: got %r, want %r"
-                             % (what, gc.case_id(c), len(bad), got.size, tuple(bad[0]), got[tuple(bad[0])], want[tuple(bad[0])]))
+    same_array(got, want, what, gc.case_id(c))
 
 
 # ---------------------------------------------------------------------------------------------- farthest point sampling
@@ -51,7 +40,7 @@ def same(got, want, what, c):
 def test_geometry_fps(hf, oracle_mod, c):
     t = gc.make_inputs(c)
     want = gc.oracle_outputs(c, t, oracle_mod)["out"]
-    x = dev(t["xyz"])
+    x = dev(DEV, t["xyz"])
     got = hf.farthest_point_sample(c["m"], x, kernel=c["kernel"], threads=c["threads"])
     same(got, want, "picks", c)
     same(hf.farthest_point_sample(c["m"], x), want, "picks of the automatic choice", c)
@@ -69,7 +58,7 @@ def _ball_query_abi(c, t):
     buf[start:start + b * n * 3].copy_(torch.from_numpy(t["xyz1"].reshape(-1)))
     x1 = ctypes.c_void_p(buf.data_ptr() + 4 * start)
     assert x1.value % 16 == (4 if c["off"] else 0)
-    x2 = dev(t["xyz2"])
+    x2 = dev(DEV, t["xyz2"])
     idx = torch.full((b, m, ns), IDX_SENTINEL, dtype=torch.int32, device="cuda")
     cnt = torch.full((b, m), IDX_SENTINEL, dtype=torch.int32, device="cuda")
     grouped = torch.full((b, m, ns, 3), float("nan"), dtype=torch.float32, device="cuda") if c["group"] else None
@@ -87,7 +76,7 @@ def _ball_query_abi(c, t):
 
 
 def _ball_query_wrapper(hf, c, t, variant):
-    x1, x2 = dev(t["xyz1"]), dev(t["xyz2"])
+    x1, x2 = dev(DEV, t["xyz1"]), dev(DEV, t["xyz2"])
     if c["group"]:
         return hf.query_ball_group(c["radius"], c["nsample"], x1, x2, center=c["center"], variant=variant)
     return hf.query_ball_point(c["radius"], c["nsample"], x1, x2, variant=variant) + (None,)
@@ -111,7 +100,7 @@ def test_geometry_ball_query(hf, oracle_mod, c):
 def test_geometry_knn(hf, oracle_mod, c):
     t = gc.make_inputs(c)
     want = gc.oracle_outputs(c, t, oracle_mod)
-    x1, x2 = dev(t["xyz1"]), dev(t["xyz2"])
+    x1, x2 = dev(DEV, t["xyz1"]), dev(DEV, t["xyz2"])
     if c["entry"] == "three_nn":
         val, idx = hf.three_nn(x2, x1)            # (unknown, known)
     else:
@@ -128,6 +117,6 @@ def test_geometry_knn(hf, oracle_mod, c):
 def test_geometry_select_top_k(hf, oracle_mod, c):
     t = gc.make_inputs(c)
     want = gc.oracle_outputs(c, t, oracle_mod)
-    outi, out = hf.select_top_k(c["k"], dev(t["dist"]))
+    outi, out = hf.select_top_k(c["k"], dev(DEV, t["dist"]))
     same(outi, want["outi"], "indices", c)
     same(out, want["out"], "distances", c)

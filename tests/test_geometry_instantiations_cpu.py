@@ -13,7 +13,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import geometry_cases as gc  # noqa: E402
-from test_gemm_instantiations_cpu import compile_to_assembly, kernel_table  # noqa: E402
+from kernel_asm import compile_to_assembly, kernel_table  # noqa: E402
 
 
 def compile_all(directory):

@@ -9,7 +9,6 @@ into a row that cls excludes show.  Integer outputs and every float output that 
 np.array_equal against the fp32 restatement (NaN for NaN); the x / z outputs of a case with a heading tensor lie within the derived
 bound of the fp64 evaluation, with equal bins on every row.  A zero heading tensor gives the bits of the call without one.  Every call
 but the atomic gradient is made twice and must give the same bits."""
-import ctypes
 import json
 import os
 import sys
@@ -20,72 +19,16 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import glue_cases as gc  # noqa: E402
-import test_bn_abi as bn_abi  # noqa: E402
-from test_bn_abi import SENTINEL, Arena, within  # noqa: E402,F401
-from test_xconv_abi import In, Out  # noqa: E402
-from test_glue_cases_cpu import check_arguments  # noqa: E402
+from abi_harness import INT_FILL, SENTINEL, Arena, Hold, IntOut, Out, abi, call, parity_report, twice, within  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-INT_FILL = -123456789
-GLUE_ENTRIES = tuple(gc.ENTRY.values())
-
-
-def _abi():
-    from heterofusionrcnn_amd import _lib
-    return _lib, _lib.lib()
-
-
-def call(status, name):
-    _lib, _ = _abi()
-    _lib.check(status, name)
-
-
-@pytest.fixture(scope="module", autouse=True)
-def parity_report():
-    """GLUE_PARITY_OUT=<file>: the worst ratios of the session as JSON (the source of profiles/glue_parity.md)"""
-    yield
-    path = os.environ.get("GLUE_PARITY_OUT")
-    if path:
-        with open(path, "w") as f:
-            json.dump({"%s|%s" % k: v for k, v in sorted(bn_abi.RATIOS.items()) if k[0].startswith(GLUE_ENTRIES)}, f, indent=1)
-
-
-class IntOut:
-    """an int32 output of n elements inside a guarded buffer of the arena, pre-filled with INT_FILL"""
-
-    def __init__(self, arena, n, passed=True):
-        self.view = arena.out((n,), dtype=torch.int32)
-        self.view.fill_(INT_FILL)
-        self.p = ctypes.c_void_p(self.view.data_ptr()) if passed and n else None
+DEV = "cuda"
+parity_report = parity_report("GLUE_PARITY_OUT", tuple(gc.ENTRY.values()))       # the source of profiles/glue_parity.md
 
 
 def host(o, shape):
     return o.view.cpu().numpy().reshape(shape)
-
-
-class Hold:
-    """places inputs on the device and keeps them alive until the caller has synchronised; None stays NULL"""
-
-    def __init__(self):
-        self.items = []
-
-    def __call__(self, a, off=False):
-        if a is None:
-            return None
-        self.items.append(In(a, off))
-        return self.items[-1].p
-
-
-def bits(a):
-    return a.view(np.uint32) if a.dtype == np.float32 else a
-
-
-def twice(run):
-    first, second = run(), run()
-    for key in first:
-        assert np.array_equal(bits(first[key]), bits(second[key])), "%s differs between two calls" % key
-    return first
 
 
 def exact(got, want, name):
@@ -105,10 +48,10 @@ def close(got, want64, bound, name, case):
 
 # ------------------------------------------------------------------------------------------------- encode
 def run_encode(c, t):
-    _lib, L = _abi()
+    _lib, L = abi()
     cst, rows, off = t["cst"], c["rows"], c["off"]
     k = cst["k"]
-    a, I = Arena(), Hold()
+    a, I = Arena(DEV), Hold(DEV)
     ins = [I(t["ref_pts"], off), I(t["ref_theta"], off), I(t["boxes"], off), I(t["mean_sizes"], off), I(cst["ss"], off), I(cst["deltas"], off),
            I(cst["hi_xz"], off)]
     outs = dict(bin_x=IntOut(a, rows * k), res_x=Out(a, rows * k, off=off), bin_z=IntOut(a, rows * k), res_z=Out(a, rows * k, off=off), bin_t=IntOut(a, rows),
@@ -124,7 +67,7 @@ def run_encode(c, t):
 def test_bin_box_encode(c):
     t = gc.encode_inputs(c)
     cst = t["cst"]
-    got = twice(lambda: run_encode(c, t))
+    got = twice(run_encode, c, t)
     enc = lambda dt, heading: gc.encode(c["rcnn"], t["ref_pts"], t["ref_theta"] if heading else None, t["boxes"], t["mean_sizes"], cst, dt)
     trig = c["heading"] == "random"
     o32, t32 = enc(np.float32, c["heading"] != "zero")          # zero heading tensor: the bits of the call without one
@@ -158,10 +101,10 @@ def check_boxes(c, got, b32, b64, t64, name):
 
 
 def run_decode(c, t):
-    _lib, L = _abi()
+    _lib, L = abi()
     cst, rows, off = t["cst"], c["rows"], c["off"]
     k = cst["k"]
-    a, I = Arena(), Hold()
+    a, I = Arena(DEV), Hold(DEV)
     ins = [I(t["ref_pts"], off), I(t["ref_theta"], off)] + [I(t[n], off and t[n].dtype == np.float32) for n in gc.DECODE_ARGS] + \
           [I(cst["ss"], off), I(cst["deltas"], off)]
     boxes = Out(a, rows * k * 7, off=off)
@@ -173,16 +116,16 @@ def run_decode(c, t):
 @pytest.mark.parametrize("c", gc.cases_of("decode"), ids=gc.case_id)
 def test_bin_box_decode(c):
     t = gc.decode_inputs(c)
-    got = twice(lambda: run_decode(c, t))["boxes"]
+    got = twice(run_decode, c, t)["boxes"]
     b32, _ = gc.decode_ref(t, heading=c["heading"] != "zero")
     b64, t64 = gc.decode_ref(t, np.float64)
     check_boxes(c, got, b32, b64, t64, "hf_bin_box_decode")
 
 
 def run_head(c, t):
-    _lib, L = _abi()
+    _lib, L = abi()
     cst, rows, k, off = t["cst"], c["rows"], c["k"], c["off"]
-    a, I = Arena(), Hold()
+    a, I = Arena(DEV), Hold(DEV)
     ins = [I(t["head"], off), I(t["ref_pts"], off), I(t["ref_theta"], off), I(t["mean_sizes_k"], off), I(cst["ss"], off), I(cst["deltas"], off)]
     boxes = Out(a, rows * 7 if c["cls"] else rows * k * 7, off=off)
     call(L.hf_bin_head_decode(rows, k, *c["bins"], *ins, float(cst["r"]), float(cst["delta_theta"]), I(t["cls"]), boxes.p, _lib.stream_ptr()), "hf_bin_head_decode")
@@ -193,7 +136,7 @@ def run_head(c, t):
 @pytest.mark.parametrize("c", gc.cases_of("head"), ids=gc.case_id)
 def test_bin_head_decode(c):
     t = gc.head_inputs(c)
-    got = twice(lambda: run_head(c, t))["boxes"]
+    got = twice(run_head, c, t)["boxes"]
     b32, _, _ = gc.head_ref(c, t, heading=c["heading"] != "zero")
     b64, t64, _ = gc.head_ref(c, t, np.float64)
     if not c["cls"]:
@@ -211,9 +154,9 @@ def test_bin_head_decode(c):
 
 # ------------------------------------------------------------------------------------------------- projection
 def run_gather(c, t):
-    _lib, L = _abi()
+    _lib, L = abi()
     b, p, h, w, ch = c["b"], c["p"], c["h"], c["w"], c["c"]
-    a, I = Arena(), Hold()
+    a, I = Arena(DEV), Hold(DEV)
     out, pix = Out(a, b * p * ch, off=c["off"] == "out"), IntOut(a, b * p * 2, passed=c["pix"])
     call(L.hf_project_gather(b, p, h, w, ch, I(t["pts"]), I(t["calib"]), I(t["img"], c["off"] == "img"), out.p, pix.p, _lib.stream_ptr()), "hf_project_gather")
     a.check()
@@ -223,7 +166,7 @@ def run_gather(c, t):
 @pytest.mark.parametrize("c", gc.cases_of("gather"), ids=gc.case_id)
 def test_project_gather(c):
     t = gc.gather_inputs(c)
-    got = twice(lambda: run_gather(c, t))
+    got = twice(run_gather, c, t)
     out, pix = gc.gather_ref(c, t)
     if c["pix"]:
         exact(got["pix"], pix, "hf_project_gather.pix")
@@ -237,10 +180,10 @@ def test_project_gather(c):
 def test_project_gather_grad(c):
     """integer-valued rows: every sum is exact in any order, so the atomic form equals the fp64 scatter bit for bit; pixels that receive
     nothing, and the whole image when p == 0, are exactly 0.0"""
-    _lib, L = _abi()
+    _lib, L = abi()
     t = gc.gather_grad_inputs(c)
     b, p, h, w, ch = c["b"], c["p"], c["h"], c["w"], c["c"]
-    a, I = Arena(), Hold()
+    a, I = Arena(DEV), Hold(DEV)
     g = Out(a, b * h * w * ch, off=c["off"])
     go, px = (I(t["grad_out"], c["off"]), I(t["pix"])) if p else (None, None)
     call(L.hf_project_gather_grad(b, p, h, w, ch, go, px, g.p, _lib.stream_ptr()), "hf_project_gather_grad")
@@ -259,9 +202,9 @@ def masks_of(c, I):
 
 
 def run_concat(c, t):
-    _lib, L = _abi()
+    _lib, L = abi()
     rows, c1, c2 = c["rows"], c["c1"], c["c2"]
-    a, I = Arena(), Hold()
+    a, I = Arena(DEV), Hold(DEV)
     m, mp = masks_of(c, I)
     out = Out(a, rows * (c1 + c2), off=c["off"] == "out")
     call(L.hf_fuse_concat(rows, c1, c2, I(t["a"], c["off"] == "a"), I(t["b"], c["off"] == "b"), mp, out.p, _lib.stream_ptr()), "hf_fuse_concat")
@@ -272,14 +215,14 @@ def run_concat(c, t):
 @pytest.mark.parametrize("c", gc.cases_of("concat"), ids=gc.case_id)
 def test_fuse_concat(c):
     t = gc.concat_inputs(c)
-    got = twice(lambda: run_concat(c, t))["out"]
+    got = twice(run_concat, c, t)["out"]
     exact(got, gc.concat(t["a"], t["b"], gc.MASKS[c["masks"]]), "hf_fuse_concat.out")
 
 
 def run_concat_grad(c, t):
-    _lib, L = _abi()
+    _lib, L = abi()
     rows, c1, c2, null = c["rows"], c["c1"], c["c2"], c["null"]
-    a, I = Arena(), Hold()
+    a, I = Arena(DEV), Hold(DEV)
     m, mp = masks_of(c, I)
     ga = Out(a, rows * c1, passed=null not in ("grad_a", "both"), off=c["off"] == "grad_a")
     gb = Out(a, rows * c2, passed=null not in ("grad_b", "both"), off=c["off"] == "grad_b")
@@ -291,7 +234,7 @@ def run_concat_grad(c, t):
 @pytest.mark.parametrize("c", gc.cases_of("concat_grad"), ids=gc.case_id)
 def test_fuse_concat_grad(c):
     t = gc.concat_inputs(c)
-    got = twice(lambda: run_concat_grad(c, t))
+    got = twice(run_concat_grad, c, t)
     want = dict(zip(("grad_a", "grad_b"), gc.concat_grad(t["grad_out"], c["c1"], gc.MASKS[c["masks"]])))
     for n in ("grad_a", "grad_b"):
         if c["null"] in (n, "both"):
@@ -299,20 +242,20 @@ def test_fuse_concat_grad(c):
         else:
             exact(got[n], want[n], "hf_fuse_concat_grad." + n)
     if c["null"] == "both":                 # nothing is read either: grad_out may be NULL
-        _lib, L = _abi()
+        _lib, L = abi()
         assert L.hf_fuse_concat_grad(c["rows"], c["c1"], c["c2"], None, None, None, None, _lib.stream_ptr()) == _lib.HF_OK
 
 
 # ------------------------------------------------------------------------------------------------- argument checks
 def test_argument_matrix_on_the_device():
-    check_arguments()
+    gc.check_arguments()
     torch.cuda.synchronize()
 
 
 def test_a_refused_gradient_leaves_grad_img_alone():
     """a NULL grad_out or pix with points to scatter is refused before the zero-fill"""
-    _lib, L = _abi()
-    a, I = Arena(), Hold()
+    _lib, L = abi()
+    a, I = Arena(DEV), Hold(DEV)
     g = Out(a, 2 * 3 * 5 * 4, fill=SENTINEL)
     go, px = I(np.ones((2, 7, 4), np.float32)), I(np.zeros((2, 7, 2), np.int32))
     assert L.hf_project_gather_grad(2, 7, 3, 5, 4, None, px, g.p, _lib.stream_ptr()) == _lib.HF_EINVAL

@@ -2,7 +2,6 @@
 the restated launch rule, the branch accounting of the encode families, the fp32 restatements against their fp64 evaluation and against
 the CPU oracle, the host's own fp32 trigonometry inside the derived bound, the redraw of undecided rows, and the argument checks of the
 seven entry points before any launch (those of hf_project_gather_grad_ordered are in tests/test_ordered_grad_cases_cpu.py)."""
-import ctypes
 import os
 import re
 import sys
@@ -332,73 +331,5 @@ def test_concat_reference():
 
 
 # ------------------------------------------------------------------------------------------------- argument checks, no launch
-def check_arguments():
-    """every call returns before anything is launched (fake non-null pointers, never dereferenced); tests/test_glue_abi.py runs this on
-    the GPU too"""
-    from heterofusionrcnn_amd import _lib
-    L = _lib.lib()
-    fake = ctypes.c_void_p(256)
-    E, OK = _lib.HF_EINVAL, _lib.HF_OK
-    bad = {}
-
-    def ptrs(n, null):
-        return [None if i == null else fake for i in range(n)]
-
-    def gather(b=1, p=4, h=3, w=5, c=4, null=None, pix=fake):
-        return L.hf_project_gather(b, p, h, w, c, *ptrs(4, null), pix, None)           # pts calib img out
-
-    def grad(b=1, p=4, h=3, w=5, c=4, null=None):
-        return L.hf_project_gather_grad(b, p, h, w, c, *ptrs(3, null), None)           # grad_out pix grad_img
-
-    def concat(rows=4, c1=4, c2=4, null=None):
-        a, b, out = ptrs(3, null)
-        return L.hf_fuse_concat(rows, c1, c2, a, b, None, out, None)
-
-    def cgrad(rows=4, c1=4, c2=4, g=fake, ga=fake, gb=fake):
-        return L.hf_fuse_concat_grad(rows, c1, c2, g, None, ga, gb, None)
-
-    def decode(rows=4, k=3, null=None):
-        p = ptrs(14, null)                  # ref_pts ref_theta(1) 9 per-class arrays ss deltas | boxes
-        return L.hf_bin_box_decode(rows, k, *p[:13], 0.5, 0.25, p[13], None)
-
-    def encode(rows=4, k=3, null=None):
-        p = ptrs(15, null)                  # ref_pts ref_theta(1) boxes mean_sizes ss deltas hi_xz | 8 outputs
-        return L.hf_bin_box_encode(rows, k, 0, *p[:7], 0.5, 0.999, 0.25, 0.125, *p[7:], None)
-
-    def head(rows=4, k=3, nbx=2, nbz=2, nbt=2, null=None, cls=None):
-        p = ptrs(7, null)                   # head ref_pts ref_theta(2) mean_sizes_k ss deltas | boxes
-        return L.hf_bin_head_decode(rows, k, nbx, nbz, nbt, *p[:6], 0.5, 0.25, cls, p[6], None)
-
-    for name, f in (("gather", gather), ("grad", grad)):
-        bad.update({"%s: %s" % (name, k): f(**v) for k, v in (("b < 0", dict(b=-1)), ("p < 0", dict(p=-1)), ("h = 0", dict(h=0)), ("w = 0", dict(w=0)),
-                                                               ("c = 0", dict(c=0)), ("h < 0", dict(h=-2)))})
-    bad.update({"gather: pointer %d is NULL" % i: gather(null=i) for i in range(4)})
-    bad.update({"grad: pointer %d is NULL" % i: grad(null=i) for i in range(3)})
-    bad["grad: no grad_img for an empty point set"] = grad(p=0, null=2)
-    for name, f in (("concat", concat), ("cgrad", cgrad)):
-        bad.update({"%s: rows < 0" % name: f(rows=-1), "%s: c1 = 0" % name: f(c1=0), "%s: c2 = 0" % name: f(c2=0), "%s: c1 < 0" % name: f(c1=-4)})
-    bad.update({"concat: pointer %d is NULL" % i: concat(null=i) for i in range(3)})
-    bad["cgrad: no grad_out"] = cgrad(g=None)
-    for name, f, n, optional in (("decode", decode, 14, (1,)), ("encode", encode, 15, (1,)), ("head", head, 7, (2,))):
-        bad.update({"%s: rows < 0" % name: f(rows=-1), "%s: k = 0" % name: f(k=0), "%s: k < 0" % name: f(k=-1)})
-        bad.update({"%s: pointer %d is NULL" % (name, i): f(null=i) for i in range(n) if i not in optional})
-    bad.update({"head: nbx = 0": head(nbx=0), "head: nbz = 0": head(nbz=0), "head: nbt = 0": head(nbt=0), "head: nbx < 0": head(nbx=-3)})
-    wrong = {k: v for k, v in bad.items() if v != E}
-    assert not wrong, wrong
-    # nothing to do: HF_OK with null pointers, nothing launched
-    none = [None] * 15
-    ok = {"gather: p = 0": L.hf_project_gather(2, 0, 3, 5, 4, None, None, None, None, None, None),
-          "gather: b = 0": L.hf_project_gather(0, 7, 3, 5, 4, None, None, None, None, None, None),
-          "grad: b = 0": L.hf_project_gather_grad(0, 7, 3, 5, 4, None, None, None, None),
-          "concat: rows = 0": L.hf_fuse_concat(0, 4, 4, None, None, None, None, None),
-          "cgrad: rows = 0": L.hf_fuse_concat_grad(0, 4, 4, None, None, None, None, None),
-          "cgrad: both gradients NULL": cgrad(ga=None, gb=None), "cgrad: both NULL and no grad_out": cgrad(g=None, ga=None, gb=None),
-          "decode: rows = 0": L.hf_bin_box_decode(0, 3, *none[:13], 0.5, 0.25, None, None),
-          "encode: rows = 0": L.hf_bin_box_encode(0, 3, 1, *none[:7], 0.5, 0.999, 0.25, 0.125, *none[:8], None),
-          "head: rows = 0": L.hf_bin_head_decode(0, 3, 2, 2, 2, *none[:6], 0.5, 0.25, None, None, None)}
-    wrong = {k: v for k, v in ok.items() if v != OK}
-    assert not wrong, wrong
-
-
 def test_argument_matrix_before_any_launch():
-    check_arguments()
+    gc.check_arguments()

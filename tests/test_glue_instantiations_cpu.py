@@ -11,7 +11,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import glue_cases as gc  # noqa: E402
-from test_gemm_instantiations_cpu import compile_to_assembly  # noqa: E402
+from kernel_asm import compile_to_assembly  # noqa: E402
 
 LOSS_KERNELS = {"rpn_loss_kernel", "rpn_loss_finalize_kernel", "rcnn_loss_kernel", "rcnn_loss_finalize_kernel"}
 

@@ -15,69 +15,14 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import gemm_cases as gc  # noqa: E402
+from abi_harness import Arena, abi, place, same, within  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
-SENTINEL = 12345.0
-GUARD = 64          # floats either side of an output: 256 bytes, keeps the slice's 16-byte alignment
 EPS, MOMENTUM = 1e-3, 0.1
 TWO24 = float(2 ** 24)
 DYADIC = torch.tensor([[1, 0, 0], [0, 0, 1], [.5, .25, .25], [.25, .5, .25], [.25, .25, .5]])
-
-
-def _abi():
-    from heterofusionrcnn_amd import _lib
-    return _lib, _lib.lib()
-
-
-class Arena:
-    """outputs as slices of sentinel-filled buffers: the floats before and after an output must be unchanged after the call"""
-
-    def __init__(self):
-        self.slots = []
-
-    def out(self, shape, init=None):
-        n = int(np.prod(shape))
-        buf = torch.full((GUARD + n + GUARD,), SENTINEL, device=DEV)
-        view = buf[GUARD:GUARD + n].view(shape)
-        if init is not None:
-            view.copy_(init)
-        self.slots.append((buf, n))
-        return view
-
-    def check(self):
-        torch.cuda.synchronize()
-        for buf, n in self.slots:
-            assert bool((buf[:GUARD] == SENTINEL).all()) and bool((buf[GUARD + n:] == SENTINEL).all()), "write outside an output"
-
-
-def place(t, off=False):
-    """the tensor on the device, at a 16-byte boundary or (off) one float past one"""
-    if t is None:
-        return None
-    buf = torch.empty(t.numel() + 8, dtype=t.dtype, device=DEV)
-    view = buf[(1 if off else 0):(1 if off else 0) + t.numel()].view(t.shape)
-    view.copy_(t)
-    assert view.data_ptr() % 16 == (4 if off else 0)
-    return view
-
-
-def same(got, want64, name):
-    want = want64.float()
-    if not torch.equal(got, want):
-        bad = (got != want) | torch.isnan(got)
-        idx = bad.nonzero()[0].tolist()
-        raise AssertionError("%s: %d of %d elements differ from the fp64 reference, first at %s: %r != %r" % (
-            name, int(bad.sum()), got.numel(), idx, float(got[tuple(idx)]), float(want[tuple(idx)])))
-
-
-def within(got, want64, bound, name):
-    diff = (got.double() - want64).abs()
-    ratio = float((diff / bound.clamp(min=1e-300)).max())
-    print("%s: max |got - ref64| / bound = %.3g" % (name, ratio))
-    ok = diff <= bound          # a NaN fails
-    assert bool(ok.all()), "%s: %d of %d elements outside the bound, worst ratio %.3g" % (name, int((~ok).sum()), got.numel(), ratio)
 
 
 # ------------------------------------------------------------------------------------------------- 1. exact family, C ABI
@@ -112,16 +57,16 @@ def operand64(t, rows_per_cloud, cin):
 
 
 def run_fwd(t, rows_per_cloud, m, c2, c1, cout, mis=None, running=True):
-    _lib, L = _abi()
+    _lib, L = abi()
     ptr = _lib.ptr
     rows = t["idx"].shape[0]
-    a = Arena()
+    a = Arena(DEV)
     z, mean, invstd = a.out((rows, cout)), a.out((cout,)), a.out((cout,))
     rm, rv = (a.out((cout,), init=t["rm"]), a.out((cout,), init=t["rv"])) if running else (None, None)
     nbytes = L.hf_linear_bn_fwd_workspace(cout)
     ws = a.out((nbytes // 4,))          # exactly the bytes the library asks for, guarded like an output
-    p2, skip, w = place(t["points2"], mis == "points2"), place(t["skip"], mis == "skip"), place(t["w"], mis == "weight")
-    idx, w3, bias = place(t["idx"]), place(t["w3"]), place(t["bias"])
+    p2, skip, w = place(DEV, t["points2"], mis == "points2"), place(DEV, t["skip"], mis == "skip"), place(DEV, t["w"], mis == "weight")
+    idx, w3, bias = place(DEV, t["idx"]), place(DEV, t["w3"]), place(DEV, t["bias"])
     _lib.check(L.hf_linear_bn_fwd_interp(rows, c2, c1, cout, ptr(p2), m, rows_per_cloud, ptr(idx), ptr(w3), ptr(skip), ptr(w), ptr(bias), ptr(z), EPS,
                                          MOMENTUM, ptr(rm), ptr(rv), ptr(mean), ptr(invstd), ptr(ws), nbytes, _lib.stream_ptr()),
                "hf_linear_bn_fwd_interp")
@@ -130,15 +75,15 @@ def run_fwd(t, rows_per_cloud, m, c2, c1, cout, mis=None, running=True):
 
 
 def run_wgrad(t, rows_per_cloud, m, c2, c1, cout, mis=None):
-    _lib, L = _abi()
+    _lib, L = abi()
     ptr = _lib.ptr
     rows, cin = t["idx"].shape[0], (c2 + c1 + 3) // 4 * 4
-    a = Arena()
+    a = Arena(DEV)
     dw = a.out((cout, cin))
     nbytes = L.hf_linear_wgrad_workspace(rows, cout, cin)
     ws = a.out((nbytes // 4,))
-    gz, p2, skip = place(t["gz"], mis == "grad_z"), place(t["points2"], mis == "points2"), place(t["skip"], mis == "skip")
-    idx, w3 = place(t["idx"]), place(t["w3"])
+    gz, p2, skip = place(DEV, t["gz"], mis == "grad_z"), place(DEV, t["points2"], mis == "points2"), place(DEV, t["skip"], mis == "skip")
+    idx, w3 = place(DEV, t["idx"]), place(DEV, t["w3"])
     _lib.check(L.hf_linear_wgrad_interp(rows, cout, c2, c1, ptr(gz), ptr(p2), m, rows_per_cloud, ptr(idx), ptr(w3), ptr(skip), ptr(dw), ptr(ws),
                                         nbytes, _lib.stream_ptr()), "hf_linear_wgrad_interp")
     a.check()
@@ -231,7 +176,7 @@ def test_interp_fwd_same_bits_as_materialised_operand(c2, c1, cout, n):
     """c2 % 4 == 0, N(0,1) data: hf_linear_bn_fwd on the rows hf_three_interpolate_concat writes, same weight.  The new kernel keeps
     the ascending-k accumulation of linear_fwd_kernel, builds the operand with the concat kernel's expression and runs on the
     same grid, so z and the statistics are EQUAL, not merely within the 2e-5 x scale that two fp32 routes are allowed"""
-    _lib, L = _abi()
+    _lib, L = abi()
     ptr, sp = _lib.ptr, _lib.stream_ptr()
     b, m = 2, 50
     g = torch.Generator().manual_seed(c2 + c1)

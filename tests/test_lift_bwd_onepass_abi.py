@@ -1,5 +1,5 @@
 """hf_onepass_lift_elu_bn_bwd (csrc/lift_bwd.hip) through the C ABI: the lifting chain's backward with dy0 = dz1 W1 formed once.
-Inputs are the lifting cases' own (tests/test_gemm_abi.lift_inputs, seeded by gemm_cases), the reference is fp64 autograd
+Inputs are the lifting cases' own (tests/gemm_runs.lift_inputs, seeded by gemm_cases), the reference is fp64 autograd
 (gemm_cases.ref_lift_bwd_autograd) and the bounds are gemm_cases.lift_bwd_bounds with this kernel's chain lengths: the grid, the
 tile walk and col_sums_store are those of lift_linear_bwd_kernel, so a lane adds 16 rows per tile and tile of its workgroup, then the
 other row-half and the four waves: 16 * tiles_per_workgroup + 4.
@@ -30,48 +30,23 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import gemm_cases as gc  # noqa: E402
-import test_gemm_abi as ga  # noqa: E402
+from abi_harness import SENTINEL, Arena, abi, call, place, within  # noqa: E402
+from gemm_runs import UNSET, lift_inputs, run_lift_bwd  # noqa: E402
+from lift_bwd_cases import CASES, MAX_C0, TWINS, instantiations  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-DEV, EPS = ga.DEV, ga.EPS
-MAX_C0 = 128                                   # the entry's limit: NT = ceil(c0 / 32) <= 4 compiles without spills
-C0S = (4, 36, 64, 96, 128)                     # 4, 36: partial 32-column groups; 128 = MAX_C0, the largest the entry accepts
-C1S = (33, 64, 100, 256)                       # 33: scalar loads
-SMALL_ROWS = (1, 129, 300)                     # one row; one full tile plus one row; a ragged third tile
-
-
-def _shapes():
-    out = [(r, c0, c1) for r in SMALL_ROWS + (40000,) for c0 in C0S for c1 in C1S]
-    out += [(gc.multi_tile_rows(gc.cdiv(c0, 32)), c0, c1) for c0 in C0S for c1 in C1S]
-    return out
-
-
-CASES = [gc._case("lift_bwd", rows=r, c0=c0, c1=c1, family="round") for r, c0, c1 in _shapes()]
-TWINS = [gc._case("lift_bwd", rows=300, c0=36, c1=100, family="exact", misalign=m) for m in ("dz1", "w1_t")]
-
-
-def instantiations(c):
-    """(kernel, template arguments) of lift_bwd.hip that a case launches: NT = ceil(c0 / 32), VEC = c1 % 4 == 0 and dz1, w1_t aligned"""
-    vec = c["c1"] % 4 == 0 and c["misalign"] not in ("dz1", "w1_t")
-    return {("lift_bwd_onepass_kernel", (gc.cdiv(c["c0"], 32), vec)), ("lift_bwd_onepass_finalize_kernel", ())}
-
-
-def selected_instantiations():
-    out = set()
-    for c in CASES + TWINS:
-        out |= instantiations(c)
-    return out
+DEV, EPS = "cuda", 1e-3
 
 
 def run_onepass(c, t, stats, short_by=0):
-    _lib, L = ga._abi()
+    _lib, L = abi(UNSET)
     ptr, sp = _lib.ptr, _lib.stream_ptr()
     rows, c0, c1, mis = c["rows"], c["c0"], c["c1"], c["misalign"]
-    a = ga.Arena()
-    x3, w0, g0, b0 = ga.place(t["x3"]), ga.place(t["w0"]), ga.place(t["bn0"][0]), ga.place(t["bn0"][1])
-    mean0, invstd0 = ga.place(stats[0]), ga.place(stats[1])
-    dz1, w1t = ga.place(t["dz1"], mis == "dz1"), ga.place(t["w1"].t().contiguous(), mis == "w1_t")
+    a = Arena(DEV)
+    x3, w0, g0, b0 = place(DEV, t["x3"]), place(DEV, t["w0"]), place(DEV, t["bn0"][0]), place(DEV, t["bn0"][1])
+    mean0, invstd0 = place(DEV, stats[0]), place(DEV, stats[1])
+    dz1, w1t = place(DEV, t["dz1"], mis == "dz1"), place(DEV, t["w1"].t().contiguous(), mis == "w1_t")
     gw0t, gw1, dg0, db0 = a.out((3, c0)), a.out((c1, c0)), a.out((c0,)), a.out((c0,))
     nbytes = L.hf_onepass_lift_elu_bn_bwd_workspace(rows, c0, c1)
     ws = a.out((nbytes // 4,))
@@ -81,18 +56,18 @@ def run_onepass(c, t, stats, short_by=0):
     out = dict(grad_w0_t=gw0t, grad_w1=gw1, dgamma0=dg0, dbeta0=db0)
     if short_by:
         return status, out
-    ga.call(status, "hf_onepass_lift_elu_bn_bwd")
+    call(status, "hf_onepass_lift_elu_bn_bwd")
     return out
 
 
 def measure(c):
     """-> (outputs of the one-pass entry, outputs of the two-pass entry, {output: (|got - ref64|, bound)})"""
-    t = ga.lift_inputs(c)
+    t = lift_inputs(c)
     dv = lambda v: v.to(DEV)
     rows, c0, c1 = c["rows"], c["c0"], c["c1"]
     gw1, gg0, gb0, gw0, mean, invstd = gc.ref_lift_bwd_autograd(dv(t["x3"]), dv(t["w0"]), dv(t["bn0"][0]), dv(t["bn0"][1]), dv(t["w1"]), dv(t["dz1"]), EPS)
     stats = (mean.float(), invstd.float())
-    got, old = run_onepass(c, t, stats), ga.run_lift_bwd(c, t, stats)
+    got, old = run_onepass(c, t, stats), run_lift_bwd(c, t, stats)
     _, _, rpc, chunks = gc.wgrad_plan(rows, c1, c0)
     b = gc.lift_bwd_bounds(dv(t["x3"]), dv(t["w0"]), [dv(t["bn0"][0]), dv(t["bn0"][1]), mean, invstd], dv(t["w1"]), dv(t["dz1"]),
                            16 * gc.tiles_per_workgroup(rows, gc.cdiv(c0, 32)) + 4, min(rows, rpc) + gc.cdiv(chunks, 16) + 15)
@@ -104,13 +79,13 @@ def measure(c):
 def test_onepass_against_fp64_autograd_and_the_two_pass_entry(c):
     got, old, ref = measure(c)
     for name in ("grad_w1", "dbeta0", "dgamma0", "grad_w0_t"):
-        ga.within(got[name], ref[name][0], ref[name][1], name)
+        within(got[name], ref[name][0], ref[name][1], name)
     for name in ("grad_w1", "dgamma0", "dbeta0"):
         assert torch.equal(got[name], old[name]), "%s differs from hf_lift_elu_bn_bwd" % name
 
 
 def _run(c):
-    t = ga.lift_inputs(c)
+    t = lift_inputs(c)
     return run_onepass(c, t, (t["bn0"][2], t["bn0"][3]))
 
 
@@ -131,14 +106,14 @@ def test_two_calls_give_the_same_bits():
 
 
 def test_limits_and_a_short_workspace_are_rejected_before_anything_is_launched():
-    _lib, L = ga._abi()
+    _lib, L = abi(UNSET)
     sp = _lib.stream_ptr()
     buf = torch.zeros(16 * 16384, device=DEV)
     buf[8 * 16384:9 * 16384] = 1.0
     q = lambda i: _lib.ptr(buf[i * 16384:])
-    poison = torch.full((4, 16384), ga.SENTINEL, device=DEV)                  # grad_w0_t, grad_w1, dgamma0, dbeta0
+    poison = torch.full((4, 16384), SENTINEL, device=DEV)                  # grad_w0_t, grad_w1, dgamma0, dbeta0
     o = lambda i: _lib.ptr(poison[i])
-    wsb = torch.full((1 << 22,), ga.SENTINEL, device=DEV)
+    wsb = torch.full((1 << 22,), SENTINEL, device=DEV)
     ws, n = _lib.ptr(wsb), wsb.numel() * 4
     rows = 8
     f = lambda c0, c1=32, x=q(0), ws=ws, n=n: L.hf_onepass_lift_elu_bn_bwd(rows, c0, c1, x, q(9), q(8), q(5), q(5), q(8), q(10), q(1), o(0), o(1), o(2),
@@ -148,14 +123,14 @@ def test_limits_and_a_short_workspace_are_rejected_before_anything_is_launched()
     got = [f(6), f(MAX_C0 + 4), f(0), f(36, 257), f(36, 0), f(36, x=None), f(36, ws=None), f(36, n=need - 1)]
     assert got == [_lib.HF_EINVAL] * 6 + [_lib.HF_EWORKSPACE] * 2
     torch.cuda.synchronize()
-    assert bool((poison == ga.SENTINEL).all()) and bool((wsb == ga.SENTINEL).all()), "a rejected call wrote something"
+    assert bool((poison == SENTINEL).all()) and bool((wsb == SENTINEL).all()), "a rejected call wrote something"
     assert f(MAX_C0) == 0 and f(36, n=need) == 0                              # the limit itself and the exact workspace are accepted
     torch.cuda.synchronize()
     c = gc._case("lift_bwd", rows=300, c0=36, c1=100, family="round")
-    t = ga.lift_inputs(c)
+    t = lift_inputs(c)
     status, out = run_onepass(c, t, (t["bn0"][2], t["bn0"][3]), short_by=1)
     assert status == _lib.HF_EWORKSPACE
-    assert all(bool((v == ga.SENTINEL).all()) for v in out.values())
+    assert all(bool((v == SENTINEL).all()) for v in out.values())
 
 
 def render():

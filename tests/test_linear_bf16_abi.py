@@ -11,34 +11,29 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import linear_bf16_cases as lc  # noqa: E402
-from test_gemm_abi import Arena, place, same, within  # noqa: E402
+from abi_harness import Arena, abi, place, same, within  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
 
 
-def _abi():
-    from heterofusionrcnn_amd import _lib
-    return _lib, _lib.lib()
-
-
 def to_bf16_device(t):
     """a host fp32 tensor -> device bf16 bits (int16 storage) by hf_f32_to_bf16"""
-    _lib, L = _abi()
-    src = place(t)
+    _lib, L = abi()
+    src = place(DEV, t)
     dst = torch.empty(t.numel() + 8, dtype=torch.int16, device=DEV)[:t.numel()].view(t.shape)
     _lib.check(L.hf_f32_to_bf16(t.numel(), _lib.ptr(src), _lib.ptr(dst), _lib.stream_ptr()), "hf_f32_to_bf16")
     return dst
 
 
 def run(c, t):
-    _lib, L = _abi()
+    _lib, L = abi()
     ptr = _lib.ptr
     has_bn, mode, _ = lc.MODES[c["mode"]]
-    a = Arena()
-    x, wb, bias = place(t["x"]), to_bf16_device(t["w"]), place(t["bias"])
-    bn = [place(v) for v in t["bn"]] if has_bn else [None] * 4
+    a = Arena(DEV)
+    x, wb, bias = place(DEV, t["x"]), to_bf16_device(t["w"]), place(DEV, t["bias"])
+    bn = [place(DEV, v) for v in t["bn"]] if has_bn else [None] * 4
     y = a.out((c["rows"], c["cout"]))
     _lib.check(L.hf_linear_bf16_fwd_eval(c["rows"], c["cin"], c["cout"], ptr(x), ptr(wb), ptr(bias), ptr(bn[0]), ptr(bn[1]), ptr(bn[2]), ptr(bn[3]),
                                          mode, ptr(y), _lib.stream_ptr()), "hf_linear_bf16_fwd_eval")
@@ -79,12 +74,12 @@ def _bits(t):
 def test_conversion_known_answers(offset):
     """hf_f32_to_bf16 bit for bit against torch's CPU conversion: the vector body, the scalar tail (the count is no multiple of four)
     and, with the destination one element past an 8-byte boundary, the scalar form alone"""
-    _lib, L = _abi()
+    _lib, L = abi()
     vals = lc.conversion_values()
     assert vals.numel() % 4 != 0
     want = _bits(vals.to(torch.bfloat16))
     assert int(want[0]) == 0x3F81 and int(want[1]) == 0x3F80 and int(want[2]) == 0x3F82      # up, tie to even down, tie to even up
-    src = place(vals)
+    src = place(DEV, vals)
     buf = torch.full((vals.numel() + 16,), 0x5555, dtype=torch.int16, device=DEV)
     dst = buf[8 + offset:8 + offset + vals.numel()]
     _lib.check(L.hf_f32_to_bf16(vals.numel(), _lib.ptr(src), _lib.ptr(dst), _lib.stream_ptr()), "hf_f32_to_bf16")
@@ -96,16 +91,16 @@ def test_conversion_known_answers(offset):
 def test_conversion_inside_the_gemm():
     """the same values through the staging conversion: x = [v, 0, 0, 0], every weight row = [1, 0, 0, 0] -> y[r, :] = bf16(v) (the
     other products are 0 * 0; -0 + 0 = +0 compares equal to -0)"""
-    _lib, L = _abi()
+    _lib, L = abi()
     vals = lc.conversion_values()
     rows = vals.numel()
     x = torch.zeros(rows, 4)
     x[:, 0] = vals
     w = torch.zeros(4, 4)
     w[:, 0] = 1.0
-    a = Arena()
+    a = Arena(DEV)
     y = a.out((rows, 4))
-    xd, wb = place(x), to_bf16_device(w)         # held until the call has run
+    xd, wb = place(DEV, x), to_bf16_device(w)         # held until the call has run
     _lib.check(L.hf_linear_bf16_fwd_eval(rows, 4, 4, _lib.ptr(xd), _lib.ptr(wb), None, None, None, None, None, 0, _lib.ptr(y),
                                          _lib.stream_ptr()), "hf_linear_bf16_fwd_eval")
     a.check()
@@ -114,7 +109,7 @@ def test_conversion_inside_the_gemm():
 
 
 def test_bad_arguments_are_rejected_on_the_device_too():
-    _lib, L = _abi()
+    _lib, L = abi()
     buf, out = torch.zeros(4096, device=DEV), torch.zeros(4096, device=DEV)
     p, off, q = _lib.ptr(buf), _lib.ptr(buf[1:]), _lib.ptr(out)
     call = lambda rows, cin, cout, x=p, w=p, y=q, bn=(None,) * 4, mode=0: L.hf_linear_bf16_fwd_eval(rows, cin, cout, x, w, None, *bn, mode, y,

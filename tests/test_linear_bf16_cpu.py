@@ -9,7 +9,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import linear_bf16_cases as lc  # noqa: E402
-from test_gemm_instantiations_cpu import LDS_PER_CU, compile_to_assembly, kernel_table  # noqa: E402
+from kernel_asm import LDS_PER_CU, compile_to_assembly, kernel_table  # noqa: E402
 
 # workgroups per CU each instantiation is meant to run with: the 256-thread forms two (amdgpu_waves_per_eu(2)), the 512-thread
 # form occupies two waves per SIMD by itself; the LDS must leave room for one more of each, so that a second workgroup can be staged

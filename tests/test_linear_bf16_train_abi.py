@@ -11,24 +11,19 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import linear_bf16_train_cases as tc  # noqa: E402
-from test_gemm_abi import Arena, place, same, within  # noqa: E402
+from abi_harness import Arena, abi, place, same, within  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
 
 
-def _abi():
-    from heterofusionrcnn_amd import _lib
-    return _lib, _lib.lib()
-
-
 def run_wgrad(c, t):
     """-> dW; the workspace is a slice of a sentinel-filled buffer as well, of exactly the size the query names"""
-    _lib, L = _abi()
+    _lib, L = abi()
     ptr = _lib.ptr
-    a = Arena()
-    g, x = place(t["g"]), place(t["x"])
+    a = Arena(DEV)
+    g, x = place(DEV, t["g"]), place(DEV, t["x"])
     nbytes = L.hf_linear_bf16_wgrad_workspace(c["rows"], c["cout"], c["cin"])
     tiles, rpc, chunks = tc.plan(c["rows"], c["cout"], c["cin"])
     assert nbytes == 4 * chunks * c["cout"] * c["cin"], "the plan restated in linear_bf16_train_cases.py is not the library's"
@@ -69,9 +64,9 @@ def test_two_calls_give_the_same_bits(c):
 
 def run_transpose(src):
     """-> dst (cols, rows) int16 bits, a slice of a buffer filled with 0x5555 whose two sides are checked"""
-    _lib, L = _abi()
+    _lib, L = abi()
     rows, cols = src.shape
-    s = place(src)
+    s = place(DEV, src)
     buf = torch.full((rows * cols + 16,), 0x5555, dtype=torch.int16, device=DEV)
     dst = buf[8:8 + rows * cols]
     _lib.check(L.hf_f32_to_bf16_transpose(rows, cols, _lib.ptr(s), _lib.ptr(dst), _lib.stream_ptr()), "hf_f32_to_bf16_transpose")
@@ -98,14 +93,14 @@ def test_transposing_conversion_known_answers():
 def test_input_gradient_as_a_composition_equals_fp64(shape):
     """dx (rows, cin) = g W: W (cout, cin) -> Wt_bf16 (cin, cout) by the transposing conversion, then the forward tile machine with the
     roles of cin and cout swapped; small integers, so the result equals fp64 bit for bit"""
-    _lib, L = _abi()
+    _lib, L = abi()
     ptr = _lib.ptr
     rows, cout, cin = shape
     t = tc.dx_inputs(rows, cout, cin)
     wt = run_transpose(t["w"])                       # (cin, cout), 16-byte aligned: eight int16 into the buffer
     assert wt.data_ptr() % 16 == 0
-    a = Arena()
-    g = place(t["g"])
+    a = Arena(DEV)
+    g = place(DEV, t["g"])
     dx = a.out((rows, cin))
     _lib.check(L.hf_linear_bf16_fwd_eval(rows, cout, cin, ptr(g), ptr(wt), None, None, None, None, None, 0, ptr(dx), _lib.stream_ptr()),
                "hf_linear_bf16_fwd_eval")
@@ -114,7 +109,7 @@ def test_input_gradient_as_a_composition_equals_fp64(shape):
 
 
 def test_bad_arguments_are_rejected_on_the_device_too():
-    _lib, L = _abi()
+    _lib, L = abi()
     E = _lib.HF_EINVAL
     buf, out, ws = torch.zeros(4096, device=DEV), torch.zeros(4096, device=DEV), torch.zeros(4096, device=DEV)
     p, q, w = _lib.ptr(buf), _lib.ptr(out), _lib.ptr(ws)

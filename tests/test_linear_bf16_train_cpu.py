@@ -9,7 +9,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import linear_bf16_train_cases as tc  # noqa: E402
-from test_gemm_instantiations_cpu import LDS_PER_CU, compile_to_assembly, kernel_table  # noqa: E402
+from kernel_asm import LDS_PER_CU, compile_to_assembly, kernel_table  # noqa: E402
 
 # workgroups per CU each instantiation is meant to run with under amdgpu_waves_per_eu(2): the 256-thread form (one wave per SIMD) two,
 # the 512-thread form (two waves per SIMD) one

@@ -7,7 +7,6 @@ are slices of sentinel-filled buffers, pre-filled with NaN and checked after the
 shows, and so does a missing zero-fill (every grad_head element that no formula reaches, every logit-gradient row that is ignored or
 unmasked, must be exactly 0.0).  The forward workspace is exactly hf_*_loss_workspace() bytes of NaN inside guards.  The backward reads
 the out5 / out6 that the forward call wrote on the device.  Every case is called twice and must give the same bits (no atomics)."""
-import ctypes
 import json
 import os
 import sys
@@ -18,33 +17,13 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import loss_cases as lc  # noqa: E402
-import test_bn_abi as bn_abi  # noqa: E402
-from test_bn_abi import GUARD, SENTINEL, Arena, within  # noqa: E402,F401
-from test_xconv_abi import NAN, In, Out  # noqa: E402
+from abi_harness import SENTINEL, Arena, In, Out, abi, call, parity_report, same_bits, within  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
+DEV = "cuda"
+parity_report = parity_report("LOSS_PARITY_OUT", ("hf_rpn_loss", "hf_rcnn_loss"))       # the source of profiles/loss_parity.md
 ENTRY = {"rpn": ("hf_rpn_loss_fwd", "hf_rpn_loss_bwd"), "rcnn": ("hf_rcnn_loss_fwd", "hf_rcnn_loss_bwd")}
-
-
-def _abi():
-    from heterofusionrcnn_amd import _lib
-    return _lib, _lib.lib()
-
-
-def call(status, name):
-    _lib, _ = _abi()
-    _lib.check(status, name)
-
-
-@pytest.fixture(scope="module", autouse=True)
-def parity_report():
-    """LOSS_PARITY_OUT=<file>: the worst ratios of the session as JSON (the source of profiles/loss_parity.md)"""
-    yield
-    path = os.environ.get("LOSS_PARITY_OUT")
-    if path:
-        with open(path, "w") as f:
-            json.dump({"%s|%s" % k: v for k, v in sorted(bn_abi.RATIOS.items()) if k[0].startswith(("hf_rpn_loss", "hf_rcnn_loss"))}, f, indent=1)
 
 
 def scalars(c):
@@ -55,21 +34,21 @@ def scalars(c):
 def run_case(c, t):
     """forward, then backward on the out5 / out6 that the forward left on the device -> host copies of out, the logit gradient and
     grad_head (rows == 0: the two gradient buffers, eight sentinels each, as the backward left them)"""
-    _lib, L = _abi()
+    _lib, L = abi()
     sp = _lib.stream_ptr()
     kind, rows, k, nbx, nbt, off = c["kind"], c["rows"], c["k"], c["nbx"], c["nbt"], c["off"]
     k1, d = k + 1, lc.head_width(nbx, nbt)
     fwd, bwd = ENTRY[kind]
     names = lc.RPN_ARGS if kind == "rpn" else lc.RCNN_ARGS
-    a = Arena()
-    args = [In(t[n], off and t[n].dtype == np.float32) for n in names]
+    a = Arena(DEV)
+    args = [In(DEV, t[n], off and t[n].dtype == np.float32) for n in names]
     ptrs = [x.p for x in args]
     out = Out(a, len(lc.OUT_NAMES[kind]), off=off)
     nbytes = getattr(L, "hf_%s_loss_workspace" % kind)()
     assert nbytes == (lc.rpn_workspace() if kind == "rpn" else lc.rcnn_workspace())
     ws = Out(a, nbytes // 4)
     call(getattr(L, fwd)(rows, k, nbx, nbt, *ptrs, *scalars(c), out.p, ws.p, nbytes, sp), fwd)
-    up = In(np.array([c["upstream"]], np.float32), off)
+    up = In(DEV, np.array([c["upstream"]], np.float32), off)
     if rows:
         g_logits, g_head = Out(a, rows * k1, off=off), Out(a, rows * k * d, off=off)
     else:
@@ -80,10 +59,6 @@ def run_case(c, t):
     if rows == 0:
         return dict(out=host(out, -1), grad_logits=host(g_logits, -1), grad_head=host(g_head, -1))
     return dict(out=host(out, -1), grad_logits=host(g_logits, (rows, k1)), grad_head=host(g_head, (rows, k, d)))
-
-
-def same_bits(x, y):
-    return x.shape == y.shape and np.array_equal(x.view(np.uint32), y.view(np.uint32))
 
 
 def close(got, want, bound, name):
@@ -134,17 +109,17 @@ def test_rcnn_loss(c):
 def test_rejected_calls_write_nothing():
     """the argument checks of tests/test_abi.py (which need no GPU) with real buffers: a short workspace and a count past the register
     arrays return before anything is launched, out5 / out6 and both gradients keep their sentinels"""
-    _lib, L = _abi()
+    _lib, L = abi()
     sp = _lib.stream_ptr()
     for kind in ("rpn", "rcnn"):
         c = next(c for c in lc.cases_of(kind) if c["rows"] == 257 and not c["off"])
         t = lc.make_inputs(c)
         rows, k, nbx, nbt = c["rows"], c["k"], c["nbx"], c["nbt"]
         fwd, bwd = (getattr(L, n) for n in ENTRY[kind])
-        a = Arena()
-        ptrs = [In(t[n]).p for n in (lc.RPN_ARGS if kind == "rpn" else lc.RCNN_ARGS)]
+        a = Arena(DEV)
+        ptrs = [In(DEV, t[n]).p for n in (lc.RPN_ARGS if kind == "rpn" else lc.RCNN_ARGS)]
         nbytes = getattr(L, "hf_%s_loss_workspace" % kind)()
-        out, ws, up = Out(a, 6, fill=SENTINEL), Out(a, nbytes // 4, fill=SENTINEL), In(np.ones(1, np.float32))
+        out, ws, up = Out(a, 6, fill=SENTINEL), Out(a, nbytes // 4, fill=SENTINEL), In(DEV, np.ones(1, np.float32))
         gl, gh = Out(a, rows * (k + 1), fill=SENTINEL), Out(a, rows * k * lc.head_width(nbx, nbt), fill=SENTINEL)
         s = scalars(c)
         assert fwd(rows, k, nbx, nbt, *ptrs, *s, out.p, ws.p, nbytes - 1, sp) == _lib.HF_EWORKSPACE

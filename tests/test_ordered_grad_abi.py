@@ -17,14 +17,15 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import ordered_grad_cases as oc  # noqa: E402
 import roi_image_cases as rc  # noqa: E402
-from test_bn_abi import Arena  # noqa: E402
-from test_xconv_abi import In, Out, _abi, call, dev64  # noqa: E402
+from abi_harness import Arena, In, Out, abi, call, dev64  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
+DEV = "cuda"
+
 
 def inp(a, off=False):
-    return In(a.copy(), off)
+    return In(DEV, a.copy(), off)
 
 
 def same_bits(got, want, name):
@@ -40,10 +41,10 @@ def workspace(nbytes):
 
 
 def run_project(name, ordered=True, short=0, off=False):
-    _lib, L = _abi()
+    _lib, L = abi()
     b, p, h, w, c = oc.PROJECT_CASES[name]
     t = oc.make_project(name)
-    a = Arena()
+    a = Arena(DEV)
     go, pix = inp(t["go"], off), inp(t["pix"])
     grad = Out(a, b * h * w * c, off=off)
     if ordered:
@@ -63,10 +64,10 @@ def run_project(name, ordered=True, short=0, off=False):
 
 
 def run_crop(name, ordered=True, short=0, off=False):
-    _lib, L = _abi()
+    _lib, L = abi()
     d, t = rc.dims(name), rc.make_inputs(name, True)
     n = t["boxes"].shape[0]
-    a = Arena()
+    a = Arena(DEV)
     go, boxes, ind = inp(t["go"], off), inp(t["boxes"]), inp(t["ind"])
     grad = Out(a, t["img"].size, off=off)
     dims = (d["b"], d["h"], d["w"], d["c"], n, d["ch"], d["cw"])
@@ -90,7 +91,7 @@ def against_the_atomic_entry(got, atomic, k, want64, bound, name):
     few = torch.from_numpy(np.broadcast_to((k <= 2)[..., None], tuple(got.shape)).copy()).cuda()
     differ = (got.contiguous().view(torch.int32) != atomic.contiguous().view(torch.int32)) & few
     assert not bool(differ.any()), "%s: %d elements of pixels with at most two entries differ from the atomic entry" % (name, int(differ.sum()))
-    want64, bound = dev64(want64.copy()), dev64(bound.copy())
+    want64, bound = dev64(DEV, want64.copy()), dev64(DEV, bound.copy())
     for what, x in (("ordered", got), ("atomic", atomic)):
         worst = float(((x.double() - want64).abs() / bound.clamp(min=1e-300)).max()) if x.numel() else 0.0
         print("%s %s: max |got - ref64| / bound = %.3g" % (name, what, worst))
@@ -148,7 +149,7 @@ def _replays(launch, go, rewrite, expect, name):
 
 
 def test_project_gather_grad_ordered_replays_in_a_captured_graph():
-    _lib, L = _abi()
+    _lib, L = abi()
     name = "straddle_c5"
     b, p, h, w, c = oc.PROJECT_CASES[name]
     t = oc.make_project(name)
@@ -171,7 +172,7 @@ def test_project_gather_grad_ordered_replays_in_a_captured_graph():
 
 
 def test_crop_and_resize_grad_ordered_replays_in_a_captured_graph():
-    _lib, L = _abi()
+    _lib, L = abi()
     name = "vec_c32"
     d, t = rc.dims(name), rc.make_inputs(name, True)
     n = t["boxes"].shape[0]

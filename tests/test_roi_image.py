@@ -11,6 +11,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import roi_image_cases as rc  # noqa: E402
+from abi_harness import within  # noqa: E402
 
 from heterofusionrcnn_amd import fusion  # noqa: E402
 
@@ -21,13 +22,10 @@ def dev(a):
     return torch.from_numpy(np.array(a)).cuda()
 
 
-def within(got, want64, bound, name):
+def within_host(got, want64, bound, name):
+    """abi_harness.within on the host, for references that are arrays or plain numbers"""
     tensor = lambda a: torch.from_numpy(np.array(a, np.float64)) if isinstance(a, np.ndarray) else torch.as_tensor(a, dtype=torch.float64)
-    diff = (got.double().cpu() - tensor(want64)).abs()
-    bound = tensor(bound)
-    worst = float((diff / bound.clamp(min=1e-300)).max()) if diff.numel() else 0.0
-    print("%s: max |got - ref| / bound = %.3g" % (name, worst))
-    assert bool((diff <= bound).all()), "%s: worst ratio %.3g" % (name, worst)
+    within(got.cpu(), tensor(want64), tensor(bound), name)
 
 
 class Calls:
@@ -60,15 +58,15 @@ def test_device_tensors_reach_the_kernels_and_agree_with_the_tensor_form(name, m
     tensor_form = fusion._image_crop_and_resize_tensor(img.detach(), boxes, ind, d["ch"], d["extrap"])
     assert calls.seen["hf_crop_and_resize"] == 1
     # each side is within the forward bound of the fp64 reference
-    within(out.detach(), r["out"], r["fwd_bound"], name + " kernel against the restatement")
-    within(tensor_form, r["out"], r["fwd_bound"], name + " tensor form against the restatement")
-    within(out.detach(), tensor_form.double().cpu(), r["fwd_bound"], name + " kernel against the tensor form")
+    within_host(out.detach(), r["out"], r["fwd_bound"], name + " kernel against the restatement")
+    within_host(tensor_form, r["out"], r["fwd_bound"], name + " tensor form against the restatement")
+    within_host(out.detach(), tensor_form.double().cpu(), r["fwd_bound"], name + " kernel against the tensor form")
     out.backward(go)
     assert calls.seen["hf_crop_and_resize_grad"] == 1
     # the [nan, ..., inf] row is among the boxes: the gradient is finite (the tensor form's is not) and within the backward bound
     assert not np.isfinite(t["boxes"][0]).all()
     assert bool(torch.isfinite(img.grad).all())
-    within(img.grad, r["grad"], r["grad_bound"], name + " gradient")
+    within_host(img.grad, r["grad"], r["grad_bound"], name + " gradient")
     assert bool((img.grad.cpu()[torch.from_numpy(r["k"] == 0)] == 0.0).all())
     assert boxes.grad is None
 
@@ -152,7 +150,7 @@ def test_rcnn_model_pools_the_image_with_two_launches_and_fuses_with_one(monkeyp
     t_rois = fusion._image_crop_and_resize_tensor(s["img_fts"], pool["yxyx"], pool["box_ind"], 7)
     ok = rc.samples(FRAMES, IMG_HW[0], IMG_HW[1], 7, 7, pool["yxyx"].cpu().numpy(), pool["box_ind"].cpu().numpy())["ok"]
     assert 0 < ok.sum() < ok.size                                  # samples inside and outside the image
-    within(pool["img_rois"], t_rois.double().cpu(), rc.FWD_BOUND * float(s["img_fts"].abs().max()), "RcnnModel img_rois")
+    within_host(pool["img_rois"], t_rois.double().cpu(), rc.FWD_BOUND * float(s["img_fts"].abs().max()), "RcnnModel img_rois")
     # ---- training mode: the flat_concat rows are [pc m0 | img m1] bit for bit, whatever the path drop decides
     seen = {}
     real_masks = RC.path_drop_masks
@@ -229,5 +227,5 @@ def test_projection_crop_and_backward_replay_from_one_graph():
         # atomics may order the sums differently in the two runs: each is within the bound of the fp64 scatter
         want, bound, k = rc.ref_backward((b, h, w, c), yxyx.cpu().numpy(), box_ind.cpu().numpy(), new_weight.cpu().numpy())
         assert k.max() >= 2
-        within(grad, want, bound, "replay %d: eager gradient" % seed)
-        within(g_grad, want, bound, "replay %d: replayed gradient" % seed)
+        within_host(grad, want, bound, "replay %d: eager gradient" % seed)
+        within_host(g_grad, want, bound, "replay %d: replayed gradient" % seed)

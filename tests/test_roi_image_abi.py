@@ -12,22 +12,23 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import roi_image_cases as rc  # noqa: E402
-from test_bn_abi import Arena, within  # noqa: E402
-from test_xconv_abi import In, Out, _abi, call, dev64  # noqa: E402
+from abi_harness import Arena, In, Out, abi, call, dev64, within  # noqa: E402
 
 pytestmark = pytest.mark.gpu
+
+DEV = "cuda"
 
 
 def inp(a, off=False):
     """the tables are read-only arrays: torch wants a writable one"""
-    return In(a.copy(), off)
+    return In(DEV, a.copy(), off)
 
 
 def run_forward(name, t, off=False):
-    _lib, L = _abi()
+    _lib, L = abi()
     d = rc.dims(name)
     n = t["boxes"].shape[0]
-    a = Arena()
+    a = Arena(DEV)
     img, boxes, ind = inp(t["img"], off), inp(t["boxes"]), inp(t["ind"])
     out = Out(a, n * d["ch"] * d["cw"] * d["c"], off=off)
     call(L.hf_crop_and_resize(d["b"], d["h"], d["w"], d["c"], n, d["ch"], d["cw"], img.p, boxes.p, ind.p, d["extrap"], out.p,
@@ -37,10 +38,10 @@ def run_forward(name, t, off=False):
 
 
 def run_backward(name, t, off=False):
-    _lib, L = _abi()
+    _lib, L = abi()
     d = rc.dims(name)
     n = t["boxes"].shape[0]
-    a = Arena()
+    a = Arena(DEV)
     go, boxes, ind = inp(t["go"]), inp(t["boxes"]), inp(t["ind"])
     grad = Out(a, t["img"].size, off=off)                         # pre-filled with NaN: a missing zero fill shows
     call(L.hf_crop_and_resize_grad(d["b"], d["h"], d["w"], d["c"], n, d["ch"], d["cw"], go.p, boxes.p, ind.p, grad.p,
@@ -54,8 +55,8 @@ def test_crop_and_resize_forward(name):
     d, t, r = rc.dims(name), rc.make_inputs(name, True), rc.reference(name, True)
     got = run_forward(name, t)
     assert torch.equal(got, run_forward(name, t)), "two calls differ"
-    want = dev64(r["out"].copy())
-    within(got, want, torch.full((), r["fwd_bound"], dtype=torch.float64, device="cuda"), "hf_crop_and_resize." + name)
+    want = dev64(DEV, r["out"].copy())
+    within(got, want, torch.full((), r["fwd_bound"], dtype=torch.float64, device="cuda"), "hf_crop_and_resize." + name, "round")
     if not d["n"]:
         return
     out_of_range = torch.from_numpy(~r["ok"]).cuda()
@@ -72,12 +73,12 @@ def test_crop_and_resize_forward(name):
 @pytest.mark.parametrize("name", list(rc.CROP_CASES))
 def test_crop_and_resize_gradient(name):
     t, r = rc.make_inputs(name, True), rc.reference(name, True)
-    want, bound = dev64(r["grad"].copy()), dev64(r["grad_bound"].copy())
+    want, bound = dev64(DEV, r["grad"].copy()), dev64(DEV, r["grad_bound"].copy())
     never = torch.from_numpy(np.broadcast_to((r["k"] == 0)[..., None], r["grad"].shape).copy()).cuda()
     for off in (False, True):           # the second call on a map one float past a 16-byte boundary: the zero fill's head and tail
         got = run_backward(name, t, off)
         assert bool(torch.isfinite(got).all())
-        within(got, want, bound, "hf_crop_and_resize_grad." + name)
+        within(got, want, bound, "hf_crop_and_resize_grad." + name, "round")
         assert bool((got[never] == 0.0).all())
 
 
@@ -90,13 +91,13 @@ def test_crop_and_resize_gradient_ignores_the_rows_that_fail():
     want, bound, _ = rc.ref_backward(t["img"].shape, t["boxes"][keep], t["ind"][keep], t["go"][keep])
     got = run_backward(name, t)
     assert bool(torch.isfinite(got).all())
-    within(got, dev64(want), dev64(bound), "hf_crop_and_resize_grad.%s without the failing rows" % name)
+    within(got, dev64(DEV, want), dev64(DEV, bound), "hf_crop_and_resize_grad.%s without the failing rows" % name, "round")
 
 
 def run_boxes(boxes, calib, which=(True, True, True)):
-    _lib, L = _abi()
+    _lib, L = abi()
     b, n, _ = boxes.shape
-    a = Arena()
+    a = Arena(DEV)
     bx, cal = inp(boxes), inp(calib)
     outs = [Out(a, b * n * 4, passed=w) for w in which]
     h, w = rc.IMAGE_HW

@@ -13,17 +13,13 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import row_gather_cases as rc  # noqa: E402
+from abi_harness import abi  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
 GUARD = 64                    # floats; a multiple of 4, so that the output keeps its alignment
 _REF = {}                     # references are computed once per case and shared
-
-
-def _abi():
-    from heterofusionrcnn_amd import _lib
-    return _lib, _lib.lib()
 
 
 def ref(kind, c, make):
@@ -82,7 +78,7 @@ def mk(rows):
 
 # ---------------------------------------------------------------- forward
 def run_forward(c, points, idx, weight):
-    _lib, L = _abi()
+    _lib, L = abi()
     b, n, m, k, ch, width, col = (c[x] for x in ("b", "n", "m", "k", "c", "width", "col"))
     rows = m * k
     p, i, w = Placed(points, c["off"] == "points"), Placed(idx), Placed(weight)
@@ -128,7 +124,7 @@ def inverse(L, nsrc, b, rows, n, idx):
 
 @pytest.mark.parametrize("c", rc.GATHER_GRAD_CASES, ids=rc.case_id)
 def test_gather_form_gradient_bit_equal(oracle_mod, c):
-    _lib, L = _abi()
+    _lib, L = abi()
     idx, weight, wide = ref("grad_in", c, lambda: rc.grad_inputs(c))
     want = ref("gg", c, lambda: rc.bits(rc.grad_oracle(oracle_mod, c, idx, weight, wide)))
     b, n, rows, ch, ld, col = (c[x] for x in ("b", "n", "rows", "c", "ld", "col"))
@@ -152,7 +148,7 @@ def test_gather_form_gradient_bit_equal(oracle_mod, c):
 
 @pytest.mark.parametrize("c", rc.SCATTER_CASES, ids=rc.case_id)
 def test_scatter_gradient_within_bound(c):
-    _lib, L = _abi()
+    _lib, L = abi()
     idx, weight, wide = ref("grad_in", c, lambda: rc.grad_inputs(c))
     want, bound = ref("sc", c, lambda: rc.scatter_reference(c, idx, weight, wide))
     b, n, rows, ch, ld, col = (c[x] for x in ("b", "n", "rows", "c", "ld", "col"))
@@ -184,7 +180,7 @@ def test_scatter_gradient_within_bound(c):
 def test_empty_shapes():
     """b = 0 launches nothing; no output rows: the forward writes nothing, the scatter gradients still zero-fill their target
     and the gather forms write it as zeros; three_interpolate_cl takes n = 0 unknown points the same way"""
-    _lib, L = _abi()
+    _lib, L = abi()
     z = Placed(np.zeros(64, np.float32))
     zi = Placed(np.zeros(64, np.int32))
     n, ch = 4, 3
@@ -219,7 +215,7 @@ def test_empty_shapes():
 
 # ---------------------------------------------------------------- inverse
 def test_both_inverse_entries_agree_and_keep_their_limits():
-    _lib, L = _abi()
+    _lib, L = abi()
     b, rows, n = 2, 37, 41
     rng = np.random.default_rng(5)
     idx = rng.integers(0, n, (b, rows, 3)).astype(np.int32)

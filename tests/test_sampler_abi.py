@@ -10,7 +10,6 @@ evaluation against its float64 evaluation, the image noise vector to 1e-12 relat
 Every output is pre-filled with a sentinel (NaN for floats, -7 for ints) and none may survive; every workspace is exactly the size its
 *_workspace entry point reports, carved out of a larger buffer whose guard bytes on both sides must be intact after the call.  The forced
 C-ABI call of every case must equal the Python wrapper on the same inputs, bit for bit."""
-import ctypes
 import os
 import sys
 
@@ -20,57 +19,16 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import sampler_cases as sc  # noqa: E402
+from abi_harness import Workspace, abi, dev, filled, host, same_array  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-GUARD, GUARD_BYTE = 256, 0xA5
+DEV = "cuda"
 RATIOS = {"iou": 0.0, "normal": 0.0}
 
 
-def _abi():
-    from heterofusionrcnn_amd import _lib
-    return _lib, _lib.lib()
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def host(t):
-    return t.detach().cpu().numpy()
-
-
-def filled(shape, dtype):
-    return torch.full(shape, float("nan") if dtype.is_floating_point else sc.SENT_I, dtype=dtype, device="cuda")
-
-
-class Workspace:
-    """exactly nbytes between two guards"""
-
-    def __init__(self, nbytes):
-        self.nbytes = int(nbytes)
-        self.buf = torch.full((self.nbytes + 2 * GUARD,), GUARD_BYTE, dtype=torch.uint8, device="cuda")
-        assert self.buf.data_ptr() % 256 == 0
-        self.p = ctypes.c_void_p(self.buf.data_ptr() + GUARD)
-
-    def check(self, what):
-        torch.cuda.synchronize()
-        assert bool((self.buf[:GUARD] == GUARD_BYTE).all()), "%s: the guard below the workspace was written" % what
-        assert bool((self.buf[GUARD + self.nbytes:] == GUARD_BYTE).all()), "%s: the guard above the workspace was written" % what
-
-
 def same(got, want, what, c):
-    got = host(got) if isinstance(got, torch.Tensor) else got
-    want = np.asarray(want)
-    assert got.shape == want.shape and got.dtype == want.dtype, (what, got.shape, want.shape, got.dtype, want.dtype)
-    if got.dtype.kind == "f":
-        assert not np.isnan(got).any(), "%s of %s: %d elements never written" % (what, sc.case_id(c), int(np.isnan(got).sum()))
-    else:
-        assert not (got == sc.SENT_I).any(), "%s of %s: %d elements never written" % (what, sc.case_id(c), int((got == sc.SENT_I).sum()))
-    if not np.array_equal(got, want):
-        bad = np.argwhere(got != want)
-        raise AssertionError("%s of %s: %d of %d elements differ, the first at %s: got %r, want %r"
-                             % (what, sc.case_id(c), len(bad), got.size, tuple(bad[0]), got[tuple(bad[0])], want[tuple(bad[0])]))
+    same_array(got, want, what, sc.case_id(c), unwritten=sc.SENT_I)
 
 
 def same_bits(a, b, what, c):
@@ -88,18 +46,18 @@ def ratio_report():
 @pytest.mark.parametrize("c", sc.cases_of("points"), ids=sc.case_id)
 def test_rpn_batch_points(c):
     from heterofusionrcnn_amd import kitti_data as KD
-    _lib, L = _abi()
+    _lib, L = abi()
     t = sc.make_inputs(c)
     b, p, total, mx = len(c["frames"]), c["p"], t["total"], t["max_frame"]
-    ins = [dev(t[k]) for k in ("points", "offsets", "velo_to_rect", "p2", "wh", "flip")]
-    state, wstate = dev(t["state"]), dev(t["state"])
+    ins = [dev(DEV, t[k]) for k in ("points", "offsets", "velo_to_rect", "p2", "wh", "flip")]
+    state, wstate = dev(DEV, t["state"]), dev(DEV, t["state"])
     nbytes = L.hf_rpn_batch_points_workspace(b, total, mx)
     assert nbytes == sc.rpn_points_workspace(b, total, mx) and nbytes % 256 == 0
     for call in range(c["calls"]):
         want = sc.ref_rpn_points(c, t, call)
-        xyz, inten = filled((b, p, 3), torch.float32), filled((b, p, 1), torch.float32)
-        src, status = filled((b, p), torch.int32), filled((b,), torch.int32)
-        ws = Workspace(nbytes)
+        xyz, inten = filled(DEV, (b, p, 3), torch.float32, sc.SENT_I), filled(DEV, (b, p, 1), torch.float32, sc.SENT_I)
+        src, status = filled(DEV, (b, p), torch.int32, sc.SENT_I), filled(DEV, (b,), torch.int32, sc.SENT_I)
+        ws = Workspace(DEV, nbytes)
         _lib.check(L.hf_rpn_batch_points(b, p, total, mx, *[_lib.ptr(x) for x in ins], _lib.ptr(state), _lib.ptr(xyz), _lib.ptr(inten),
                                          _lib.ptr(src), _lib.ptr(status), ws.p, nbytes, _lib.stream_ptr()), "rpn_batch_points")
         ws.check("hf_rpn_batch_points")
@@ -118,12 +76,12 @@ def test_rpn_batch_points(c):
 @pytest.mark.parametrize("c", sc.cases_of("labels"), ids=sc.case_id)
 def test_rpn_point_labels(c):
     from heterofusionrcnn_amd import kitti_data as KD
-    _lib, L = _abi()
+    _lib, L = abi()
     t = sc.make_inputs(c)
     b, p, g = c["b"], c["p"], c["g"]
     want_cls, want_reg, _ = sc.ref_rpn_labels(c, t)
-    xyz, boxes, classes, cnt = dev(t["xyz"]), dev(t["boxes"]), dev(t["classes"]), dev(t["gt_count"])
-    cls, reg = filled((b, p), torch.int32), filled((b, p, 7), torch.float32)
+    xyz, boxes, classes, cnt = dev(DEV, t["xyz"]), dev(DEV, t["boxes"]), dev(DEV, t["classes"]), dev(DEV, t["gt_count"])
+    cls, reg = filled(DEV, (b, p), torch.int32, sc.SENT_I), filled(DEV, (b, p, 7), torch.float32, sc.SENT_I)
     _lib.check(L.hf_rpn_point_labels(b, p, g, _lib.ptr(xyz), _lib.ptr(boxes) if g else None, _lib.ptr(classes) if g else None, _lib.ptr(cnt),
                                      float(c["expand"]), _lib.ptr(cls), _lib.ptr(reg), _lib.stream_ptr()), "rpn_point_labels")
     torch.cuda.synchronize()
@@ -140,17 +98,17 @@ def test_rpn_point_labels(c):
 @pytest.mark.parametrize("c", sc.cases_of("image"), ids=sc.case_id)
 def test_rpn_batch_image(c):
     from heterofusionrcnn_amd import kitti_data as KD
-    _lib, L = _abi()
+    _lib, L = abi()
     t = sc.make_inputs(c)
     b = len(c["frames"])
     ow, oh = c["out"]
-    ins = [dev(t[k]) for k in ("images", "offsets", "wh", "flip", "jitter")]
-    state, wstate = dev(t["state"]), dev(t["state"])
+    ins = [dev(DEV, t[k]) for k in ("images", "offsets", "wh", "flip", "jitter")]
+    state, wstate = dev(DEV, t["state"]), dev(DEV, t["state"])
     nbytes = L.hf_rpn_batch_image_workspace(b, t["max_pixels"])
     assert nbytes == sc.rpn_image_workspace(b, t["max_pixels"])
     for call in range(c["calls"]):
-        image, noise, stats = filled((b, oh, ow, 3), torch.float32), filled((b, 3), torch.float64), filled((b, 21), torch.float64)
-        ws = Workspace(nbytes)
+        image, noise, stats = filled(DEV, (b, oh, ow, 3), torch.float32, sc.SENT_I), filled(DEV, (b, 3), torch.float64, sc.SENT_I), filled(DEV, (b, 21), torch.float64, sc.SENT_I)
+        ws = Workspace(DEV, nbytes)
         _lib.check(L.hf_rpn_batch_image(b, t["max_pixels"], len(t["images"]), *[_lib.ptr(x) for x in ins], oh, ow, _lib.ptr(state),
                                         _lib.ptr(image), _lib.ptr(noise), _lib.ptr(stats), ws.p, nbytes, _lib.stream_ptr()), "rpn_batch_image")
         ws.check("hf_rpn_batch_image")
@@ -180,11 +138,11 @@ def test_rpn_batch_image(c):
 
 # ---------------------------------------------------------------------------------------------- RCNN targets
 def _targets_call(c, t, state, ws):
-    _lib, L = _abi()
+    _lib, L = abi()
     b, m, g, r = c["b"], c["m"], c["g"], c["r"]
     ins = t["dev"]
-    rois, iou, gt_of = filled((b, r, 7), torch.float32), filled((b, r), torch.float32), filled((b, r, 8), torch.float32)
-    stats = filled((b, 4), torch.int32)
+    rois, iou, gt_of = filled(DEV, (b, r, 7), torch.float32, sc.SENT_I), filled(DEV, (b, r), torch.float32, sc.SENT_I), filled(DEV, (b, r, 8), torch.float32, sc.SENT_I)
+    stats = filled(DEV, (b, 4), torch.int32, sc.SENT_I)
     f32 = lambda v: float(np.float32(v))
     _lib.check(L.hf_rcnn_proposal_targets(b, m, g, _lib.ptr(ins[0]), _lib.ptr(ins[1]), _lib.ptr(ins[2]) if g else None, _lib.ptr(ins[3]),
                                           f32(c["neg"][0]), f32(c["neg"][1]), f32(c["pos"][0]), f32(c["pos"][1]), r, f32(c["fg_ratio"]),
@@ -212,17 +170,17 @@ def normal_bound(want32, want64, src, max_normal):
 @pytest.mark.parametrize("c", sc.cases_of("targets"), ids=sc.case_id)
 def test_rcnn_proposal_targets(c, oracle_mod):
     from heterofusionrcnn_amd import rcnn_train as RT
-    _lib, L = _abi()
+    _lib, L = abi()
     t = dict(sc.make_inputs(c))
     b, m, g, r = c["b"], c["m"], c["g"], c["r"]
-    t["dev"] = [dev(t[k]) for k in ("proposals", "proposal_count", "gt", "gt_count")]
-    state, wstate = dev(t["state"]), dev(t["state"])
+    t["dev"] = [dev(DEV, t[k]) for k in ("proposals", "proposal_count", "gt", "gt_count")]
+    state, wstate = dev(DEV, t["state"]), dev(DEV, t["state"])
     nbytes = L.hf_rcnn_targets_workspace(b, m, g)
     assert nbytes == sc.rcnn_targets_workspace(b, m, g)
     aug = sc.aug_code(c)
     for call in range(c["calls"]):
         want = sc.ref_rcnn_targets(c, t, call)
-        rois, iou, gt_of, stats = _targets_call(c, t, state, Workspace(nbytes))
+        rois, iou, gt_of, stats = _targets_call(c, t, state, Workspace(DEV, nbytes))
         same(stats, want["stats"], "stats (call %d)" % call, c)
         same(gt_of, want["gt_of_rois"], "gt_of_rois", c)
         if c["train"]:
@@ -260,10 +218,10 @@ def test_rcnn_proposal_targets(c, oracle_mod):
 @pytest.mark.parametrize("c", [c for c in sc.cases_of("targets") if c["calls"] == 1 and (c["train"] or c["g"] == 0)], ids=sc.case_id)
 def test_box3d_iou_matrix(c, oracle_mod):
     from heterofusionrcnn_amd import rcnn_data
-    _lib, L = _abi()
+    _lib, L = abi()
     t = sc.make_inputs(c)
     b, m, g = c["b"], c["m"], c["g"]
-    ins = [dev(t[k]) for k in ("proposals", "proposal_count", "gt", "gt_count")]
+    ins = [dev(DEV, t[k]) for k in ("proposals", "proposal_count", "gt", "gt_count")]
     out = torch.full((b, m, max(g, 1)), float("nan"), dtype=torch.float32, device="cuda")
     status = L.hf_box3d_iou_matrix(b, m, g, _lib.ptr(ins[0]), _lib.ptr(ins[1]), _lib.ptr(ins[2]) if g else None, _lib.ptr(ins[3]), _lib.ptr(out),
                                    _lib.stream_ptr())

@@ -7,7 +7,7 @@ element for element, so out, grad_x, grad_f, grad_wd and grad_fts must be the SA
 dbeta are new sums in another order than hf_bn_relu_bwd's; they are held to fp64 NumPy / torch sums of the kernel's own grad_f with the
 bound form tests/bn_cases.py derives for the bn_bwd sums (ref_bn_bwd: gamma(chain + 3) sum |dh| X + the ELU term + the cast), `chain` =
 the fp32 additions on the longest path into one block's partial.  Inputs are seeded normals / uniforms (no integers: every order of adds
-rounds differently), outputs are sentinel-guarded slices, inputs lie between NaN bands (tests/test_xconv_abi.py's In / Out).
+rounds differently), outputs are sentinel-guarded slices, inputs lie between NaN bands (tests/abi_harness.py's In / Out).
 
 Shapes.  B = 2 clouds of n_src = 50 table rows and P = 37 points: 74 rows.
   forward   xdw_pair_grid gives 19 blocks of rows_per_block = 4 (the last one 2): a block trip covers 8 rows (4 waves x kXcRows = 2), so
@@ -20,8 +20,6 @@ Shapes.  B = 2 clouds of n_src = 50 table rows and P = 37 points: 74 rows.
             one 16.  P is sized from those two numbers, which the test reads back from the workspace query.
 c0 = 64: a forward wave (128 channels) straddles the lifted / gathered split at lane 32; c0 = 128: it does not.  c1 = 1 makes c odd: V2 =
 false loads and a dead upper half in the last pair; c1 = 64 and 66 are the V2 = true forms, 66 with one live pair in the last chunk."""
-import ctypes
-import json
 import os
 import sys
 
@@ -32,9 +30,8 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import bn_cases as bc  # noqa: E402
 import xconv_cases as xc  # noqa: E402
-from test_bn_abi import SENTINEL, Arena, within  # noqa: E402
-import test_bn_abi as bn_abi  # noqa: E402
-from test_xconv_abi import In, Out  # noqa: E402
+from abi_harness import SENTINEL, Arena, In, Out, abi, call, parity_report, within  # noqa: E402
+from xconv_runs import check_argument_limits  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -43,30 +40,12 @@ B, N_SRC, P = 2, 50, 37
 TALL = dict(k=8, m=1, c0=128, c1=64, b=2, n=N_SRC, p=4200)
 CASES = [dict(k=k, m=m, c0=c0, c1=c1, b=B, n=N_SRC, p=P) for (k, m) in KM for c0 in (64, 128) for c1 in (1, 64, 66)] + [TALL]
 OUTPUTS = ("out", "x", "f", "wd", "fts", "dgamma", "dbeta")
+DEV = "cuda"
+parity_report = parity_report("XCONV_BN_PARITY_OUT", "hf_xconv_depthwise_gather_bn")      # the source of profiles/xconv_bn_parity.md
 
 
 def case_id(c):
     return "k%dm%d-c%d+%d-b%dp%dn%d" % (c["k"], c["m"], c["c0"], c["c1"], c["b"], c["p"], c["n"])
-
-
-def _abi():
-    from heterofusionrcnn_amd import _lib
-    return _lib, _lib.lib()
-
-
-def call(status, name):
-    _lib, _ = _abi()
-    _lib.check(status, name)
-
-
-@pytest.fixture(scope="module", autouse=True)
-def parity_report():
-    """XCONV_BN_PARITY_OUT=<file>: the worst error / bound ratios of the session as JSON (the source of profiles/xconv_bn_parity.md)"""
-    yield
-    path = os.environ.get("XCONV_BN_PARITY_OUT")
-    if path:
-        with open(path, "w") as f:
-            json.dump({"%s|%s" % k: v for k, v in sorted(bn_abi.RATIOS.items()) if k[0].startswith("hf_xconv_depthwise_gather_bn")}, f, indent=1)
 
 
 def make_inputs(c):
@@ -88,7 +67,7 @@ class Device:
     def __init__(self, c, t):
         self.c, self.t = c, t
         for name in ("x", "z1", "fts", "wd", "go", "gamma", "beta", "mean", "invstd", "idx", "offsets", "entries"):
-            setattr(self, name, In(t[name]))
+            setattr(self, name, In(DEV, t[name]))
 
 
 def dims(c):
@@ -103,12 +82,12 @@ def sizes(c):
 
 def run_old(d):
     """hf_bn_relu_fwd_eval into a buffer, then the unfolded pair of entries (the gradient with its workspace)"""
-    _lib, L = _abi()
+    _lib, L = abi()
     sp = _lib.stream_ptr()
     c = d.c
     b, n, p, k, c0, c1, m = dims(c)
     sz = sizes(c)
-    a = Arena()
+    a = Arena(DEV)
     f = Out(a, sz["f"])
     call(L.hf_bn_relu_fwd_eval(b * p * k, c0, d.z1.p, d.gamma.p, d.beta.p, d.mean.p, d.invstd.p, 2, f.p, sp), "hf_bn_relu_fwd_eval")
     g = {name: Out(a, sz[name]) for name in ("out", "x", "f", "wd", "fts")}
@@ -122,12 +101,12 @@ def run_old(d):
 
 
 def run_new(d):
-    _lib, L = _abi()
+    _lib, L = abi()
     sp = _lib.stream_ptr()
     c = d.c
     b, n, p, k, c0, c1, m = dims(c)
     sz = sizes(c)
-    a = Arena()
+    a = Arena(DEV)
     g = {name: Out(a, sz[name]) for name in OUTPUTS}
     call(L.hf_xconv_depthwise_gather_bn(b, n, p, k, c0, c1, m, d.x.p, d.z1.p, d.gamma.p, d.beta.p, d.mean.p, d.invstd.p, d.fts.p, d.idx.p,
                                         d.wd.p, g["out"].p, sp), "hf_xconv_depthwise_gather_bn")
@@ -173,7 +152,7 @@ def test_folded_entries_against_the_two_launch_route(c):
 
 def test_the_launchers_give_the_geometry_the_shapes_were_sized_for():
     """rows_per_block of both launchers, read back from the library: the backward grid is the number of partial rows in the workspace"""
-    _, L = _abi()
+    _, L = abi()
     for c, fwd, bwd in ((CASES[0], (19, 4, 2), (3, 32, 10)), (TALL, (934, 9, 3), (263, 32, 16))):
         b, n, p, k, c0, c1, m = dims(c)
         rows, ch = b * p, c0 + c1
@@ -187,5 +166,4 @@ def test_the_launchers_give_the_geometry_the_shapes_were_sized_for():
 
 
 def test_one_past_each_argument_limit_is_refused():
-    import test_xconv_bn_instantiations_cpu as cpu
-    cpu.check_argument_limits()
+    check_argument_limits()

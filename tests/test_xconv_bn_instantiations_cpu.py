@@ -10,7 +10,8 @@ import tempfile
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from test_gemm_instantiations_cpu import compile_to_assembly, kernel_table  # noqa: E402
+from kernel_asm import compile_to_assembly, kernel_table  # noqa: E402
+from xconv_runs import check_argument_limits  # noqa: E402
 
 XBN_DISPATCH = ((8, 1), (8, 2), (8, 4))        # HF_XBN_DISPATCH of csrc/xconv_bn.hip = _XBN_KM of pointcnn.py
 
@@ -53,45 +54,6 @@ def test_the_backward_keeps_four_waves_per_simd(table):
             seen += 1
             assert args[3] is True and f["vgpr"] <= 128, (args, f["vgpr"])
     assert seen == len(XBN_DISPATCH)
-
-
-def check_argument_limits():
-    """one past each limit of the two entry points returns HF_EINVAL before any launch (fake non-null pointers, never dereferenced); the
-    limit itself passes the argument check and is stopped by the missing workspace.  tests/test_xconv_bn_abi.py runs this on the GPU too"""
-    import ctypes
-    from heterofusionrcnn_amd import _lib
-    L = _lib.lib()
-    fake = ctypes.c_void_p(256)
-    EINVAL, EWS = _lib.HF_EINVAL, _lib.HF_EWORKSPACE
-
-    def fwd(b=2, n=50, p=37, k=8, c0=64, c1=32, m=1, null=None, out=fake):
-        ins = [None if i == null else fake for i in range(9)]           # x z1 gamma beta mean invstd fts idx wd
-        return L.hf_xconv_depthwise_gather_bn(b, n, p, k, c0, c1, m, *ins, out, None)
-
-    def bwd(b=2, n=50, p=37, k=8, c0=64, c1=32, m=1, null=None, inv=(fake, fake), grads=(fake, fake, fake, fake), sums=(fake, fake), ws=None, nbytes=0):
-        ins = [None if i == null else fake for i in range(10)]          # ... and grad_out
-        return L.hf_xconv_depthwise_gather_bn_grad(b, n, p, k, c0, c1, m, *ins, *inv, *grads, *sums, ws, nbytes, None)
-
-    bad = {}
-    for name, f in (("fwd", fwd), ("bwd", bwd)):
-        bad.update({"%s: c0 = 48" % name: f(c0=48), "%s: c0 = 0" % name: f(c0=0), "%s: c1 = 0" % name: f(c1=0), "%s: n_src = 0" % name: f(n=0),
-                    "%s: (8, 3)" % name: f(m=3), "%s: (8, 8)" % name: f(m=8), "%s: (4, 1)" % name: f(k=4), "%s: (12, 1)" % name: f(k=12),
-                    "%s: b < 0" % name: f(b=-1),
-                    "%s: rows k c = 2^32" % name: f(b=1024, p=1024, c0=256, c1=256), "%s: table rows x c = 2^32" % name: f(b=1024, n=8192, p=1, c0=256, c1=256)})
-        bad.update({"%s: input %d is NULL" % (name, i): f(null=i) for i in range(9)})
-    bad.update({"fwd: no output": fwd(out=None), "bwd: no grad_out": bwd(null=9), "bwd: nothing asked for": bwd(grads=(None,) * 4),
-                "bwd: grad_fts without the inverse table": bwd(inv=(None, None)), "bwd: grad_f without dgamma": bwd(sums=(None, fake)),
-                "bwd: grad_f without dbeta": bwd(sums=(fake, None))})
-    wrong = {name: got for name, got in bad.items() if got != EINVAL}
-    assert not wrong, wrong
-    # the limits themselves: only the workspace is left to refuse
-    assert bwd() == EWS and bwd(m=2) == EWS and bwd(m=4) == EWS and bwd(c0=128) == EWS
-    assert bwd(b=1024, p=1023, c0=256, c1=256) == EWS and bwd(b=1024, n=8191, p=1, c0=256, c1=256) == EWS
-    need = L.hf_xconv_depthwise_gather_bn_grad_workspace(2, 37, 8, 64, 32, 1)
-    assert need > L.hf_xconv_depthwise_gather_grad_workspace(2, 37, 8, 64, 32, 1) and bwd(ws=fake, nbytes=need - 1) == EWS
-    assert bwd(grads=(fake, None, fake, fake), sums=(None, None)) == EWS        # without grad_f the two sums are not required
-    assert L.hf_xconv_depthwise_gather_bn_grad_workspace(0, 37, 8, 64, 32, 1) == 0
-    assert fwd(b=0) == _lib.HF_OK                                               # an empty batch launches nothing
 
 
 def test_one_past_each_argument_limit_is_refused():

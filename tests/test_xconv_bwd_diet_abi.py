@@ -22,7 +22,6 @@ Shapes (the smallest at which each path of the new code is taken):
                block's chunk, the last block of xconv_dw_bwd_fw_kernel holds one row); 131 rows (blocks of 33: an odd chunk, the last 32)
   options      M = 1, 2, 3, 4 dense; M = 1, 2, 4 folded; each of grad_x, grad_f, grad_wd, grad_fts alone and all together
 Every gather and folded case is called twice: the same bits."""
-import ctypes
 import os
 import sys
 
@@ -32,20 +31,11 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import xconv_cases as xc  # noqa: E402
-import test_xconv_abi as xa  # noqa: E402
-from test_bn_abi import SENTINEL, Arena  # noqa: E402
-from test_xconv_abi import In, Out, call  # noqa: E402
+import xconv_runs as xa  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 FOLDED_KM = ((8, 1), (8, 2), (8, 4))
-
-
-def n_grad_x(c):
-    """roundings on the longest path into one entry of grad_x, from xc_bwd_x_rows' add order"""
-    n = c["m"] + xc.cdiv(c["c0"] + c["c1"], 64) + 6
-    assert n <= xc.roundings(c)["x"]
-    return n
 
 
 def _c(family, regime, k, m, gather, b, p, n, c0, c1, **kw):
@@ -90,15 +80,6 @@ CASES = _cases()
 FOLDED = [c for c in CASES if c["gather"] and (c["k"], c["m"]) in FOLDED_KM]
 
 
-def _check(c, t, got, entry):
-    ref = xc.ref_fused_bwd(c, t, c["want"])
-    mag = {} if xa.is_exact(c) else xc.ref_fused_bwd(c, t, c["want"], mag=True)
-    n = xc.roundings(c, t)
-    n["x"] = n_grad_x(c)
-    for name in got:
-        xa.compare(c, got[name], ref[name], mag.get(name), n[name], "%s.grad_%s" % (entry, name))
-
-
 @pytest.mark.parametrize("c", CASES, ids=xc.case_id)
 def test_backward_entries(c):
     """hf_xconv_depthwise_grad, or hf_xconv_depthwise_gather_grad with a workspace and without one (the same bits in every output but
@@ -106,76 +87,24 @@ def test_backward_entries(c):
     t = xc.make_inputs(c)
     got, _ = xa.run_bwd(c, t)
     assert set(got) == set(c["want"])
-    _check(c, t, got, "hf_xconv_depthwise%s_grad" % ("_gather" if c["gather"] else ""))
+    xa.check_bwd_short_x(c, t, got, "hf_xconv_depthwise%s_grad" % ("_gather" if c["gather"] else ""))
     if not c["gather"]:
         return
     again, _ = xa.run_bwd(c, t)
     for name in got:
         assert torch.equal(got[name], again[name]), "grad_%s differs between two calls" % name
     other, _ = xa.run_bwd(c, t, ws=not c["ws"])
-    _check(dict(c, ws=not c["ws"]), t, other, "hf_xconv_depthwise_gather_grad")
+    xa.check_bwd_short_x(dict(c, ws=not c["ws"]), t, other, "hf_xconv_depthwise_gather_grad")
     for name in got:
         if name != "wd":
             assert torch.equal(got[name], other[name]), "grad_%s differs with and without a workspace" % name
 
 
 # ------------------------------------------------------------------------------------------------------- the folded entry
-def folded_inputs(c):
-    """the case's inputs with z1 in place of F_delta and the four BatchNorm constants"""
-    t = xc.make_inputs(c)
-    rng = np.random.default_rng(xc._seed(c) ^ 0x5eed)
-    c0 = c["c0"]
-    if xa.is_exact(c):
-        t["z1"] = rng.integers(1, 3, t["fd"].shape).astype(np.float32)
-        t["gamma"], t["invstd"] = np.ones(c0, np.float32), np.ones(c0, np.float32)
-        t["mean"], t["beta"] = np.zeros(c0, np.float32), np.zeros(c0, np.float32)
-    else:
-        t["z1"] = t["fd"]
-        t["gamma"], t["invstd"] = rng.uniform(0.5, 1.5, c0).astype(np.float32), rng.uniform(0.5, 2.0, c0).astype(np.float32)
-        t["mean"], t["beta"] = (0.1 * rng.standard_normal(c0)).astype(np.float32), (0.1 * rng.standard_normal(c0)).astype(np.float32)
-    return t
-
-
-def run_folded(c, t):
-    """-> (the gradients of hf_xconv_depthwise_gather_bn_grad, those of hf_bn_relu_fwd_eval + hf_xconv_depthwise_gather_grad with a
-    workspace, F_delta as the library normalises it)"""
-    _lib, L = xa._abi()
-    sp = _lib.stream_ptr()
-    b, n, p, k, c0, c1, m = c["b"], c["n"], c["p"], c["k"], c["c0"], c["c1"], c["m"]
-    rows = b * p
-    d = {name: In(t[name]) for name in ("x", "z1", "fts", "wd", "go", "gamma", "beta", "mean", "invstd", "idx", "offsets", "entries")}
-    a = Arena()
-    f = Out(a, rows * k * c0)
-    call(L.hf_bn_relu_fwd_eval(rows * k, c0, d["z1"].p, d["gamma"].p, d["beta"].p, d["mean"].p, d["invstd"].p, 2, f.p, sp), "hf_bn_relu_fwd_eval")
-    res = []
-    for folded in (True, False):
-        g = {name: Out(a, xa.BWD_SHAPES[name](c), passed=name in c["want"]) for name in xc.ALL4}
-        if folded:
-            dg, db = Out(a, c0, passed="f" in c["want"]), Out(a, c0, passed="f" in c["want"])
-            nbytes = L.hf_xconv_depthwise_gather_bn_grad_workspace(b, p, k, c0, c1, m)
-            ws = Out(a, nbytes // 4, fill=SENTINEL)
-            call(L.hf_xconv_depthwise_gather_bn_grad(b, n, p, k, c0, c1, m, d["x"].p, d["z1"].p, d["gamma"].p, d["beta"].p, d["mean"].p,
-                                                     d["invstd"].p, d["fts"].p, d["idx"].p, d["wd"].p, d["go"].p, d["offsets"].p,
-                                                     d["entries"].p, g["x"].p, g["f"].p, g["fts"].p, g["wd"].p, dg.p, db.p, ws.p, nbytes, sp),
-                 "hf_xconv_depthwise_gather_bn_grad")
-        else:
-            nbytes = L.hf_xconv_depthwise_gather_grad_workspace(b, p, k, c0, c1, m)
-            ws = Out(a, nbytes // 4, fill=SENTINEL)
-            call(L.hf_xconv_depthwise_gather_grad(b, n, p, k, c0, c1, m, d["x"].p, f.p, d["fts"].p, d["idx"].p, d["wd"].p, d["go"].p,
-                                                  d["offsets"].p, d["entries"].p, g["x"].p, g["f"].p, g["fts"].p, g["wd"].p, ws.p, nbytes, sp),
-                 "hf_xconv_depthwise_gather_grad")
-        a.check()
-        for name in xc.ALL4:
-            if not g[name].passed:
-                assert bool((g[name].view == SENTINEL).all()), "grad_%s was not asked for and was written" % name
-        res.append({name: g[name].view for name in xc.ALL4 if g[name].passed})
-    return res[0], res[1], f.view
-
-
 @pytest.mark.parametrize("c", FOLDED, ids=xc.case_id)
 def test_folded_entry(c):
-    t = folded_inputs(c)
-    new, old, f = run_folded(c, t)
+    t = xa.folded_inputs(c)
+    new, old, f = xa.run_folded(c, t)
     assert set(new) == set(c["want"])
     for name in new:
         assert torch.equal(new[name], old[name]), "grad_%s: %d of %d elements are not the bits of the two-launch route" % (
@@ -183,8 +112,8 @@ def test_folded_entry(c):
     t["fd"] = f.cpu().numpy().reshape(t["fd"].shape)
     if xa.is_exact(c):
         assert np.array_equal(t["fd"], t["z1"])
-    _check(c, t, new, "hf_xconv_depthwise_gather_bn_grad")
-    again, _, _ = run_folded(c, t)
+    xa.check_bwd_short_x(c, t, new, "hf_xconv_depthwise_gather_bn_grad")
+    again, _, _ = xa.run_folded(c, t)
     for name in new:
         assert torch.equal(new[name], again[name]), "grad_%s differs between two calls" % name
 

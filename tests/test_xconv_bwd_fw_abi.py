@@ -10,7 +10,7 @@ EXACT family (integers in [-2, 2]; folded: z1 in {1, 2}, gamma = invstd = 1, mea
 ROUND family (seeded normals): within xconv_cases' n u M; the kernel's add order is the one those counts were taken from (every output
 element keeps its sequence of multiplies and adds; packing runs across pairs of k or j, never along a sum), so no new count is needed.
 The folded entry is also held to the bits of the two-launch route.  Every gather and folded case is called twice: the same bits.
-Sentinels surround every output (test_bn_abi.Arena).
+Sentinels surround every output (abi_harness.Arena).
 
 Shapes (the smallest at which each path is taken):
   rows      1 row (three waves have none, the batch has one live row); 5 rows with rows_per_cloud = 1 (every row its own cloud); 33 rows
@@ -29,8 +29,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import xconv_cases as xc  # noqa: E402
-import test_xconv_abi as xa  # noqa: E402
-import test_xconv_bwd_diet_abi as bd  # noqa: E402
+import xconv_runs as xa  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -94,7 +93,7 @@ def test_backward_entries(c):
     t = xc.make_inputs(c)
     got, _ = xa.run_bwd(c, t)
     assert set(got) == set(c["want"])
-    bd._check(c, t, got, "hf_xconv_depthwise%s_grad" % ("_gather" if c["gather"] else ""))
+    xa.check_bwd_short_x(c, t, got, "hf_xconv_depthwise%s_grad" % ("_gather" if c["gather"] else ""))
     if not c["gather"]:
         return
     again, _ = xa.run_bwd(c, t)
@@ -102,7 +101,7 @@ def test_backward_entries(c):
         if name != "wd" or c["ws"]:
             assert torch.equal(got[name], again[name]), "grad_%s differs between two calls" % name
     other, _ = xa.run_bwd(c, t, ws=not c["ws"])
-    bd._check(dict(c, ws=not c["ws"]), t, other, "hf_xconv_depthwise_gather_grad")
+    xa.check_bwd_short_x(dict(c, ws=not c["ws"]), t, other, "hf_xconv_depthwise_gather_grad")
     for name in got:
         if name != "wd":
             assert torch.equal(got[name], other[name]), "grad_%s differs with and without a workspace" % name
@@ -110,8 +109,8 @@ def test_backward_entries(c):
 
 @pytest.mark.parametrize("c", FOLDED, ids=xc.case_id)
 def test_folded_entry(c):
-    t = bd.folded_inputs(c)
-    new, old, f = bd.run_folded(c, t)
+    t = xa.folded_inputs(c)
+    new, old, f = xa.run_folded(c, t)
     assert set(new) == set(c["want"])
     for name in new:
         assert torch.equal(new[name], old[name]), "grad_%s: %d of %d elements are not the bits of the two-launch route" % (
@@ -119,8 +118,8 @@ def test_folded_entry(c):
     t["fd"] = f.cpu().numpy().reshape(t["fd"].shape)
     if xa.is_exact(c):
         assert (t["fd"] == t["z1"]).all()
-    bd._check(c, t, new, "hf_xconv_depthwise_gather_bn_grad")
-    again, _, _ = bd.run_folded(c, t)
+    xa.check_bwd_short_x(c, t, new, "hf_xconv_depthwise_gather_bn_grad")
+    again, _, _ = xa.run_folded(c, t)
     for name in new:
         assert torch.equal(new[name], again[name]), "grad_%s differs between two calls" % name
 

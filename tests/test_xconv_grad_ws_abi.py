@@ -24,7 +24,9 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from abi_harness import SENTINEL, Arena, In, Out, abi, call, dev64, within  # noqa: E402
 
+DEV = "cuda"
 U = 2.0 ** -24
 # name: (rows, k, c, m, expected row chunks)
 CASES = {"one_chunk": (3, 8, 40, 2, 1), "five_chunks": (20, 8, 40, 2, 5), "ragged_3": (77, 8, 40, 1, 3), "ragged_44": (1400, 8, 40, 2, 44),
@@ -64,13 +66,11 @@ def test_workspace_size_and_argument_checks_without_a_gpu():
 
 
 def _run(name, with_ws, off=False):
-    from test_bn_abi import Arena
-    from test_xconv_abi import In, Out, _abi, call
-    _lib, L = _abi()
+    _lib, L = abi()
     rows, k, c, m, _ = CASES[name]
     t = make(name)
-    a = Arena()
-    x, f, wd, go = (In(t[n]) for n in ("x", "f", "wd", "go"))
+    a = Arena(DEV)
+    x, f, wd, go = (In(DEV, t[n]) for n in ("x", "f", "wd", "go"))
     gx, gf, gw = Out(a, rows * k * k), Out(a, rows * k * c, off=off), Out(a, k * c * m)
     if with_ws:
         nbytes = L.hf_xconv_depthwise_grad_workspace(rows, k, c, m)
@@ -86,19 +86,17 @@ def _run(name, with_ws, off=False):
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", list(CASES))
 def test_weight_gradient_against_fp64_and_the_atomic_entry_point(name):
-    from test_bn_abi import within
-    from test_xconv_abi import dev64
     rows, k, c, m, chunks = CASES[name]
     want, um = reference(make(name), k, c, m)
-    want, um = dev64(want), dev64(um)
+    want, um = dev64(DEV, want), dev64(DEV, um)
     bound_ws, bound = (-(-rows // chunks) + chunks + k + 2) * um, (rows + k + 2) * um
     gx, gf, gw = _run(name, True)
-    within(gw, want, bound_ws, "hf_xconv_depthwise_grad_ws." + name)
+    within(gw, want, bound_ws, "hf_xconv_depthwise_grad_ws." + name, "round")
     for _ in range(2):
         again = _run(name, True)
         assert all(torch.equal(p.view(torch.int32), q.view(torch.int32)) for p, q in zip((gx, gf, gw), again)), "two calls differ"
     ax, af, aw = _run(name, False)
-    within(aw, want, bound, "hf_xconv_depthwise_grad." + name)
+    within(aw, want, bound, "hf_xconv_depthwise_grad." + name, "round")
     assert bool(((gw - aw).abs().double() <= bound_ws + bound).all())
     assert torch.equal(gx.view(torch.int32), ax.view(torch.int32)) and torch.equal(gf.view(torch.int32), af.view(torch.int32))
     # grad_f one float past a 16-byte boundary: the same bits everywhere
@@ -107,11 +105,9 @@ def test_weight_gradient_against_fp64_and_the_atomic_entry_point(name):
 
 @pytest.mark.gpu
 def test_empty_batch_zero_fills_the_weight_gradient_and_needs_no_workspace():
-    from test_bn_abi import Arena
-    from test_xconv_abi import In, Out, _abi, call
-    _lib, L = _abi()
-    a = Arena()
-    wd = In(np.ones((8, 40, 2), np.float32))
+    _lib, L = abi()
+    a = Arena(DEV)
+    wd = In(DEV, np.ones((8, 40, 2), np.float32))
     gw = Out(a, 8 * 40 * 2)
     one = ctypes.c_void_p(wd.p.value)           # never read: there are no rows
     call(L.hf_xconv_depthwise_grad_ws(0, 8, 40, 2, one, one, wd.p, one, None, None, gw.p, None, 0, _lib.stream_ptr()), "hf_xconv_depthwise_grad_ws")
@@ -122,17 +118,15 @@ def test_empty_batch_zero_fills_the_weight_gradient_and_needs_no_workspace():
 @pytest.mark.gpu
 def test_only_the_weight_gradient_and_only_the_others():
     """grad_wd alone and grad_x / grad_f alone: the same bits as all three together; what is not asked for is not written"""
-    from test_bn_abi import Arena
-    from test_xconv_abi import In, Out, _abi, call
-    _lib, L = _abi()
+    _lib, L = abi()
     name = "ragged_3"
     rows, k, c, m, _ = CASES[name]
     t = make(name)
     gx0, gf0, gw0 = _run(name, True)
     nbytes = L.hf_xconv_depthwise_grad_workspace(rows, k, c, m)
     for want_w in (True, False):
-        a = Arena()
-        x, f, wd, go = (In(t[n]) for n in ("x", "f", "wd", "go"))
+        a = Arena(DEV)
+        x, f, wd, go = (In(DEV, t[n]) for n in ("x", "f", "wd", "go"))
         gx, gf, gw = Out(a, rows * k * k, passed=not want_w), Out(a, rows * k * c, passed=not want_w), Out(a, k * c * m, passed=want_w)
         ws = Out(a, nbytes // 4, passed=want_w)
         call(L.hf_xconv_depthwise_grad_ws(rows, k, c, m, x.p, f.p, wd.p, go.p, gx.p, gf.p, gw.p, ws.p, nbytes if want_w else 0,
@@ -140,7 +134,7 @@ def test_only_the_weight_gradient_and_only_the_others():
         a.check()
         if want_w:
             assert torch.equal(gw.view.view(torch.int32), gw0.reshape(-1).view(torch.int32))
-            assert bool((gx.view == 12345.0).all()) and bool((gf.view == 12345.0).all())
+            assert bool((gx.view == SENTINEL).all()) and bool((gf.view == SENTINEL).all())
         else:
             assert torch.equal(gx.view.view(torch.int32), gx0.view(torch.int32)) and torch.equal(gf.view.view(torch.int32), gf0.view(torch.int32))
-            assert bool((gw.view == 12345.0).all()) and bool((ws.view == 12345.0).all())
+            assert bool((gw.view == SENTINEL).all()) and bool((ws.view == SENTINEL).all())

@@ -11,7 +11,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import xconv_cases as xc  # noqa: E402
-from test_gemm_instantiations_cpu import compile_to_assembly, kernel_table  # noqa: E402
+from kernel_asm import compile_to_assembly, kernel_table  # noqa: E402
 
 
 @pytest.fixture(scope="module")
