@@ -120,6 +120,9 @@ _SIGNATURES = {
     "hf_crop_and_resize_grad": [_i, _i, _i, _i, ctypes.c_longlong, _i, _i, _vp, _vp, _vp, _vp, _vp],
     "hf_crop_and_resize_grad_ordered_workspace": [_i, _i, _i, _i, ctypes.c_longlong, _i, _i],
     "hf_crop_and_resize_grad_ordered": [_i, _i, _i, _i, ctypes.c_longlong, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
+    "hf_conv3x3_nhwc": [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _vp],
+    "hf_upconv3x3s2_nhwc": [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _vp],
+    "hf_maxpool2x2_nhwc": [_i, _i, _i, _i, _vp, _i, _i, _vp, _vp],
     "hf_fuse_concat": [ctypes.c_longlong, _i, _i, _vp, _vp, _vp, _vp, _vp],
     "hf_fuse_concat_grad": [ctypes.c_longlong, _i, _i, _vp, _vp, _vp, _vp, _vp],
     "hf_rpn_loss_workspace": [],

@@ -1,6 +1,6 @@
 """Detect from KITTI files with both trained models: python -m heterofusionrcnn_amd.detect DATASET_DIR RPN.pt RCNN.pt OUT_DIR
 [--split val] [--config rpn_multiclass] [--batch 8] [--seed 0] [--workers 8] [--score-threshold 0.1] [--handoff-rounding]
-[--host-rows] [--eval] [--precision {fp32,bf16}]
+[--host-rows] [--eval] [--precision {fp32,bf16}] [--image-branch {torch,native}]
 
 The reference's `run_inference.py` over both stages (hf/core/evaluator.py:934-1065 for the first, :300-420 and
 evaluator_utils.py:88-166 for the second), without the hand-off on disk: RPN.pt is what train_rpn --save (or a checkpoint of
@@ -17,6 +17,8 @@ neither for the disk nor for the text.  --host-rows keeps inference.write_frame_
 the writer: the parity anchor, byte-identical to rcnn_data.run_rcnn_from_handoff on an export with the same seed and batch.
 --precision bf16 sends the wide dense layers of both stages to the bf16 matrix-core kernel (mlp.inference_precision; the heads that
 are decoded into scores and boxes stay fp32); the default, fp32, is the route described above, bit for bit.
+--image-branch native runs both VGG pyramids (the RPN's and the RCNN's) on the channel-last kernels of csrc/conv_nhwc.hip
+(image_pyramid.image_branch); the default, torch, leaves them on the vendor library.
 """
 import argparse
 import contextlib
@@ -27,6 +29,7 @@ import numpy as np
 import torch
 
 from . import checkpoint as ckpt_mod
+from . import image_pyramid
 from . import kitti_data as KD
 from . import mlp
 from .export_rpn import WriteBack, load_rpn, proposals_from_files
@@ -72,10 +75,11 @@ def _write_rows(out_dir, names, counts, host, event, classes):
 @torch.no_grad()
 def detect(dataset_dir, rpn, rcnn, out_dir, split="val", config="rpn_multiclass", batch=8, seed=0, workers=8, score_threshold=0.1,
            handoff_rounding=False, host_rows=False, img_conv=None, num_points=16384, img_hw=(360, 1200), pre_nms_size=9000,
-           nms_thresh=0.8, post_nms_size=100, classes=CLASSES, precision="fp32"):
-    """rpn / rcnn: see load_models.  precision: mlp.inference_precision for the duration of the call.
+           nms_thresh=0.8, post_nms_size=100, classes=CLASSES, precision="fp32", image_branch="torch"):
+    """rpn / rcnn: see load_models.  precision: mlp.inference_precision for the duration of the call; image_branch:
+    image_pyramid.image_branch for the same duration, over both pyramids.
     -> {name: rows written} for every frame of the split"""
-    scope = mlp.inference_precision(precision)
+    scope, img_scope = mlp.inference_precision(precision), image_pyramid.image_branch(image_branch)
     net, second = load_models(rpn, rcnn, config, img_conv)
     modes = (net.training, second.training)
     net.eval()
@@ -86,7 +90,7 @@ def detect(dataset_dir, rpn, rcnn, out_dir, split="val", config="rpn_multiclass"
                                    (pre_nms_size, nms_thresh, post_nms_size), classes, always_image=True)
     written = {}
     try:
-        with scope, contextlib.closing(batches), contextlib.closing(WriteBack()) as back:
+        with scope, img_scope, contextlib.closing(batches), contextlib.closing(WriteBack()) as back:
             for frames, meta, xyz, inten, image, out in batches:
                 h = handoff_in_memory(out, xyz, inten, handoff_rounding)
                 dets, _ = second.detect(h["xyz"], h["rpn_fts"], h["intensity"], h["fg_mask"], h["proposals"], image, meta["calib"])
@@ -124,13 +128,16 @@ def build_parser():
     ap.add_argument("--eval", action="store_true", help="then evaluate OUT_DIR against DATASET_DIR/label_2 (kitti_eval)")
     ap.add_argument("--precision", choices=mlp.PRECISIONS, default="fp32",
                     help="bf16: the wide dense layers of both stages on the bf16 matrix cores (fp32 accumulation, fp32 output heads)")
+    ap.add_argument("--image-branch", choices=image_pyramid.IMAGE_BRANCHES, default="torch",
+                    help="native: both VGG pyramids on this package's channel-last convolution kernels instead of the vendor library")
     return ap
 
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
     written = detect(args.dataset_dir, args.rpn, args.rcnn, args.out_dir, args.split, args.config, args.batch, args.seed,
-                     args.workers, args.score_threshold, args.handoff_rounding, args.host_rows, precision=args.precision)
+                     args.workers, args.score_threshold, args.handoff_rounding, args.host_rows, precision=args.precision,
+                     image_branch=args.image_branch)
     print("done: %d frames, %d rows" % (len(written), sum(written.values())))
     if args.eval:
         from . import kitti_eval

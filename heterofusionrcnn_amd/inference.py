@@ -5,7 +5,8 @@ BASELINE config 5 "Two-stage RPN -> tf_cropping -> RCNN inference on KITTI val, 
                     360 x 1200 and mean-subtracted          hf/datasets/kitti/kitti_dataset.py:300-410, img_feature_extractor.py:8-30
   image branch      ImgVggPyr: the VGG pyramid of hf/core/feature_extractors/img_vgg_pyramid.py:31-175 as a plain torch module
                     (a stock convolutional network on MIOpen, no custom op; OUTSIDE the hot path: bench.py's step takes its
-                    output as an input).  Here so that the flow runs from files to files.
+                    output as an input).  Here so that the flow runs from files to files.  In eval mode it can run on this
+                    package's channel-last kernels instead: image_pyramid.image_branch("native"), opt-in
   detection         two_stage.TwoStageDetector (rank-strided frame shards, geometry prefetched one batch ahead)
   result writing    score threshold (eval_config kitti_score_threshold 0.1), 3-D boxes projected into the image, boxes that
                     leave the image or cover more than 80 % of it dropped, the rest truncated, KITTI label lines with alpha
@@ -23,7 +24,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import box_codec, dp, kitti_io
+from . import box_codec, dp, image_pyramid, kitti_io
 
 IMAGE_MEAN = (92.8403, 97.7996, 93.5843)        # img_feature_extractor.py:9-11 (R, G, B)
 CLASSES = ("Car", "Pedestrian", "Cyclist")      # rpn_multiclass.config dataset_config.classes
@@ -66,6 +67,13 @@ class ImgVggPyr(nn.Module):
         self.out_channel = c1
 
     def forward(self, image):
+        if image_pyramid.image_branch_name() == "native" and image.is_cuda and image.dtype == torch.float32:
+            # opt-in (image_pyramid.image_branch): eval mode on this package's channel-last kernels.  Never a silent return to the
+            # route below: a caller that asked for the native route and cannot have it is told so
+            if self.training or torch.is_grad_enabled():
+                raise RuntimeError("image_branch('native') is inference only: the module must be in eval mode with autograd off "
+                                   "(training=%s, grad enabled=%s)" % (self.training, torch.is_grad_enabled()))
+            return image_pyramid.forward_native(self, image)
         x = image.permute(0, 3, 1, 2)
         # preprocess_input; on the device the mean is uploaded once, so that a captured train step makes no host copy
         mean = box_codec.const_f32(x.device, IMAGE_MEAN) if x.is_cuda and x.dtype == torch.float32 else \
@@ -206,9 +214,11 @@ def write_result_rows(path, rows, classes=CLASSES):
 
 
 @torch.no_grad()
-def run_kitti_inference(detector, img_net, dataset_dir, names, out_dir, ctx, frames_per_batch=8, seed=0, score_threshold=0.1):
+def run_kitti_inference(detector, img_net, dataset_dir, names, out_dir, ctx, frames_per_batch=8, seed=0, score_threshold=0.1,
+                        image_branch="torch"):
     """The file-to-file flow of BASELINE config 5 on this rank's shard of `names` (rank-strided, dp.shard_frames): load, image
-    branch, two stages, result files <out_dir>/<name>.txt.  Returns {name: number of boxes written} gathered on rank 0."""
+    branch (image_branch: image_pyramid.image_branch for the pyramid's calls), two stages, result files <out_dir>/<name>.txt.
+    Returns {name: number of boxes written} gathered on rank 0."""
     from .pipeline import GeometryPrefetcher
     os.makedirs(out_dir, exist_ok=True)
     mine = [names[i] for i in dp.shard_frames(len(names), ctx.rank, ctx.world)]
@@ -233,7 +243,8 @@ def run_kitti_inference(detector, img_net, dataset_dir, names, out_dir, ctx, fra
             staged.append(load(batches[bi + 2]))
             if prefetch is not None:
                 prefetch.submit(staged[-1][1]["xyz"])
-        img_fts = img_net(dev["image"])
+        with image_pyramid.image_branch(image_branch):
+            img_fts = img_net(dev["image"])
         dets = detector(dev["xyz"], dev["intensity"], img_fts, dev["calib"], geometry=geo)
         for f, det in zip(frames, dets):
             written[f["name"]] = write_frame_results(os.path.join(out_dir, f["name"] + ".txt"), det, f["calib_orig"], f["image_size"],

@@ -33,6 +33,7 @@ import torch
 
 from . import _lib
 from . import checkpoint as ckpt_mod
+from . import image_pyramid
 from . import kitti_data as KD
 from ._lib import check, dev_tensor, ptr, require, stream_ptr
 from .inference import CLASSES
@@ -181,8 +182,10 @@ def global_step_of(path):
 # ------------------------------------------------------------------------------------------------ the RPN
 @torch.no_grad()
 def validate_rpn(dataset_dir, model, split="val", config="rpn_multiclass", batch=8, seed=0, workers=8, img_conv=None,
-                 num_points=16384, img_hw=(360, 1200), pre_nms_size=9000, nms_thresh=0.8, post_nms_size=100, classes=CLASSES):
-    """model: whatever export_rpn.load_rpn accepts (a --save file, a checkpoint file, a state_dict, a built model).  The frames
+                 num_points=16384, img_hw=(360, 1200), pre_nms_size=9000, nms_thresh=0.8, post_nms_size=100, classes=CLASSES,
+                 image_branch="torch"):
+    """image_branch: image_pyramid.image_branch for the pyramid's calls.
+    model: whatever export_rpn.load_rpn accepts (a --save file, a checkpoint file, a state_dict, a built model).  The frames
     of the split are read once, in order, without augmentation (export_rpn.proposals_from_files: the point samples of
     export_rpn.export at the same seed); ONE eval-mode forward per batch (RpnModel.propose) feeds the fused loss forward
     (labels from kitti_data.point_labels), hf_argmax_accuracy and hf_proposal_stats.
@@ -208,7 +211,7 @@ def validate_rpn(dataset_dir, model, split="val", config="rpn_multiclass", batch
     batches = proposals_from_files(net, dataset_dir, names, batch, workers, seed, num_points, img_hw,
                                    (pre_nms_size, nms_thresh, post_nms_size), classes)
     try:
-        with contextlib.closing(batches):
+        with image_pyramid.image_branch(image_branch), contextlib.closing(batches):
             for bi, (frames, meta, xyz, inten, _, out) in enumerate(batches):
                 b, p = xyz.shape[:2]
                 off = len(seen)
@@ -267,8 +270,9 @@ def rcnn_val_forward(trainer, bt):
 
 
 @torch.no_grad()
-def validate_rcnn(dataset_dir, handoff_dir, model, split="val", batch=2, workers=8, img_conv=None):
-    """model: a train_rcnn --save file, a checkpoint file, a state_dict or a built rcnn_train.RcnnTrainer.  Frames with a label of
+def validate_rcnn(dataset_dir, handoff_dir, model, split="val", batch=2, workers=8, img_conv=None, image_branch="torch"):
+    """image_branch: image_pyramid.image_branch for the pyramid's calls.
+    model: a train_rcnn --save file, a checkpoint file, a state_dict or a built rcnn_train.RcnnTrainer.  Frames with a label of
     the classes, once, in order, without augmentation (rcnn_data.KittiRcnnBatches(mode="val")); per batch rcnn_val_forward and
     hf_argmax_accuracy over the B m RoIs, one group per frame (padded proposal rows count as background RoIs).
     -> {"names", "frames": {name: {correct, rois}}, "rows", "batch_losses" (nb, 4) [box_classification, bin_classification,
@@ -290,7 +294,8 @@ def validate_rcnn(dataset_dir, handoff_dir, model, split="val", batch=2, workers
         batch_frames, seen = [], []
         for bi, bt in enumerate(data):
             b, off = len(bt.names), len(seen)
-            parts, cls_logits, target = rcnn_val_forward(trainer, bt)
+            with image_pyramid.image_branch(image_branch):
+                parts, cls_logits, target = rcnn_val_forward(trainer, bt)
             losses[bi] = torch.stack([parts[k] for k in RCNN_LOSSES])
             argmax_accuracy(cls_logits, target, b, correct[off:off + b])
             seen += list(bt.names)
@@ -327,6 +332,8 @@ def build_parser():
         if stage == "rpn":
             sp.add_argument("--config", choices=CONFIGS, default="rpn_multiclass")
             sp.add_argument("--seed", type=int, default=0, help="seed of the point sampling")
+        sp.add_argument("--image-branch", choices=image_pyramid.IMAGE_BRANCHES, default="torch",
+                        help="native: the VGG pyramid on this package's channel-last convolution kernels instead of the vendor library")
     return ap
 
 
@@ -343,9 +350,11 @@ def main(argv=None):
         todo = [(global_step_of(args.model), args.model)]
     for step, path in todo:
         if args.stage == "rpn":
-            res = validate_rpn(args.dataset_dir, path, args.split, args.config, args.batch, args.seed, args.workers)
+            res = validate_rpn(args.dataset_dir, path, args.split, args.config, args.batch, args.seed, args.workers,
+                               image_branch=args.image_branch)
         else:
-            res = validate_rcnn(args.dataset_dir, args.handoff_dir, path, args.split, args.batch, args.workers)
+            res = validate_rcnn(args.dataset_dir, args.handoff_dir, path, args.split, args.batch, args.workers,
+                                image_branch=args.image_branch)
         for line in summary_lines(args.stage, step, res["totals"]):
             print(line)
         if args.out:

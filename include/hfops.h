@@ -549,6 +549,28 @@ int hf_crop_and_resize(int b, int h, int w, int c, long long n, int crop_h, int 
                        const float *boxes_yxyx, const int *box_ind, float extrapolation, float *out, hf_stream_t stream);
 int hf_crop_and_resize_grad(int b, int h, int w, int c, long long n, int crop_h, int crop_w, const float *grad_out,
                             const float *boxes_yxyx, const int *box_ind, float *grad_img, hf_stream_t stream);
+/* The image pyramid's inference kernels (inference.ImgVggPyr in eval mode, image_pyramid.py), csrc/conv_nhwc.hip.  All tensors
+ * fp32, dense channel-last, passed as rows of pixels; row and byte offsets are 64-bit, b*h*w <= INT_MAX (INT_MAX / 4 for the
+ * up-convolution).
+ * hf_conv3x3_nhwc: x (b,h,w,cin); wt (9,cout,cin), tap t = 3 ky + kx, each tap an (N, K) matrix.  z[p,:] = sum over t of
+ * x'[src(p,t),:] wt[t]^T with src = (oy + ky - 1, ox + kx - 1) in the same image; a tap outside the image adds zero and is not
+ * read.  in_sub: cin floats or NULL; x' = x - in_sub on the elements inside the image only, the padding stays zero.  Epilogue:
+ * y = z * scale + shift per output channel (NULL: 1 / 0; multiply and add rounded separately), then max(., 0) if `relu`; y goes to
+ * columns [y_col, y_col + cout) of rows y_stride wide, one row per pixel, the other columns are not touched.  The MFMA is
+ * v_mfma_f32_32x32x2_f32 over the flattened (tap, channel) axis in a fixed order: two calls give the same bits.
+ * hf_upconv3x3s2_nhwc: ConvTranspose2d(3, stride 2, padding 1, output_padding 1): x (b,h,w,cin) -> y (b,2h,2w,cout) with the same
+ * epilogue and column slice; wt[3 ky + kx][co][ci] = the module's weight[ci,co,ky,kx].  Input pixel iy feeds output row
+ * 2 iy - 1 + ky (the same in x): an even row takes ky = 1, an odd row ky = 0 from iy = (oy+1)/2 if < h and ky = 2 from (oy-1)/2.
+ * One launch, one pass per output parity class over its 1, 2, 2 or 4 taps; no MFMA work for a tap that does not exist.
+ * hf_maxpool2x2_nhwc: y (b,h/2,w/2,c) dense = the maximum over each 2x2 window (a NaN wins, as torch) of columns
+ * [x_col, x_col + c) of x's rows, x_stride wide; a last odd row or column is dropped; h or w == 1 launches nothing.
+ * All three: no workspace, no allocation, no host round trip, capturable.  HF_EINVAL before any HIP call: b, h, w, cin (c) < 1,
+ * cout outside 1..256, a negative column, a slice that does not fit the stride, b*h*w beyond the limit, a NULL x, wt or y. */
+int hf_conv3x3_nhwc(int b, int h, int w, int cin, int cout, const float *x, const float *in_sub, const float *wt,
+                    const float *scale, const float *shift, int relu, float *y, int y_stride, int y_col, hf_stream_t stream);
+int hf_upconv3x3s2_nhwc(int b, int h, int w, int cin, int cout, const float *x, const float *wt, const float *scale,
+                        const float *shift, int relu, float *y, int y_stride, int y_col, hf_stream_t stream);
+int hf_maxpool2x2_nhwc(int b, int h, int w, int c, const float *x, int x_stride, int x_col, float *y, hf_stream_t stream);
 /* The 'concat' fusion of the RPN / RCNN with its path drop (hf/core/models/rpn_model.py:515-546, rcnn_model.py:560-590):
  * out (rows, c1+c2) = [a * masks[0] | b * masks[1]]; masks = two floats ON THE DEVICE (this step's path-drop decision,
  * create_path_drop_masks, rpn_model.py:1130-1193) or NULL for (1, 1).  _grad: grad_a = grad_out[:, :c1] * masks[0],
