@@ -123,6 +123,12 @@ _SIGNATURES = {
     "hf_conv3x3_nhwc": [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _vp],
     "hf_upconv3x3s2_nhwc": [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _vp],
     "hf_maxpool2x2_nhwc": [_i, _i, _i, _i, _vp, _i, _i, _vp, _vp],
+    "hf_conv3x3s2_nhwc": [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _vp],
+    "hf_conv3x3_nhwc_wgrad_workspace": [_i, _i, _i, _i, _i],
+    "hf_conv3x3_nhwc_wgrad": [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
+    "hf_upconv3x3s2_nhwc_wgrad_workspace": [_i, _i, _i, _i, _i],
+    "hf_upconv3x3s2_nhwc_wgrad": [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp],
+    "hf_maxpool2x2_nhwc_bwd": [_i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _i, _i, _i, _vp],
     "hf_fuse_concat": [ctypes.c_longlong, _i, _i, _vp, _vp, _vp, _vp, _vp],
     "hf_fuse_concat_grad": [ctypes.c_longlong, _i, _i, _vp, _vp, _vp, _vp, _vp],
     "hf_rpn_loss_workspace": [],
@@ -202,6 +208,8 @@ _RESTYPES = {
     "hf_rpn_batch_image_workspace": _sz,
     "hf_project_gather_grad_ordered_workspace": _sz,
     "hf_crop_and_resize_grad_ordered_workspace": _sz,
+    "hf_conv3x3_nhwc_wgrad_workspace": _sz,
+    "hf_upconv3x3s2_nhwc_wgrad_workspace": _sz,
     "hf_version": ctypes.c_char_p,
     "hf_strerror": ctypes.c_char_p,
 }

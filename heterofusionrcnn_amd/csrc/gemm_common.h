@@ -2,7 +2,7 @@
 // pieces of the forward form (LDS layout, staging geometry, the MFMA stage fwd_mfma_stage, the D-register row map, the column-sum
 // epilogue col_sums_store), the wgrad-form chunk loop (wgrad_tile_loop), and the launch plans that both the launchers and the
 // workspace queries must agree on.  fwd_mfma_stage and wgrad_tile_loop hold the only MFMA calls of those sources.  The three wgrad
-// kernels are an operand source handed to wgrad_tile_loop.  The five forward kernels keep their own loop over tiles and stages
+// kernels are an operand source handed to wgrad_tile_loop (conv_nhwc.hip's, which masks its G operand, to wgrad_tile_loop_staged).  The five forward kernels keep their own loop over tiles and stages
 // around fwd_mfma_stage: through one shared forward loop (fetch / stage functors) their register allocation moved by up to 45
 // VGPRs, scratch grew in four instantiations, and the lifting kernels ran 3-8 % slower on the benchmark's shapes
 // (profiles/gemm_refactor_ab.md, last section, which also says why a tile's accumulator zeroing stays written out in each).
@@ -146,13 +146,11 @@ struct WgradTile {
     }
 };
 
-// The chunk loop.  fetch(rt) issues the loads of the stage at row rt (G into gr[]); stage_x(p, rt) gives the four floats to store in
-// Xs for pass p from what fetch loaded -- evaluated when the stage is stored, so the loads stay in flight across the MFMA loop.
-// gr[] is the kernel's own array, which fetch overwrites through its captures: the loop only reads it, after each fetch.
-template <int WM, int WN, class Fetch, class StageX>
-__device__ __forceinline__ void wgrad_tile_loop(typename WgradTile<WM, WN>::Lds &lds, const WgradTile<WM, WN> &q, int cout, int cin,
-                                                float *__restrict__ partial,
-                                                const float4 (&gr)[WgradTile<WM, WN>::GPASS], Fetch fetch, StageX stage_x)
+// The chunk loop.  fetch(rt) issues the loads of the stage at row rt; stage_g(p) and stage_x(p, rt) give the four floats to store in
+// Gs and Xs for pass p from what fetch loaded -- evaluated when the stage is stored, so the loads stay in flight across the MFMA loop.
+template <int WM, int WN, class Fetch, class StageG, class StageX>
+__device__ __forceinline__ void wgrad_tile_loop_staged(typename WgradTile<WM, WN>::Lds &lds, const WgradTile<WM, WN> &q, int cout, int cin,
+                                                       float *__restrict__ partial, Fetch fetch, StageG stage_g, StageX stage_x)
 {
     using T = WgradTile<WM, WN>;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
@@ -169,7 +167,7 @@ __device__ __forceinline__ void wgrad_tile_loop(typename WgradTile<WM, WN>::Lds 
     for (long long rt = q.r0; rt < q.r1; rt += kGemmRowsPerStage) {
 #pragma unroll
         for (int p = 0; p < T::GPASS; ++p)
-            *reinterpret_cast<float4 *>(&lds.Gs[(q.grow + p * T::GROWS) * T::GS + (t % T::GC4) * 4]) = gr[p];
+            *reinterpret_cast<float4 *>(&lds.Gs[(q.grow + p * T::GROWS) * T::GS + (t % T::GC4) * 4]) = stage_g(p);
 #pragma unroll
         for (int p = 0; p < T::XPASS; ++p)
             *reinterpret_cast<float4 *>(&lds.Xs[(q.xrow + p * T::XROWS) * T::XS + (t % T::XC4) * 4]) = stage_x(p, rt);
@@ -212,6 +210,16 @@ __device__ __forceinline__ void wgrad_tile_loop(typename WgradTile<WM, WN>::Lds 
                 if (n < cout && k < cin) out[static_cast<size_t>(n) * cin + k] = acc[i][j][g];
             }
         }
+}
+
+// The loop with G stored as loaded: gr[] is the kernel's own array, which fetch overwrites through its captures; the loop only reads
+// it, after each fetch.
+template <int WM, int WN, class Fetch, class StageX>
+__device__ __forceinline__ void wgrad_tile_loop(typename WgradTile<WM, WN>::Lds &lds, const WgradTile<WM, WN> &q, int cout, int cin,
+                                                float *__restrict__ partial,
+                                                const float4 (&gr)[WgradTile<WM, WN>::GPASS], Fetch fetch, StageX stage_x)
+{
+    wgrad_tile_loop_staged<WM, WN>(lds, q, cout, cin, partial, fetch, [&](int p) { return gr[p]; }, stage_x);
 }
 
 struct WgradPlan {

@@ -67,6 +67,10 @@ class ImgVggPyr(nn.Module):
         self.out_channel = c1
 
     def forward(self, image):
+        if image_pyramid.train_branch_name() == "native" and self.training and torch.is_grad_enabled() and image.is_cuda \
+                and image.dtype == torch.float32:
+            # opt-in (image_pyramid.train_branch): the training direction on this package's kernels, one autograd node
+            return image_pyramid.forward_train(self, image)
         if image_pyramid.image_branch_name() == "native" and image.is_cuda and image.dtype == torch.float32:
             # opt-in (image_pyramid.image_branch): eval mode on this package's channel-last kernels.  Never a silent return to the
             # route below: a caller that asked for the native route and cannot have it is told so

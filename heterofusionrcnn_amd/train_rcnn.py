@@ -13,6 +13,7 @@ import argparse
 import sys
 
 from . import checkpoint as ckpt_mod
+from . import image_pyramid
 from . import train_loop
 from .determinism import IMAGE_CONFIGS_REFUSED, as_level, level, refuse_image_config
 from .inference import ImgVggPyr
@@ -63,17 +64,19 @@ class RcnnStage:
 def train(dataset_dir, handoff_dir, split="train", steps=100, batch=2, seed=0, save=None, log_every=10, workers=8, lr=1e-3,
           graph=True, img_conv=None, aug_list=None, log=print, clip_norm=0.0, lr_decay=None, tf_epsilon=False, check_numerics=False,
           checkpoint_dir=None, checkpoint_every=ckpt_mod.CHECKPOINT_INTERVAL, max_checkpoints=None, resume=False,
-          precision="fp32", deterministic=False):
+          precision="fp32", image_train_branch="torch", deterministic=False):
     """-> (list of the per-step losses of this run, read at the end; the trainer)
-    The train-op, checkpoint, resume, precision and deterministic keywords are train_rpn.train's (`steps` is the final global step when resuming);
+    The train-op, checkpoint, resume, precision, image_train_branch and deterministic keywords are train_rpn.train's (`steps` is the final global step when resuming);
     the RCNN fuses the image, so deterministic=True is refused before anything is built and deterministic="image" is the level it trains at."""
     if (as_level(deterministic) or level()) is True:
         refuse_image_config("train_rcnn")
     stage = RcnnStage(img_conv, dataset_dir=dataset_dir, handoff_dir=handoff_dir, split=split, batch=batch, seed=seed, aug_list=aug_list,
                       workers=workers)
-    return train_loop.run(stage, steps, seed, save, log_every, lr, graph, log, clip_norm, lr_decay, tf_epsilon, check_numerics,
-                          checkpoint_dir, checkpoint_every, max_checkpoints, resume, precision,
-                          deterministic=deterministic)
+    # the scope holds for the whole run: the capture of the step and every eager step read it where ImgVggPyr.forward runs
+    with image_pyramid.train_branch(image_train_branch):
+        return train_loop.run(stage, steps, seed, save, log_every, lr, graph, log, clip_norm, lr_decay, tf_epsilon, check_numerics,
+                              checkpoint_dir, checkpoint_every, max_checkpoints, resume, precision,
+                              deterministic=deterministic)
 
 
 def build_parser():
@@ -84,6 +87,9 @@ def build_parser():
     ap.add_argument("handoff_dir")
     ap.add_argument("--batch", type=int, default=2, help="frames per step (rcnn_multiclass.config:218)")
     ckpt_mod.add_train_op_arguments(ap, "rcnn_multiclass.config")
+    ap.add_argument("--image-train-branch", choices=image_pyramid.TRAIN_BRANCHES, default="torch",
+                    help="the image pyramid's forward and backward: torch (the vendor library) or native (this package's NHWC "
+                         "fp32-MFMA kernels, no atomics; allowed at every --deterministic level)")
     return ap
 
 
@@ -93,7 +99,8 @@ def main(argv=None):
     if args.deterministic and not args.deterministic_image:
         ap.error("--deterministic: " + IMAGE_CONFIGS_REFUSED)
     losses, _ = train(args.dataset_dir, args.handoff_dir, args.split, args.steps, args.batch, args.seed, args.save, args.log_every,
-                      args.workers, graph=not args.no_graph, deterministic=ckpt_mod.deterministic_level(args), **ckpt_mod.train_op_kwargs(args))
+                      args.workers, graph=not args.no_graph, deterministic=ckpt_mod.deterministic_level(args), image_train_branch=args.image_train_branch,
+                       **ckpt_mod.train_op_kwargs(args))
     if losses:
         print("done: %d steps, first loss %.5f, last loss %.5f" % (len(losses), losses[0], losses[-1]))
     else:

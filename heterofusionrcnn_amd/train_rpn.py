@@ -15,6 +15,7 @@ import math
 import sys
 
 from . import checkpoint as ckpt_mod
+from . import image_pyramid
 from . import rpn as rpn_mod
 from . import train_loop
 from .determinism import IMAGE_CONFIGS_REFUSED, as_level, level, refuse_image_config
@@ -77,13 +78,15 @@ class RpnStage:
 def train(dataset_dir, split="train", steps=100, batch=8, config="rpn_multiclass", seed=0, save=None, log_every=10, workers=8,
           lr=1e-3, graph=True, img_conv=None, num_points=16384, log=print, clip_norm=0.0, lr_decay=None, tf_epsilon=False,
           check_numerics=False, checkpoint_dir=None, checkpoint_every=ckpt_mod.CHECKPOINT_INTERVAL, max_checkpoints=None, resume=False,
-          precision="fp32", deterministic=False):
+          precision="fp32", image_train_branch="torch", deterministic=False):
     """-> (list of the per-step losses of this run, floats read at the end; the loader status)
     clip_norm / lr_decay / tf_epsilon: optim.MultiTensorAdam's (ckpt_mod.reference_train_op() holds the reference's values);
     check_numerics: a NaN / Inf loss raises FloatingPointError at the next log point (always before a checkpoint is written);
     checkpoint_dir: a checkpoint every checkpoint_every global steps, the newest max_checkpoints kept; resume: continue from the
     newest checkpoint there, `steps` then being the final global step.  precision "bf16": the wide dense layers train on the bf16
     matrix cores (the whole call runs under mlp.training_precision); a checkpoint resumes only at the precision it was written at.
+    image_train_branch: "native" trains the image pyramid on this package's kernels (image_pyramid.train_branch; no atomics, allowed at
+    every deterministic level); "torch" is the stock module on the vendor library.
     deterministic: True or "image", the run is inside determinism.deterministic at that level (bit-reproducible: train_loop.run).  True
     trains rpn_multiclass_points only: the config that fuses the image is refused before anything is built.  "image" trains every
     config, the image-feature gradients in their ordered form."""
@@ -91,9 +94,11 @@ def train(dataset_dir, split="train", steps=100, batch=8, config="rpn_multiclass
         refuse_image_config("train_rpn, config rpn_multiclass")
     stage = RpnStage(config, img_conv, dataset_dir=dataset_dir, split=split, classes=CLASSES, batch=batch, num_points=num_points,
                      seed=seed, workers=workers)
-    return train_loop.run(stage, steps, seed, save, log_every, lr, graph, log, clip_norm, lr_decay, tf_epsilon, check_numerics,
-                          checkpoint_dir, checkpoint_every, max_checkpoints, resume, precision,
-                          deterministic=deterministic)
+    # the scope holds for the whole run: the capture of the step and every eager step read it where ImgVggPyr.forward runs
+    with image_pyramid.train_branch(image_train_branch):
+        return train_loop.run(stage, steps, seed, save, log_every, lr, graph, log, clip_norm, lr_decay, tf_epsilon, check_numerics,
+                              checkpoint_dir, checkpoint_every, max_checkpoints, resume, precision,
+                              deterministic=deterministic)
 
 
 def build_parser():
@@ -103,6 +108,9 @@ def build_parser():
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--config", choices=CONFIGS, default="rpn_multiclass")
     ckpt_mod.add_train_op_arguments(ap, "rpn_multiclass.config")
+    ap.add_argument("--image-train-branch", choices=image_pyramid.TRAIN_BRANCHES, default="torch",
+                    help="the image pyramid's forward and backward: torch (the vendor library) or native (this package's NHWC "
+                         "fp32-MFMA kernels, no atomics; allowed at every --deterministic level)")
     return ap
 
 
@@ -112,7 +120,8 @@ def main(argv=None):
     if args.deterministic and not args.deterministic_image and args.config == "rpn_multiclass":
         ap.error("--deterministic with --config rpn_multiclass: " + IMAGE_CONFIGS_REFUSED)
     losses, st = train(args.dataset_dir, args.split, args.steps, args.batch, args.config, args.seed, args.save, args.log_every,
-                       args.workers, graph=not args.no_graph, deterministic=ckpt_mod.deterministic_level(args), **ckpt_mod.train_op_kwargs(args))
+                       args.workers, graph=not args.no_graph, deterministic=ckpt_mod.deterministic_level(args), image_train_branch=args.image_train_branch,
+                       **ckpt_mod.train_op_kwargs(args))
     if losses:
         print("done: %d steps, first loss %.5f, last loss %.5f, status %s" % (len(losses), losses[0], losses[-1], st))
     else:

@@ -571,6 +571,39 @@ int hf_conv3x3_nhwc(int b, int h, int w, int cin, int cout, const float *x, cons
 int hf_upconv3x3s2_nhwc(int b, int h, int w, int cin, int cout, const float *x, const float *wt, const float *scale,
                         const float *shift, int relu, float *y, int y_stride, int y_col, hf_stream_t stream);
 int hf_maxpool2x2_nhwc(int b, int h, int w, int c, const float *x, int x_stride, int x_col, float *y, hf_stream_t stream);
+/* The image pyramid's training direction (image_pyramid.forward_train), csrc/conv_nhwc.hip.  Same tensors, same limits, same
+ * argument checks as the three entry points above (HF_EINVAL before any HIP call); no allocation, no host round trip, no
+ * floating-point atomic, capturable; two calls on the same inputs give the same bits.
+ * hf_conv3x3s2_nhwc: the adjoint of hf_upconv3x3s2_nhwc and its input gradient.  x (b,2h,2w,cin) -> y (b,h,w,cout): output pixel
+ * (oy,ox) sums x[2 oy - 1 + ky, 2 ox - 1 + kx,:] wt[3 ky + kx]^T over the nine taps, zero outside the image; wt (9,cout,cin);
+ * epilogue and column slice as hf_conv3x3_nhwc; b*h*w <= INT_MAX / 4.  With wt[t][ci][co] = the up-convolution's wt[t][co][ci] and
+ * x = dz it returns that layer's dx.  (The plain convolution's input gradient is hf_conv3x3_nhwc itself on dz with
+ * w[t][ci][co] = wt[8 - t][co][ci].)
+ * hf_conv3x3_nhwc_wgrad: x (b,h,w,cin), dz (b,h,w,cout) -> dwt (9,cout,cin), dwt[t][co][ci] = sum over pixels p of
+ * dz[p][co] x'[p + tap_t][ci], t = 3 ky + kx, tap_t = (ky - 1, kx - 1); x' = x - in_sub (cin floats or NULL) inside the image and zero
+ * in the padding, the forward's rule.  fp32 MFMA over the pixel rows, which are cut into chunks of at least 256 rows: the chunks'
+ * partial matrices go to the workspace and are added in ascending order; a single chunk writes dwt itself and needs no
+ * workspace.  cout <= 256, cin <= 512, b*h*w <= INT_MAX.
+ * hf_upconv3x3s2_nhwc_wgrad: x (b,h,w,cin), dz (b,2h,2w,cout) -> dwt (9,cout,cin), dwt[t][co][ci] = sum over (iy,ix) of
+ * dz[2 iy - 1 + ky, 2 ix - 1 + kx][co] x[iy,ix][ci] where that output pixel exists.  The same kernel with the stride on the dz side;
+ * b*h*w <= INT_MAX / 4.
+ * hf_*_wgrad_workspace: the bytes either needs (0 for a single chunk, and 0 outside the contract); HF_EINVAL for a missing or
+ * short workspace.
+ * hf_maxpool2x2_nhwc_bwd: x as hf_maxpool2x2_nhwc read it (columns [x_col, x_col + c) of rows x_stride wide), dpooled
+ * (b,h/2,w/2,c) dense -> columns [dx_col, dx_col + c) of dx's rows, dx_stride wide.  The argmax of every window is recomputed from
+ * x with the forward's rule: a strictly greater value or a NaN replaces the maximum, so the first maximum wins a tie.  accumulate =
+ * 0: every pixel of the slice is written, dpooled at the argmax, zero elsewhere, zero in a last odd row or column.  accumulate = 1:
+ * the same values are added (one fp32 add) to the pixels of whole windows; nothing else is touched. */
+int hf_conv3x3s2_nhwc(int b, int h, int w, int cin, int cout, const float *x, const float *wt, const float *scale,
+                      const float *shift, int relu, float *y, int y_stride, int y_col, hf_stream_t stream);
+size_t hf_conv3x3_nhwc_wgrad_workspace(int b, int h, int w, int cin, int cout);
+int hf_conv3x3_nhwc_wgrad(int b, int h, int w, int cin, int cout, const float *x, const float *in_sub, const float *dz,
+                          float *dwt, void *workspace, size_t workspace_bytes, hf_stream_t stream);
+size_t hf_upconv3x3s2_nhwc_wgrad_workspace(int b, int h, int w, int cin, int cout);
+int hf_upconv3x3s2_nhwc_wgrad(int b, int h, int w, int cin, int cout, const float *x, const float *dz, float *dwt,
+                              void *workspace, size_t workspace_bytes, hf_stream_t stream);
+int hf_maxpool2x2_nhwc_bwd(int b, int h, int w, int c, const float *x, int x_stride, int x_col, const float *dpooled, float *dx,
+                           int dx_stride, int dx_col, int accumulate, hf_stream_t stream);
 /* The 'concat' fusion of the RPN / RCNN with its path drop (hf/core/models/rpn_model.py:515-546, rcnn_model.py:560-590):
  * out (rows, c1+c2) = [a * masks[0] | b * masks[1]]; masks = two floats ON THE DEVICE (this step's path-drop decision,
  * create_path_drop_masks, rpn_model.py:1130-1193) or NULL for (1, 1).  _grad: grad_a = grad_out[:, :c1] * masks[0],
