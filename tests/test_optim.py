@@ -131,6 +131,67 @@ def test_multi_tensor_adam_gradients_at_new_addresses_every_step():
         np.testing.assert_allclose(pa.detach().cpu().numpy(), pb.detach().cpu().numpy(), rtol=2e-5, atol=2e-6)
 
 
+@pytest.mark.gpu
+def test_multi_tensor_adam_on_flat_gradients_off_the_16_byte_grid():
+    """the train step's layout: the gradients are views of one graph_step.FlatGrads buffer, packed back to back, so most of them start
+    4, 8 or 12 bytes past a 16-byte boundary and the update takes its element-by-element branch.  Against torch.optim.Adam (same
+    placement of epsilon), then with clipping and the smooth schedule against the fp64 restatement of TensorFlow's train op"""
+    from heterofusionrcnn_amd.graph_step import FlatGrads
+    from heterofusionrcnn_amd.optim import MultiTensorAdam
+    steps = 6
+
+    def gradients(seed):
+        gen = torch.Generator().manual_seed(seed)
+        return [[torch.randn(s, generator=gen) * (10.0 ** (step % 3 - 1)) for s in SHAPES] for step in range(steps)]
+
+    def adopt(ps):
+        flat = FlatGrads(ps)
+        flat.adopt()
+        offsets = [p.grad.data_ptr() % 16 for p in ps]
+        assert any(offsets), "every gradient view is 16-byte aligned: the shapes no longer pack off the grid"
+        assert {4, 8, 12} & set(offsets)
+        return flat
+
+    a, b = _params(0, SHAPES, "cuda"), _params(0, SHAPES, "cuda")
+    flat = adopt(a)
+    oa = MultiTensorAdam(a, lr=3e-3, betas=(0.9, 0.999), eps=1e-8, tf_epsilon=False)
+    ob = torch.optim.Adam(b, lr=3e-3, betas=(0.9, 0.999), eps=1e-8)
+    for gs in gradients(1):
+        for view, pb, g in zip(flat.views, b, gs):
+            view.copy_(g)
+            pb.grad = g.cuda()
+        oa.step()
+        ob.step()
+    assert all(p.grad.data_ptr() == v.data_ptr() for p, v in zip(a, flat.views))
+    for pa, pb in zip(a, b):
+        np.testing.assert_allclose(pa.detach().cpu().numpy(), pb.detach().cpu().numpy(), rtol=2e-5, atol=2e-6)
+
+    lr, b1, b2, eps, scale, clip, decay = 1e-2, 0.9, 0.999, 1e-8, 0.25, 1.0, (3, 0.5, False)
+    ps = _params(3, SHAPES, "cuda")
+    ref = [p.detach().cpu().double().numpy().copy() for p in ps]
+    m = [np.zeros_like(r) for r in ref]
+    v = [np.zeros_like(r) for r in ref]
+    flat = adopt(ps)
+    opt = MultiTensorAdam(ps, lr=lr, betas=(b1, b2), eps=eps, tf_epsilon=True, grad_scale=scale, clip_norm=clip, lr_decay=decay)
+    clipped = set()
+    for t, gs in enumerate(gradients(4), start=1):
+        lr_t = lr * decay[1] ** ((t - 1) / decay[0])                 # smooth: no floor
+        for i, (view, g) in enumerate(zip(flat.views, gs)):
+            view.copy_(g)
+            x = g.double().numpy() * scale
+            norm = np.sqrt((x * x).sum())
+            clipped.add(bool(norm > clip))
+            x = x * clip / max(norm, clip)
+            m[i] = b1 * m[i] + (1 - b1) * x
+            v[i] = b2 * v[i] + (1 - b2) * x * x
+            ref[i] -= lr_t * np.sqrt(1 - b2 ** t) / (1 - b1 ** t) * m[i] / (np.sqrt(v[i]) + eps)
+        opt.step()
+    assert clipped == {True, False}
+    assert opt.lr_at(steps - 1) == pytest.approx(lr * 0.5 ** ((steps - 1) / 3), rel=1e-6)
+    for p, r in zip(ps, ref):
+        np.testing.assert_allclose(p.detach().cpu().numpy(), r, rtol=3e-5, atol=3e-6)
+
+
 def test_multi_tensor_adam_has_no_cpu_path():
     from heterofusionrcnn_amd.optim import MultiTensorAdam
     with pytest.raises(RuntimeError, match="no CPU implementation"):
