@@ -7,6 +7,17 @@ workgroup looks its chunk up.  The gradients are read where autograd left them: 
 allocate fresh gradients; a captured graph does not) the table is rewritten and uploaded, otherwise a step is two launches
 (the step counter, the update).
 
+Who owns which table.  Eager steps and captured steps may be mixed freely on one optimizer (graph_step.TrainStep does: its
+warm-up steps and its capture share one), so they never share a table:
+  eager steps   launch on ONE device table / chunk map / chunk count that only eager uploads write.  The cache key `_key` is the
+                gradient addresses of the last EAGER upload, which is exactly what that table holds: no capture and no replay
+                touches either.  An eager step uploads iff its gradients' addresses (or the set of tensors that have one)
+                differ from the key; eager steps on unmoved gradients upload once.
+  a capture     takes a device table, a chunk map and pinned staging of its own for good and ALWAYS records its own upload
+                nodes and its own chunk count, whatever the key says: every replay rewrites and reads only that table, and no
+                later eager step can change what a replay updates.  It neither reads nor sets the key.
+`table_uploads` counts the uploads Python issued (eager uploads, and one per capture while it is recorded); a replay issues none.
+
 `tf_epsilon=True` (default) is TensorFlow's update  p -= lr sqrt(1-b2^t)/(1-b1^t) m / (sqrt(v) + eps); False is
 torch.optim.Adam's placement of epsilon (tests/test_optim.py pins the arithmetic of that mode to torch's own optimizer).
 
@@ -93,14 +104,15 @@ class MultiTensorAdam:
         # pinned staging for the table upload.  The upload is asynchronous and the host may be several steps ahead of the device,
         # so a rewrite never touches a buffer whose upload may still be pending: eager rewrites rotate through a ring (an event
         # per slot, waited on before the slot is reused); a capture takes a slot of its own for good (the graph's upload nodes
-        # re-read it at every replay).  All pinned allocations happen outside captures (hipHostMalloc is not capturable).
+        # re-read it at every replay), together with a device table and map of its own (module docstring).  All pinned
+        # allocations happen outside captures (hipHostMalloc is not capturable), the captures' device tables with them.
         self._ring = [self._new_staging() for _ in range(4)]
         self._ring_at = 0
-        self._for_captures = [self._new_staging() for _ in range(2)]
-        self._captured_staging = []
-        self._dev_table = torch.empty(self._table_bytes, dtype=torch.uint8, device=dev)
-        self._dev_map = torch.empty((self._map_rows, 2), dtype=torch.int32, device=dev)
-        self._key, self._chunks = None, 0
+        self._for_captures = [self._new_capture_set() for _ in range(2)]
+        self._captured = []                                   # the sets captures took: alive as long as the optimizer
+        self._dev_table, self._dev_map = self._new_device_table()        # the eager steps' own
+        self._key, self._chunks = None, 0                     # what the last eager upload wrote there
+        self.table_uploads = 0
         self.total_elements = total
         # the per-chunk sums of squares of the clipped step (one double per map row), allocated here: never inside a capture
         self._partials = torch.empty(max(self._map_rows, 1), dtype=torch.float64, device=dev)
@@ -108,6 +120,15 @@ class MultiTensorAdam:
     def _new_staging(self):
         return [torch.empty(self._table_bytes, dtype=torch.uint8).pin_memory(),
                 torch.empty((self._map_rows, 2), dtype=torch.int32).pin_memory(), None]
+
+    def _new_device_table(self):
+        dev = self.params[0].device
+        return (torch.empty(self._table_bytes, dtype=torch.uint8, device=dev),
+                torch.empty((self._map_rows, 2), dtype=torch.int32, device=dev))
+
+    def _new_capture_set(self):
+        """what one capture owns: pinned staging, a device table and a device map"""
+        return self._new_staging()[:2] + list(self._new_device_table())
 
     # the framework optimizers' surface that callers here use
     def zero_grad(self, set_to_none=True):
@@ -117,25 +138,8 @@ class MultiTensorAdam:
             elif p.grad is not None:
                 p.grad.zero_()
 
-    def _refresh(self):
-        """rewrite + upload the table when a gradient moved (or appeared / vanished)"""
-        key = tuple(p.grad.data_ptr() if p.grad is not None else 0 for p in self.params)
-        if key == self._key:
-            return
-        capturing = torch.cuda.is_current_stream_capturing()
-        if capturing:
-            if not self._for_captures:
-                raise RuntimeError("MultiTensorAdam: no pinned staging left for another capture (run one eager step between captures)")
-            slot = self._for_captures.pop()
-            self._captured_staging.append(slot)
-        else:
-            while len(self._for_captures) < 2:
-                self._for_captures.append(self._new_staging())
-            slot = self._ring[self._ring_at]
-            self._ring_at = (self._ring_at + 1) % len(self._ring)
-            if slot[2] is not None:
-                slot[2].synchronize()           # the upload that last read this slot has executed (four rewrites ago: rarely waits)
-        host_table, host_map = slot[0], slot[1]
+    def _write_table(self, host_table, host_map, dev_table, dev_map):
+        """the table of the tensors that have a gradient now -> pinned staging -> device, on the current stream; returns its chunks"""
         entries = (_Entry * len(self.params)).from_buffer(host_table.numpy())
         rows, live = [], 0
         for i, p in enumerate(self.params):
@@ -147,36 +151,57 @@ class MultiTensorAdam:
             entries[live] = _Entry(p.data_ptr(), g.data_ptr(), self.exp_avg[i].data_ptr(), self.exp_avg_sq[i].data_ptr(), p.numel())
             rows += [(live, c) for c in range((p.numel() + self.chunk - 1) // self.chunk)]
             live += 1
-        self._chunks = len(rows)
         if rows:
             host_map[:len(rows)] = torch.tensor(rows, dtype=torch.int32)
-        # pinned staging -> device on the current stream (inside a capture this becomes a node of the graph: it re-uploads the
-        # same bytes at every replay, 12 KB)
-        self._dev_table.copy_(host_table, non_blocking=True)
-        self._dev_map.copy_(host_map, non_blocking=True)
-        if not capturing:
+        # inside a capture the two copies become nodes of the graph: they re-upload the same bytes at every replay, 12 KB
+        dev_table.copy_(host_table, non_blocking=True)
+        dev_map.copy_(host_map, non_blocking=True)
+        self.table_uploads += 1
+        return len(rows)
+
+    def _refresh(self):
+        """-> (device table, device map, chunks) this step launches on.  Eager: the eager table, rewritten + uploaded when a gradient
+        moved (or appeared / vanished) since the last eager upload.  Capturing: a table of the capture's own, always uploaded"""
+        if torch.cuda.is_current_stream_capturing():
+            if not self._for_captures:
+                raise RuntimeError("MultiTensorAdam: no pinned staging left for another capture (run one eager step between captures)")
+            own = self._for_captures.pop()
+            self._captured.append(own)
+            return own[2], own[3], self._write_table(*own)
+        while len(self._for_captures) < 2:
+            self._for_captures.append(self._new_capture_set())
+        key = tuple(p.grad.data_ptr() if p.grad is not None else 0 for p in self.params)
+        if key != self._key:
+            slot = self._ring[self._ring_at]
+            self._ring_at = (self._ring_at + 1) % len(self._ring)
+            if slot[2] is not None:
+                slot[2].synchronize()           # the upload that last read this slot has executed (four rewrites ago: rarely waits)
+            self._key = None                    # until the upload below is enqueued the table matches no key
+            self._chunks = self._write_table(slot[0], slot[1], self._dev_table, self._dev_map)
             slot[2] = torch.cuda.Event()
             slot[2].record()
-        self._key = key
+            self._key = key
+        return self._dev_table, self._dev_map, self._chunks
 
     @torch.no_grad()
     def step(self):
-        self._refresh()
+        table, chunk_map, chunks = self._refresh()
         self.step_count.add_(1.0)
         L = _lib.lib()
         mode = 0 if self.tf_epsilon else 1
         if self.clip_norm == 0.0 and self.lr_decay is None:
-            check(L.hf_adam_multi(self._chunks, ptr(self._dev_table), ptr(self._dev_map), ptr(self.step_count), self.lr,
+            check(L.hf_adam_multi(chunks, ptr(table), ptr(chunk_map), ptr(self.step_count), self.lr,
                                   self.betas[0], self.betas[1], self.eps, self.grad_scale, mode, stream_ptr()), "adam_multi")
             return
+        # _partials is scratch of one step (written, then read, in stream order): eager and captured steps share it
         if self.clip_norm > 0.0:
-            check(L.hf_adam_sqnorm_partials(self._chunks, ptr(self._dev_table), ptr(self._dev_map), self.grad_scale,
+            check(L.hf_adam_sqnorm_partials(chunks, ptr(table), ptr(chunk_map), self.grad_scale,
                                             ptr(self._partials), stream_ptr()), "adam_sqnorm_partials")
         decay, steps, factor = 0, 1.0, 1.0
         if self.lr_decay is not None:
             steps, factor, staircase = self.lr_decay
             decay = 2 if staircase else 1
-        check(L.hf_adam_multi_sched(self._chunks, ptr(self._dev_table), ptr(self._dev_map), ptr(self.step_count), ptr(self._partials),
+        check(L.hf_adam_multi_sched(chunks, ptr(table), ptr(chunk_map), ptr(self.step_count), ptr(self._partials),
                                     self.clip_norm, self.lr, decay, steps, factor, self.betas[0], self.betas[1], self.eps,
                                     self.grad_scale, mode, stream_ptr()), "adam_multi_sched")
 
