@@ -160,19 +160,7 @@ def wgrad_bound(s, n):
     return (n + 2) * U * s + FLOOR
 
 
-def conv_s2_tap_sum(x, wt):
-    """x (b,2h,2w,cin), wt (9,cout,cin) fp64 -> z, S (b,h,w,cout): output (oy, ox) reads input (2 oy - 1 + ky, 2 ox - 1 + kx)"""
-    b, h2, w2, cin = x.shape
-    pad = torch.zeros((b, h2 + 1, w2 + 1, cin), dtype=torch.float64)
-    pad[:, 1:, 1:] = x
-    z = torch.zeros((b, h2 // 2, w2 // 2, wt.shape[1]), dtype=torch.float64)
-    s = torch.zeros_like(z)
-    for ky in range(3):
-        for kx in range(3):
-            src = pad[:, ky:ky + h2:2, kx:kx + w2:2]                 # pad index 2 oy + ky = input index 2 oy - 1 + ky
-            z += src @ wt[3 * ky + kx].T
-            s += src.abs() @ wt[3 * ky + kx].abs().T
-    return z, s
+conv_s2_tap_sum = pc.conv_s2_tap_sum                                  # the forward kernel's third form: stated next to the other two
 
 
 @functools.lru_cache(maxsize=None)
@@ -228,6 +216,117 @@ def pool_bwd_expected(name):
     F.max_pool2d(x, 2).backward(torch.from_numpy(t["g"].copy()).permute(0, 3, 1, 2).contiguous())
     grad = x.grad.permute(0, 2, 3, 1).contiguous().numpy()
     return {"grad": grad, "sum": t["base"] + grad}
+
+
+# ------------------------------------------------------------------------------------------------ the dispatch rules, restated
+# launch_conv_wgrad and conv_wgrad_plan of conv_nhwc.hip, wgrad_plan of gemm_common.h (restated in gemm_cases.wgrad_plan); the pool's
+# backward and the forward kernel's rules are image_pyramid_cases'.  tests/test_image_pyramid_train_cases_cpu.py looks the texts up.
+SOURCE_RULES = (
+    ("conv_nhwc.hip", "WgradPlan p = wgrad_plan(rows, 9 * cout, cin);"),
+    ("conv_nhwc.hip", "if (p.wm != 2) { p.wm = 2; p.mtiles = 1; }      // 9 cout <= 64: one tile, partly empty"),
+    ("conv_nhwc.hip", "using Q = WgradTile<2, WN>;"),
+    ("conv_nhwc.hip", "const dim3 grid(p.mtiles * p.ntiles, p.chunks);"),
+    ("conv_nhwc.hip", "const bool gvec = vec4_ok(dz, cout), xvec = vec4_ok(x, cin);"),
+    ("conv_nhwc.hip", "if (p.wn == 2) HF_CWGRAD_V(2);"),
+    ("conv_nhwc.hip", "return p.chunks > 1 ? sizeof(float) * static_cast<size_t>(p.chunks) * 9 * cout * cin : 0;"),
+    ("gemm_common.h", "p.wm = cout > 64 ? 2 : 1;"),
+    ("gemm_common.h", "p.wn = cin > 64 ? 2 : 1;"),
+    ("gemm_common.h", "p.mtiles = div_up(cout, 64 * p.wm);"),
+    ("gemm_common.h", "p.ntiles = div_up(cin, 64 * p.wn);"),
+    ("gemm_common.h", "long long want = static_cast<long long>(kNumCU) * 3 / (p.mtiles * p.ntiles);"),
+    ("gemm_common.h", "if (rpc < 256) rpc = 256;"),
+)
+
+
+def wgrad_instantiation(case, off=None):
+    """the kernel hf_conv3x3_nhwc_wgrad or (case["up"]) hf_upconv3x3s2_nhwc_wgrad launches; off: "dz" or "x" one float past a
+    16-byte boundary"""
+    gvec = case["cout"] % 4 == 0 and off != "dz"
+    xvec = case["cin"] % 4 == 0 and off != "x"
+    return ("conv_wgrad_kernel", (2 if case["cin"] > 64 else 1, gvec, xvec, bool(case.get("up", False))))
+
+
+def conv_wgrad_plan(case):
+    """the plan of the (9 cout, cin) matrix over b h w reduction rows (for both directions the pixels of x), always with the 128-row
+    M tile: {"wn", "mtiles", "ntiles", "rows_per_chunk", "chunks", "forced": 9 cout <= 64, one partly empty tile, "workspace": bytes}"""
+    import gemm_cases as gc
+    m, cin = 9 * case["cout"], case["cin"]
+    wm, wn, rpc, chunks = gc.wgrad_plan(case["b"] * case["h"] * case["w"], m, cin)
+    return {"wn": wn, "mtiles": 1 if wm != 2 else pc.cdiv(m, 128), "ntiles": pc.cdiv(cin, 64 * wn), "rows_per_chunk": rpc, "chunks": chunks,
+            "forced": wm != 2, "workspace": 4 * chunks * m * cin if chunks > 1 else 0}
+
+
+# ------------------------------------------------------------------------------------------------ the exact family
+# image_pyramid_cases' family for the weight gradients: x integers in [-8, 8], in_sub in [-2, 2], dz sparse in {-1, 0, 1}: every
+# partial sum of every chunk and of the reduction over chunks is an integer of magnitude <= S = sum |dz| |x'| <= 10 rows < 2^24
+EXACT_WGRAD_COUT = (1, 7, 8, 5, 33, 32, 128)             # 9 cout <= 64 (1, 5, 7): the forced tile; 8 just past it; 5, 33: GVEC = false by shape
+EXACT_WGRAD_CIN = (3, 5, 36, 64, 65, 68, 256)            # 64 | 65: WN; 65 is WN = 2 with a scalar X
+
+
+def exact_wgrad_cases(up):
+    """every (cin, cout) once, geometry and in_sub rotating; then dz and x, each in turn, one float past the boundary at both WN"""
+    cases, n = {}, 0
+    for i, cin in enumerate(EXACT_WGRAD_CIN):
+        for j, cout in enumerate(EXACT_WGRAD_COUT):
+            b, h, w = WGRAD_SHAPES[(i + j) % len(WGRAD_SHAPES)]
+            cases["b%dh%dw%d_ci%d_co%d" % (b, h, w, cin, cout)] = dict(up=up, b=b, h=h, w=w, cin=cin, cout=cout, off=None,
+                                                                        sub=bool(SUB_PATTERN[n % len(SUB_PATTERN)]) and not up)
+            n += 1
+    for cin, cout in ((36, 32), (68, 128)):
+        for k, off in enumerate(("dz", "x")):
+            cases["b1h12w22_ci%d_co%d_off_%s" % (cin, cout, off)] = dict(up=up, b=1, h=12, w=22, cin=cin, cout=cout, off=off,
+                                                                          sub=k == 0 and not up)
+    return cases
+
+
+EXACT_WGRAD_CASES = exact_wgrad_cases(False)
+EXACT_UPWGRAD_CASES = exact_wgrad_cases(True)            # (b, h, w) is the INPUT of the up-convolution
+EXACT_S2_CASES, REGIME_S2_CASES = pc.EXACT_S2_CASES, pc.REGIME_S2_CASES
+
+
+@functools.lru_cache(maxsize=None)
+def exact_wgrad_case(up, name):
+    """(case, inputs as float32 arrays, dwt (9,cout,cin) fp64, max S), computed once"""
+    import gemm_cases as gc
+    c = (EXACT_UPWGRAD_CASES if up else EXACT_WGRAD_CASES)[name]
+    g = pc._exact_gen("wgrad%d" % up + name)
+    k = 2 if up else 1
+    t = {"x": gc.ints(g, (c["b"], c["h"], c["w"], c["cin"]), -8, 8).numpy(),
+         "dz": gc.sparse_pm1(g, (c["b"], k * c["h"], k * c["w"], c["cout"])).numpy(),
+         "in_sub": gc.ints(g, (c["cin"],), -2, 2).numpy() if c["sub"] else None}
+    dwt, s = upconv_wgrad_sum(_t64(t["x"]), _t64(t["dz"])) if up else conv_wgrad_sum(_t64(t["x"]), _t64(t["dz"]), _t64(t["in_sub"]))
+    return c, t, dwt, float(s.max())
+
+
+def abi_cases():
+    """[{"id", "family", "kernels"}] of every C-ABI case of tests/test_image_pyramid_train_abi.py (image_pyramid_cases.abi_cases'
+    form); the dgrad cases run the forward kernel with cin and cout exchanged"""
+    out = []
+    add = lambda test, family, name, *kernels: out.append({"id": "%s/%s/%s" % (test, family, name), "family": family, "kernels": set(kernels)})
+    for test, up, table in (("wgrad", False, WGRAD_CASES), ("upwgrad", True, UPWGRAD_CASES)):
+        for name, c in table.items():
+            add(test, "round", name, wgrad_instantiation(dict(c, up=up)))
+    add("wgrad", "round", "b1h12w22_ci36_co40_off_x", wgrad_instantiation(WGRAD_CASES["b1h12w22_ci36_co40"], "x"))
+    for test, table in (("wgrad", EXACT_WGRAD_CASES), ("upwgrad", EXACT_UPWGRAD_CASES)):
+        for name, c in table.items():
+            add(test, "exact", name, wgrad_instantiation(c, c["off"]))
+    for name, c in S2_CASES.items():
+        add("conv3x3s2", "round", name, pc.conv_instantiation(dict(c, mode="s2")))
+    for family, table in (("exact", EXACT_S2_CASES), ("regime", REGIME_S2_CASES)):
+        for name, c in table.items():
+            add("conv3x3s2", family, name, pc.conv_instantiation(c, c["off"]))
+    for name in DGRAD_CASES:
+        c = pc.CONV_CASES[name]
+        add("dgrad", "round", name, pc.conv_instantiation(dict(mode="conv", cin=c["cout"], cout=c["cin"])))
+    for family, table in (("round", POOL_BWD_CASES), ("regime", pc.REGIME_POOL_BWD_CASES)):
+        for name, c in table.items():
+            add("maxpool2x2_bwd", family, name, pc.pool_instantiation(c, True, backward=True), pc.pool_instantiation(c, False, backward=True))
+    return out
+
+
+def selected_instantiations(cases=None):
+    """what the cases of both ABI files reach in conv_nhwc.hip"""
+    return pc.selected_instantiations(pc.abi_cases() + abi_cases() if cases is None else cases)
 
 
 # ------------------------------------------------------------------------------------------------ HF_EINVAL

@@ -3,8 +3,10 @@ restatements against torch's own convolutions, image_pyramid.pack against the mo
 HF_EINVAL paths of the three entry points (they return before any HIP call), the scope and its refusals."""
 import ctypes
 import os
+import re
 import sys
 
+import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
@@ -81,6 +83,114 @@ def test_case_tables_cover_what_the_kernels_branch_on():
     r = pc.conv_reference("conv", "first_layer_0")
     assert r["y"].shape == (70, 32) and bool((r["y"] >= 0).all()) and bool((r["bound"] > 0).all())
     assert pc.conv_reference("upconv", "b2h3w5_ci36_co32")["y"].shape == (2 * 6 * 10, 32)
+
+
+# ---------------------------------------------------------------------------------------------- the restated dispatch rules
+def _source(name):
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    with open(os.path.join(root, "heterofusionrcnn_amd", "csrc", name)) as f:
+        return f.read()
+
+
+@pytest.mark.parametrize("name,constant,value", pc.SOURCE_CONSTANTS, ids=lambda v: str(v))
+def test_constants_are_those_of_the_sources(name, constant, value):
+    found = re.findall(r"constexpr\s+int\s+%s\s*=\s*(\d+)\s*;" % constant, _source(name))
+    assert found == [str(value)], "%s of %s changed: the restated rules of image_pyramid_cases.py and the regimes of its cases depend on it" % (constant, name)
+
+
+@pytest.mark.parametrize("name,text", pc.SOURCE_RULES, ids=lambda v: v[:40].replace(" ", "_"))
+def test_rule_literals_are_those_of_the_sources(name, text):
+    assert _source(name).count(text) == 1, "the dispatch rule of %s changed: restate it in image_pyramid_cases.py (%r)" % (name, text)
+
+
+def test_restated_rules():
+    assert [pc.conv_nt(c) for c in (1, 32, 33, 64, 65, 128, 129, 256)] == [1, 1, 2, 2, 4, 4, 8, 8]
+    assert [pc.resident_grid(nt, 10 ** 6) for nt in (1, 2, 4, 8)] == [2048, 2048, 1536, 1024] and pc.resident_grid(1, 3) == 3
+    c = dict(mode="up", b=1, h=2, w=2, cin=36, cout=40)
+    assert pc.conv_instantiation(c) == ("conv3x3_kernel", (2, True, 1)) and pc.conv_instantiation(c, "wt") == ("conv3x3_kernel", (2, False, 1))
+    assert pc.conv_instantiation(dict(c, cin=3, mode="s2")) == ("conv3x3_kernel", (2, False, 2))
+    assert pc.conv_stages(c) == (2, 3, 3, 5) and pc.conv_stages(dict(c, mode="conv")) == (11,) and pc.conv_stages(dict(cin=3)) == (1,)
+    assert pc.conv_tiles(dict(b=1, h=12, w=22, cout=32)) == (1, 1) and pc.conv_tiles(dict(b=2, h=192, w=320, cout=32)) == (1, 1)
+    p = dict(b=2, h=6, w=10, c=32)
+    assert pc.pool_instantiation(p, True) == ("maxpool2x2_kernel", (4,)) and pc.pool_instantiation(p, False, "x") == ("maxpool2x2_kernel", (1,))
+    assert pc.pool_instantiation(dict(p, c=3), True, backward=True) == ("maxpool2x2_bwd_kernel", (1,))
+    assert pc.pool_items(p) == 2 * 3 * 5 * 8 and pc.pool_items(dict(b=1, h=5, w=7, c=3), backward=True) == 3 * 4 * 3 and not pc.pool_strides(p)
+
+
+# ---------------------------------------------------------------------------------------------- the exact family
+EXACT_TABLES = (("conv", pc.EXACT_CONV_CASES), ("up", pc.EXACT_UPCONV_CASES), ("s2", pc.EXACT_S2_CASES))
+
+
+@pytest.mark.parametrize("mode,cases", EXACT_TABLES, ids=[m for m, _ in EXACT_TABLES])
+def test_exact_family_is_exact_and_reaches_every_form(mode, cases):
+    assert len(cases) == len(pc.EXACT_CIN) * len(pc.EXACT_COUT) + 2 * len(pc.EXACT_ALIGN_COUT)
+    for name, c in cases.items():
+        _, t, y, smax = pc.exact_conv_case(mode, name)
+        assert c["mode"] == mode and pc.exact_condition(smax) and smax <= 9 * 256 * 10, name
+        assert float((y * 8).frac().abs().max()) == 0 and torch.equal(y.float().double(), y), name
+        assert set(np.unique(t["wt"])) <= {-1.0, 0.0, 1.0} and float(np.abs(t["x"]).max()) <= 8 and np.array_equal(t["x"], np.round(t["x"]))
+        if c["affine"]:
+            assert set(np.unique(np.abs(t["scale"]))) <= {0.5, 1.0, 2.0} and float(np.abs(t["shift"]).max()) <= 4
+            assert np.array_equal(t["shift"] * 4, np.round(t["shift"] * 4))
+    # all eight instantiations of the mode; the scalar form by shape and, at cin % 4 == 0, by x and by wt off the boundary
+    reach = {pc.conv_instantiation(c, c["off"])[1] for c in cases.values()}
+    assert reach == {(nt, vec, pc.CONV_MODES.index(mode)) for nt in (1, 2, 4, 8) for vec in (False, True)}
+    for nt in (1, 2, 4, 8):
+        scalar = [c for c in cases.values() if pc.conv_instantiation(c, c["off"])[1][:2] == (nt, False)]
+        assert {c["off"] for c in scalar if c["cin"] % 4 == 0} == {"x", "wt"} and any(c["cin"] % 4 for c in scalar), nt
+    plain = [c for c in cases.values() if c["off"] is None]
+    assert {c["cin"] for c in plain} == set(pc.EXACT_CIN) and {c["cout"] for c in plain} == set(pc.EXACT_COUT)
+    for key, values in (("cin", pc.EXACT_CIN), ("cout", pc.EXACT_COUT)):
+        for v in values:           # every cin and every cout meets every geometry and every flag pattern the entry point has
+            mine = [c for c in plain if c[key] == v]
+            assert {(c["b"], c["h"], c["w"]) for c in mine} == set(pc.CONV_SHAPES), (key, v)
+            for flag in ("affine", "relu", "slice") + (("sub",) if mode == "conv" else ()):
+                assert {c[flag] for c in mine} == {False, True}, (key, v, flag)
+    # the K axis: one stage, whole stages, a 4-wide tail, a scalar quad over two taps
+    assert {pc.conv_stages(c) for c in plain if c["cin"] == 3} == ({(1,)} if mode != "up" else {(1, 1, 1, 1)})
+    assert all((9 * c["cin"]) % pc.FWD_KC == 0 for c in plain if c["cin"] in (32, 256))
+    assert all(c["cin"] % 4 and (2 * c["cin"]) % 4 for c in plain if c["cin"] in (5, 33))
+
+
+def test_exact_references_are_torch_convolutions():
+    """integers: the restatements and torch's own fp64 convolutions agree exactly, whatever order either sums in"""
+    for mode, name in (("conv", "b2h5w7_ci3_co1"), ("conv", "b1h12w22_ci36_co40_off_wt"), ("up", "b2h5w7_ci3_co1"), ("up", "b1h12w22_ci36_co128_off_x"),
+                       ("s2", "b2h5w7_ci3_co1"), ("s2", "b1h12w22_ci36_co256_off_x")):
+        c, t, y, _ = pc.exact_conv_case(mode, name)
+        x, wt = torch.from_numpy(t["x"]).double(), torch.from_numpy(t["wt"]).double()
+        if c["sub"]:
+            x = F.pad((x - torch.from_numpy(t["in_sub"]).double()).permute(0, 3, 1, 2), (1, 1, 1, 1)).permute(0, 2, 3, 1)
+        k = wt.reshape(3, 3, c["cout"], c["cin"])
+        if mode == "up":
+            z = F.conv_transpose2d(x.permute(0, 3, 1, 2), k.permute(3, 2, 0, 1), stride=2, padding=1, output_padding=1)
+        else:
+            z = F.conv2d(x.permute(0, 3, 1, 2), k.permute(2, 3, 0, 1), stride=2 if mode == "s2" else 1, padding=0 if c["sub"] else 1)
+        z = z.permute(0, 2, 3, 1)
+        if c["affine"]:
+            z = z * torch.from_numpy(t["scale"]).double() + torch.from_numpy(t["shift"]).double()
+        z = z.clamp(min=0.0) if c["relu"] else z
+        assert torch.equal(z.reshape(-1, c["cout"]), y) and bool((y != 0).any()), (mode, name)
+
+
+def test_regime_cases_walk_the_persistent_grid_and_the_grid_stride_loops():
+    for table in (pc.REGIME_CONV_CASES, pc.REGIME_UPCONV_CASES, pc.REGIME_S2_CASES):
+        for name, c in table.items():
+            fewest, most = pc.conv_tiles(c)
+            # every workgroup prefetches a next tile under its last K stage, some twice; a ragged last tile; rows and images end inside tiles
+            assert fewest >= 2 and most >= 3 and pc.conv_rows(c) % pc.FWD_ROWS and c["w"] % pc.FWD_ROWS and (c["h"] * c["w"]) % pc.FWD_ROWS, name
+            assert pc.exact_condition(9 * c["cin"] * 10), name                 # S <= 9 cin max|x'|
+    assert {pc.conv_instantiation(c) for c in pc.REGIME_CONV_CASES.values()} == {("conv3x3_kernel", a) for a in ((1, True, 0), (1, False, 0), (8, True, 0))}
+    assert pc.conv_rows(pc.REGIME_CONV_CASES["nt1_vec"]) == 524547 and pc.conv_rows(pc.REGIME_CONV_CASES["nt8_vec"]) == 262654
+    for table, backward in ((pc.REGIME_POOL_CASES, False), (pc.REGIME_POOL_BWD_CASES, True)):
+        assert {pc.pool_instantiation(c, s, backward=backward)[1] for c in table.values() for s in (False, True)} == {(1,), (4,)}
+        for name, c in table.items():
+            for sliced in (False, True):
+                lanes = pc.POOL_MAX_GRID * pc.POOL_THREADS
+                assert lanes < pc.pool_items(c, sliced, backward) < 2 * lanes and pc.pool_strides(c, sliced, backward), name
+    assert all(c["h"] % 2 and c["w"] % 2 for c in pc.REGIME_POOL_BWD_CASES.values()) and pc.REGIME_POOL_CASES["vec1"]["w"] % 2
+    assert not any(pc.pool_strides(c, s) or pc.pool_strides(c, s, True) for c in pc.POOL_CASES.values() for s in (False, True))
+    t = pc.regime_pool_inputs("vec1")
+    assert 0.3 < float((t["x"] == 0).mean()) < 0.7
 
 
 def _layer_tap_sum(layer, x):

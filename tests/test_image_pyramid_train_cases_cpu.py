@@ -127,6 +127,70 @@ def test_case_tables_cover_what_the_kernels_branch_on():
     assert bool((r["bound"] > 0).all())
 
 
+@pytest.mark.parametrize("name,text", tc.SOURCE_RULES, ids=lambda v: v[:40].replace(" ", "_"))
+def test_rule_literals_are_those_of_the_sources(name, text):
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    with open(os.path.join(root, "heterofusionrcnn_amd", "csrc", name)) as f:
+        assert f.read().count(text) == 1, "the dispatch rule of %s changed: restate it in image_pyramid_train_cases.py (%r)" % (name, text)
+
+
+def test_restated_wgrad_rules_agree_with_the_library():
+    """the workspace query is the one piece of the plan the library shows without a GPU"""
+    from heterofusionrcnn_amd import _lib
+    L = _lib.lib()
+    for up, table in ((False, tc.EXACT_WGRAD_CASES), (True, tc.EXACT_UPWGRAD_CASES)):
+        query = L.hf_upconv3x3s2_nhwc_wgrad_workspace if up else L.hf_conv3x3_nhwc_wgrad_workspace
+        for name, c in table.items():
+            assert query(c["b"], c["h"], c["w"], c["cin"], c["cout"]) == tc.conv_wgrad_plan(c)["workspace"], name
+    c = dict(b=1, h=40, w=52, cin=65, cout=7)
+    assert tc.wgrad_instantiation(c) == ("conv_wgrad_kernel", (2, False, False, False))
+    assert tc.wgrad_instantiation(dict(c, cin=68, cout=8, up=True), "dz") == ("conv_wgrad_kernel", (2, False, True, True))
+    p = tc.conv_wgrad_plan(c)
+    assert p["forced"] and (p["mtiles"], p["ntiles"], p["wn"]) == (1, 1, 2) and p["rows_per_chunk"] == 256 and p["chunks"] == 9
+    assert not tc.conv_wgrad_plan(dict(c, cout=8))["forced"] and tc.conv_wgrad_plan(dict(c, cout=128))["mtiles"] == 9
+
+
+@pytest.mark.parametrize("up", (False, True), ids=("conv", "up"))
+def test_exact_wgrad_family_is_exact_and_reaches_every_form(up):
+    cases = tc.EXACT_UPWGRAD_CASES if up else tc.EXACT_WGRAD_CASES
+    assert len(cases) == len(tc.EXACT_WGRAD_CIN) * len(tc.EXACT_WGRAD_COUT) + 4
+    for name, c in cases.items():
+        _, t, dwt, smax = tc.exact_wgrad_case(up, name)
+        assert smax < 2 ** 24 and smax <= 10 * c["b"] * c["h"] * c["w"] and torch.equal(dwt, dwt.round()), name
+        assert set(np.unique(t["dz"])) <= {-1.0, 0.0, 1.0} and float(np.abs(t["x"]).max()) <= 8 and np.array_equal(t["x"], np.round(t["x"]))
+        if (c["h"], c["w"]) == (1, 1):
+            live = (4, 5, 7, 8) if up else (4,)
+            assert all(bool((dwt[k] == 0).all()) for k in range(9) if k not in live), name
+    reach = {tc.wgrad_instantiation(c, c["off"])[1] for c in cases.values()}
+    assert reach == {(wn, g, x, up) for wn in (1, 2) for g in (False, True) for x in (False, True)}
+    plain = [c for c in cases.values() if c["off"] is None]
+    for key, values in (("cin", tc.EXACT_WGRAD_CIN), ("cout", tc.EXACT_WGRAD_COUT)):
+        for v in values:
+            assert {(c["b"], c["h"], c["w"]) for c in plain if c[key] == v} == set(tc.WGRAD_SHAPES), (key, v)
+    assert {c["cout"] for c in plain if tc.conv_wgrad_plan(c)["forced"]} == {1, 5, 7}
+    assert {tc.conv_wgrad_plan(c)["chunks"] for c in plain} == {1, 2, 9}                  # 70 rows and one pixel; 264; 2080
+    assert {c["sub"] for c in plain} == ({False} if up else {False, True})
+    for wn in (1, 2):              # dz, then x, off the boundary where the shape alone would take both float4 paths
+        moved = {c["off"]: tc.wgrad_instantiation(c, c["off"])[1] for c in cases.values() if c["off"] and (c["cin"] > 64) == (wn == 2)}
+        assert moved == {"dz": (wn, False, True, up), "x": (wn, True, False, up)}
+
+
+def test_exact_wgrad_references_are_torch_autograd():
+    for up, name in ((False, "b1h12w22_ci36_co32_off_dz"), (False, "b2h5w7_ci3_co1"), (True, "b1h12w22_ci68_co128_off_x"), (True, "b2h5w7_ci3_co1")):
+        c, t, dwt, _ = tc.exact_wgrad_case(up, name)
+        x, dz = torch.from_numpy(t["x"]).double(), torch.from_numpy(t["dz"]).double()
+        weight = torch.zeros((c["cin"], c["cout"], 3, 3) if up else (c["cout"], c["cin"], 3, 3), dtype=torch.float64, requires_grad=True)
+        if up:
+            out = F.conv_transpose2d(x.permute(0, 3, 1, 2), weight, stride=2, padding=1, output_padding=1)
+            perm = (2, 3, 1, 0)
+        else:
+            xs = x if t["in_sub"] is None else x - torch.from_numpy(t["in_sub"]).double()
+            out = F.conv2d(F.pad(xs.permute(0, 3, 1, 2), (1, 1, 1, 1)), weight)
+            perm = (2, 3, 0, 1)
+        out.backward(dz.permute(0, 3, 1, 2))
+        assert torch.equal(weight.grad.permute(*perm).reshape(9, c["cout"], c["cin"]), dwt) and bool((dwt != 0).any()), name
+
+
 def test_module_conditions_hold_for_the_seed():
     """the module-level tolerances (8 x the fp32 host route's own error, per tensor) must be above zero, must see a dropped skip or
     pooled path at every level, and must not be decided by a ReLU mask or an argmax that the fp32 rounding could flip"""
