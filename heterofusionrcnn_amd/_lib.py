@@ -122,6 +122,8 @@ _SIGNATURES = {
     "hf_crop_and_resize_grad_ordered": [_i, _i, _i, _i, ctypes.c_longlong, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
     "hf_conv3x3_nhwc": [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _vp],
     "hf_upconv3x3s2_nhwc": [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _vp],
+    "hf_conv3x3_nhwc_bf16": [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _vp],
+    "hf_upconv3x3s2_nhwc_bf16": [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _vp],
     "hf_maxpool2x2_nhwc": [_i, _i, _i, _i, _vp, _i, _i, _vp, _vp],
     "hf_conv3x3s2_nhwc": [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _vp],
     "hf_conv3x3_nhwc_wgrad_workspace": [_i, _i, _i, _i, _i],

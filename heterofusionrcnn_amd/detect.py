@@ -1,6 +1,6 @@
 """Detect from KITTI files with both trained models: python -m heterofusionrcnn_amd.detect DATASET_DIR RPN.pt RCNN.pt OUT_DIR
 [--split val] [--config rpn_multiclass] [--batch 8] [--seed 0] [--workers 8] [--score-threshold 0.1] [--handoff-rounding]
-[--host-rows] [--eval] [--precision {fp32,bf16}] [--image-branch {torch,native}]
+[--host-rows] [--eval] [--precision {fp32,bf16}] [--image-branch {torch,native}] [--image-precision {fp32,bf16}]
 
 The reference's `run_inference.py` over both stages (hf/core/evaluator.py:934-1065 for the first, :300-420 and
 evaluator_utils.py:88-166 for the second), without the hand-off on disk: RPN.pt is what train_rpn --save (or a checkpoint of
@@ -19,6 +19,7 @@ the writer: the parity anchor, byte-identical to rcnn_data.run_rcnn_from_handoff
 are decoded into scores and boxes stay fp32); the default, fp32, is the route described above, bit for bit.
 --image-branch native runs both VGG pyramids (the RPN's and the RCNN's) on the channel-last kernels of csrc/conv_nhwc.hip
 (image_pyramid.image_branch); the default, torch, leaves them on the vendor library.
+--image-precision bf16 (with --image-branch native only) runs their convolutions on csrc/conv_nhwc_bf16.hip (image_pyramid.image_precision).
 """
 import argparse
 import contextlib
@@ -75,11 +76,14 @@ def _write_rows(out_dir, names, counts, host, event, classes):
 @torch.no_grad()
 def detect(dataset_dir, rpn, rcnn, out_dir, split="val", config="rpn_multiclass", batch=8, seed=0, workers=8, score_threshold=0.1,
            handoff_rounding=False, host_rows=False, img_conv=None, num_points=16384, img_hw=(360, 1200), pre_nms_size=9000,
-           nms_thresh=0.8, post_nms_size=100, classes=CLASSES, precision="fp32", image_branch="torch"):
+           nms_thresh=0.8, post_nms_size=100, classes=CLASSES, precision="fp32", image_branch="torch", image_precision="fp32"):
     """rpn / rcnn: see load_models.  precision: mlp.inference_precision for the duration of the call; image_branch:
-    image_pyramid.image_branch for the same duration, over both pyramids.
+    image_pyramid.image_branch for the same duration, over both pyramids; image_precision: image_pyramid.image_precision next to it
+    ("bf16" needs image_branch="native": ValueError otherwise).
     -> {name: rows written} for every frame of the split"""
+    image_pyramid.check_precision_route(image_branch, image_precision)
     scope, img_scope = mlp.inference_precision(precision), image_pyramid.image_branch(image_branch)
+    img_prec = image_pyramid.image_precision(image_precision)
     net, second = load_models(rpn, rcnn, config, img_conv)
     modes = (net.training, second.training)
     net.eval()
@@ -90,7 +94,7 @@ def detect(dataset_dir, rpn, rcnn, out_dir, split="val", config="rpn_multiclass"
                                    (pre_nms_size, nms_thresh, post_nms_size), classes, always_image=True)
     written = {}
     try:
-        with scope, img_scope, contextlib.closing(batches), contextlib.closing(WriteBack()) as back:
+        with scope, img_scope, img_prec, contextlib.closing(batches), contextlib.closing(WriteBack()) as back:
             for frames, meta, xyz, inten, image, out in batches:
                 h = handoff_in_memory(out, xyz, inten, handoff_rounding)
                 dets, _ = second.detect(h["xyz"], h["rpn_fts"], h["intensity"], h["fg_mask"], h["proposals"], image, meta["calib"])
@@ -130,14 +134,19 @@ def build_parser():
                     help="bf16: the wide dense layers of both stages on the bf16 matrix cores (fp32 accumulation, fp32 output heads)")
     ap.add_argument("--image-branch", choices=image_pyramid.IMAGE_BRANCHES, default="torch",
                     help="native: both VGG pyramids on this package's channel-last convolution kernels instead of the vendor library")
+    ap.add_argument("--image-precision", choices=image_pyramid.IMAGE_PRECISIONS, default="fp32",
+                    help="bf16: with --image-branch native, the pyramid's convolutions on the bf16 matrix cores (fp32 tensors and accumulation)")
     return ap
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    ap = build_parser()
+    args = ap.parse_args(argv)
+    if args.image_precision == "bf16" and args.image_branch != "native":
+        ap.error("--image-precision bf16 needs --image-branch native")
     written = detect(args.dataset_dir, args.rpn, args.rcnn, args.out_dir, args.split, args.config, args.batch, args.seed,
                      args.workers, args.score_threshold, args.handoff_rounding, args.host_rows, precision=args.precision,
-                     image_branch=args.image_branch)
+                     image_branch=args.image_branch, image_precision=args.image_precision)
     print("done: %d frames, %d rows" % (len(written), sum(written.values())))
     if args.eval:
         from . import kitti_eval

@@ -167,11 +167,13 @@ def proposals_from_files(net, dataset_dir, names, batch, workers, seed, num_poin
 @torch.no_grad()
 def export(dataset_dir, model, out_dir, split="train", config="rpn_multiclass", batch=8, img_conv=None, workers=8, seed=0,
            num_points=16384, img_hw=(360, 1200), pre_nms_size=9000, nms_thresh=0.8, post_nms_size=100, classes=CLASSES, log=print,
-           image_branch="torch"):
-    """image_branch: image_pyramid.image_branch for the pyramid's calls.
+           image_branch="torch", image_precision="fp32"):
+    """image_branch: image_pyramid.image_branch for the pyramid's calls; image_precision: image_pyramid.image_precision next to it
+    ("bf16" needs image_branch="native": ValueError otherwise).
     model: a path to a saved state_dict (train_rpn --save) or to a checkpoint (train_rpn --checkpoint-dir), a state_dict, or a
     built model (RpnModel / RpnWithImageBranch).
     -> {name: {"proposals", "labels", "recall_50", "recall_70"}} for every frame of the split"""
+    image_pyramid.check_precision_route(image_branch, image_precision)
     net = load_rpn(model, config, img_conv)
     was_training = net.training
     net.eval()
@@ -181,7 +183,8 @@ def export(dataset_dir, model, out_dir, split="train", config="rpn_multiclass", 
     batches = proposals_from_files(net, dataset_dir, names, batch, workers, seed, num_points, img_hw,
                                    (pre_nms_size, nms_thresh, post_nms_size), classes)
     try:
-        with image_pyramid.image_branch(image_branch), contextlib.closing(batches), contextlib.closing(WriteBack()) as back:
+        with image_pyramid.image_branch(image_branch), image_pyramid.image_precision(image_precision), contextlib.closing(batches), \
+                contextlib.closing(WriteBack()) as back:
             for bi, (frames, meta, xyz, inten, _, out) in enumerate(batches):
                 rows = handoff_pack(xyz, inten, out["fg_mask"], out["rpn_fts"])
                 b, m = out["proposals"].shape[:2]
@@ -209,9 +212,13 @@ def main(argv=None):
     ap.add_argument("--workers", type=int, default=8, help="host threads that read and decode the files")
     ap.add_argument("--image-branch", choices=image_pyramid.IMAGE_BRANCHES, default="torch",
                     help="native: the VGG pyramid on this package's channel-last convolution kernels instead of the vendor library")
+    ap.add_argument("--image-precision", choices=image_pyramid.IMAGE_PRECISIONS, default="fp32",
+                    help="bf16: with --image-branch native, the pyramid's convolutions on the bf16 matrix cores (fp32 tensors and accumulation)")
     args = ap.parse_args(argv)
+    if args.image_precision == "bf16" and args.image_branch != "native":
+        ap.error("--image-precision bf16 needs --image-branch native")
     totals = export(args.dataset_dir, args.model, args.out_dir, args.split, args.config, args.batch, workers=args.workers,
-                    seed=args.seed, image_branch=args.image_branch)
+                    seed=args.seed, image_branch=args.image_branch, image_precision=args.image_precision)
     labels = sum(t["labels"] for t in totals.values())
     print("done: %d frames, %d labels, Recall@3DIoU=0.5: %.3f  Recall@3DIoU=0.7: %.3f" % (
         len(totals), labels, sum(t["recall_50"] for t in totals.values()) / max(labels, 1),

@@ -17,6 +17,11 @@ inference and one for training.
                        hf_bn_relu_bwd_ld, the weight gradients, the forward kernels as input gradients and the pool's gradient backward.
                        No atomics: two runs from one state give the same bits
 
+  image_precision(p)   with image_pyramid.image_precision("bf16"): ... -- forward_native sends its convolutions to the bf16
+                       matrix-core kernels of csrc/conv_nhwc_bf16.hip (fp32 tensors, bf16 operands, fp32 accumulation and epilogue),
+                       all but the class that bf16_conv_pays keeps on the fp32 kernel (the first layer, cin = 3, measured slower);
+                       "fp32" (the default) keeps today's bits.  forward_train never reads it
+
 image_branch alone never trains: that scope raises for a module in training mode or with autograd on."""
 import functools
 import weakref
@@ -55,6 +60,36 @@ class _BranchScope:
 
 image_branch = functools.partial(_BranchScope, _IMAGE_BRANCH)
 
+IMAGE_PRECISIONS = ("fp32", "bf16")
+_IMAGE_PRECISION = ["fp32"]
+NATIVE_BF16_LAUNCHES = [0]   # convolution launches of forward_native that went to csrc/conv_nhwc_bf16.hip so far
+
+
+def image_precision_name():
+    return _IMAGE_PRECISION[0]
+
+
+class _PrecisionScope(_BranchScope):
+    """with image_pyramid.image_precision("bf16"): ... -- the operand precision of forward_native's convolutions; the previous
+    setting returns on exit"""
+
+    def __init__(self, cell, mode):
+        if mode not in IMAGE_PRECISIONS:
+            raise ValueError("image precision must be one of %s, got %r" % (IMAGE_PRECISIONS, mode))
+        self.cell, self.mode = cell, mode
+
+
+image_precision = functools.partial(_PrecisionScope, _IMAGE_PRECISION)
+
+
+def check_precision_route(image_branch, image_precision):
+    """the public entry points' rule: bf16 convolutions exist on the native route only, and asking for them elsewhere is an error,
+    never a silent fp32 run"""
+    if image_precision not in IMAGE_PRECISIONS:
+        raise ValueError("image precision must be one of %s, got %r" % (IMAGE_PRECISIONS, image_precision))
+    if image_precision == "bf16" and image_branch != "native":
+        raise ValueError("image_precision='bf16' needs image_branch='native': the vendor-library route has no bf16 convolutions")
+
 TRAIN_BRANCHES = ("torch", "native")
 _TRAIN_BRANCH = ["torch"]
 NATIVE_TRAIN_CALLS = [0]     # forward_train calls so far
@@ -85,7 +120,8 @@ def fold_bn(bn):
 
 
 def _pack_layer(seq):
-    """_ConvBNReLU / _UpConvBNReLU -> {"wt" (9, cout, cin) with tap t = 3 ky + kx, "scale", "shift", "cin", "cout", "up"}"""
+    """_ConvBNReLU / _UpConvBNReLU -> {"wt" (9, cout, cin) with tap t = 3 ky + kx, "scale", "shift", "cin", "cout", "up"};
+    "wt_bf16" joins on the layer's first bf16 launch (_bf16_weights)"""
     conv, bn = seq[0], seq[1]
     up = isinstance(conv, torch.nn.ConvTranspose2d)
     w = conv.weight.detach()
@@ -120,12 +156,40 @@ def pack(img_net):
     return packed
 
 
-def _conv(layer, x, y, y_col=0, in_sub=None):
-    """one launch: x (b, h, w, cin) dense -> columns [y_col, y_col + cout) of y's rows (b, h, w, y_stride), or (b, 2h, 2w, .)"""
+def bf16_conv_pays(rows, cin, cout, up):
+    """whether a convolution of forward_native goes to the bf16 kernels under image_precision("bf16"): rows = b h w of the grid the
+    GEMM runs over, up = the up-convolution.  One class stays on the fp32 kernel: cin % 4 != 0, the scalar staging path, which in the
+    pyramid is the first layer (cin = 3, K = 27).  Its single 64-wide stage is mostly past K and staging, not the MFMA, sets its pace:
+    0.342 ms (p10-p90 0.341-0.344) in bf16 against 0.252 ms (0.249-0.255) on the fp32 kernel at (8, 360, 1200, 3 -> 32), while every
+    layer with cin % 4 == 0 wins by 1.6x to 4.4x (scripts/probes/image_pyramid_bf16_timing.py, profiles/image_pyramid_bf16_timing.json,
+    the "layers" table).  rows, cout and up do not enter: no other class lost"""
+    return cin % 4 == 0
+
+
+def _bf16_weights(layer):
+    """the layer's tap matrices as bf16 (hf_f32_to_bf16), made on first use and kept in the packed layer: they live and die with it"""
+    wb = layer.get("wt_bf16")
+    if wb is None:
+        wb = layer["wt_bf16"] = _dense_kernels.f32_to_bf16(layer["wt"])
+    return wb
+
+
+def _conv(layer, x, y, y_col=0, in_sub=None, bf16=False):
+    """one launch: x (b, h, w, cin) dense -> columns [y_col, y_col + cout) of y's rows (b, h, w, y_stride), or (b, 2h, 2w, .);
+    bf16: on the kernels of csrc/conv_nhwc_bf16.hip"""
     b, h, w, cin = x.shape
     require(cin == layer["cin"], "the layer takes %d channels, the input has %d" % (layer["cin"], cin))
     L = _lib.lib()
-    if layer["up"]:
+    if bf16:
+        wb = _bf16_weights(layer)
+        NATIVE_BF16_LAUNCHES[0] += 1
+        if layer["up"]:
+            check(L.hf_upconv3x3s2_nhwc_bf16(b, h, w, cin, layer["cout"], ptr(x), ptr(wb), ptr(layer["scale"]), ptr(layer["shift"]), 1,
+                                             ptr(y), y.shape[-1], y_col, stream_ptr()), "upconv3x3s2_nhwc_bf16")
+        else:
+            check(L.hf_conv3x3_nhwc_bf16(b, h, w, cin, layer["cout"], ptr(x), ptr(in_sub), ptr(wb), ptr(layer["scale"]),
+                                         ptr(layer["shift"]), 1, ptr(y), y.shape[-1], y_col, stream_ptr()), "conv3x3_nhwc_bf16")
+    elif layer["up"]:
         check(L.hf_upconv3x3s2_nhwc(b, h, w, cin, layer["cout"], ptr(x), ptr(layer["wt"]), ptr(layer["scale"]), ptr(layer["shift"]), 1,
                                     ptr(y), y.shape[-1], y_col, stream_ptr()), "upconv3x3s2_nhwc")
     else:
@@ -134,17 +198,27 @@ def _conv(layer, x, y, y_col=0, in_sub=None):
     return y
 
 
-def forward_native(img_net, image):
-    """ImgVggPyr.forward in eval mode on the kernels of csrc/conv_nhwc.hip: image (B, H, W, 3) fp32 on the device, H and W multiples
-    of 8 (three pools and three doublings must meet again) -> (B, H, W, c1) contiguous"""
+def forward_native(img_net, image, taps=None):
+    """ImgVggPyr.forward in eval mode on the kernels of csrc/conv_nhwc.hip -- under image_precision("bf16") the convolutions on those
+    of csrc/conv_nhwc_bf16.hip, same buffers, same launches: image (B, H, W, 3) fp32 on the device, H and W multiples
+    of 8 (three pools and three doublings must meet again) -> (B, H, W, c1) contiguous.  taps: a list that receives (name, output)
+    of every convolution, up-convolution and pool in launch order, the written slice of a concat buffer as a view; no launch and no
+    copy is added for it"""
     image = _lib.dev_tensor(image, torch.float32, "image")
     require(image.dim() == 4 and image.shape[-1] == 3, "image shape must be (B, H, W, 3), got %s" % (tuple(image.shape),))
     b, h, w, _ = image.shape
     require(b > 0 and h % 8 == 0 and w % 8 == 0 and h > 0 and w > 0, "image height and width must be positive multiples of 8, got %d x %d" % (h, w))
     p = pack(img_net)
     NATIVE_CALLS[0] += 1
+    want_bf16 = _IMAGE_PRECISION[0] == "bf16"
+    bf16 = lambda layer, rows: want_bf16 and bool(bf16_conv_pays(rows, layer["cin"], layer["cout"], layer["up"]))
     L = _lib.lib()
     new = lambda hh, ww, c: torch.empty((b, hh, ww, c), dtype=torch.float32, device=image.device)
+
+    def tap(name, out, col=0, width=None):
+        if taps is not None:
+            taps.append((name, out if width is None else out[..., col:col + width]))
+
     x, sub, cats = image, p["mean"], []
     for level, block in enumerate(p["blocks"]):
         hh, ww = h >> level, w >> level
@@ -152,18 +226,22 @@ def forward_native(img_net, image):
             into_cat = level < 3 and i == len(block) - 1
             if into_cat:
                 cats.append(new(hh, ww, 2 * layer["cout"]))          # [encoder | up]
-            x = _conv(layer, x, cats[-1] if into_cat else new(hh, ww, layer["cout"]), 0, sub)
+            x = _conv(layer, x, cats[-1] if into_cat else new(hh, ww, layer["cout"]), 0, sub, bf16(layer, b * hh * ww))
+            tap("conv%d_%d" % (level + 1, i), x, 0, layer["cout"] if into_cat else None)
             sub = None
         if level < 3:
             c = block[-1]["cout"]
             pooled = new(hh // 2, ww // 2, c)
             check(L.hf_maxpool2x2_nhwc(b, hh, ww, c, ptr(x), 2 * c, 0, ptr(pooled), stream_ptr()), "maxpool2x2_nhwc")
+            tap("pool%d" % (level + 1), pooled)
             x = pooled
     for level, up, fusion in zip((2, 1, 0), p["up"], p["fusion"]):
         cat = cats[level]
         require(cat.shape[-1] == 2 * up["cout"] == fusion["cin"], "the decoder's widths do not match the encoder's")
-        _conv(up, x, cat, up["cout"])
-        x = _conv(fusion, cat, new(h >> level, w >> level, fusion["cout"]))
+        _conv(up, x, cat, up["cout"], None, bf16(up, b * x.shape[1] * x.shape[2]))
+        tap("upconv%d" % (level + 1), cat, up["cout"], up["cout"])
+        x = _conv(fusion, cat, new(h >> level, w >> level, fusion["cout"]), 0, None, bf16(fusion, b * (h >> level) * (w >> level)))
+        tap("fusion%d" % (level + 1), x)
     return x
 
 

@@ -183,8 +183,9 @@ def global_step_of(path):
 @torch.no_grad()
 def validate_rpn(dataset_dir, model, split="val", config="rpn_multiclass", batch=8, seed=0, workers=8, img_conv=None,
                  num_points=16384, img_hw=(360, 1200), pre_nms_size=9000, nms_thresh=0.8, post_nms_size=100, classes=CLASSES,
-                 image_branch="torch"):
-    """image_branch: image_pyramid.image_branch for the pyramid's calls.
+                 image_branch="torch", image_precision="fp32"):
+    """image_branch: image_pyramid.image_branch for the pyramid's calls; image_precision: image_pyramid.image_precision next to it
+    ("bf16" needs image_branch="native": ValueError otherwise).
     model: whatever export_rpn.load_rpn accepts (a --save file, a checkpoint file, a state_dict, a built model).  The frames
     of the split are read once, in order, without augmentation (export_rpn.proposals_from_files: the point samples of
     export_rpn.export at the same seed); ONE eval-mode forward per batch (RpnModel.propose) feeds the fused loss forward
@@ -195,6 +196,7 @@ def validate_rpn(dataset_dir, model, split="val", config="rpn_multiclass", batch
     Differences from the reference (evaluator.py:642-646 divides per-batch sums by the sample count; equal at its batch size 1):
     accuracy is correct points / points, and the average losses are the per-batch losses weighted by the frames in the batch."""
     from .export_rpn import load_rpn, proposals_from_files
+    image_pyramid.check_precision_route(image_branch, image_precision)
     net = load_rpn(model, config, img_conv)
     rpn = net.rpn if hasattr(net, "img_net") else net
     was_training = net.training
@@ -211,7 +213,7 @@ def validate_rpn(dataset_dir, model, split="val", config="rpn_multiclass", batch
     batches = proposals_from_files(net, dataset_dir, names, batch, workers, seed, num_points, img_hw,
                                    (pre_nms_size, nms_thresh, post_nms_size), classes)
     try:
-        with image_pyramid.image_branch(image_branch), contextlib.closing(batches):
+        with image_pyramid.image_branch(image_branch), image_pyramid.image_precision(image_precision), contextlib.closing(batches):
             for bi, (frames, meta, xyz, inten, _, out) in enumerate(batches):
                 b, p = xyz.shape[:2]
                 off = len(seen)
@@ -270,8 +272,10 @@ def rcnn_val_forward(trainer, bt):
 
 
 @torch.no_grad()
-def validate_rcnn(dataset_dir, handoff_dir, model, split="val", batch=2, workers=8, img_conv=None, image_branch="torch"):
-    """image_branch: image_pyramid.image_branch for the pyramid's calls.
+def validate_rcnn(dataset_dir, handoff_dir, model, split="val", batch=2, workers=8, img_conv=None, image_branch="torch",
+                  image_precision="fp32"):
+    """image_branch: image_pyramid.image_branch for the pyramid's calls; image_precision: image_pyramid.image_precision next to it
+    ("bf16" needs image_branch="native": ValueError otherwise).
     model: a train_rcnn --save file, a checkpoint file, a state_dict or a built rcnn_train.RcnnTrainer.  Frames with a label of
     the classes, once, in order, without augmentation (rcnn_data.KittiRcnnBatches(mode="val")); per batch rcnn_val_forward and
     hf_argmax_accuracy over the B m RoIs, one group per frame (padded proposal rows count as background RoIs).
@@ -280,6 +284,7 @@ def validate_rcnn(dataset_dir, handoff_dir, model, split="val", batch=2, workers
     Accuracy and average losses are defined as in validate_rpn (correct RoIs / RoIs; frame-weighted batch losses)."""
     from .rcnn_data import KittiRcnnBatches
     from .rcnn_train import RcnnTrainer
+    image_pyramid.check_precision_route(image_branch, image_precision)
     device = next(model.parameters()).device if isinstance(model, RcnnTrainer) else None
     data = KittiRcnnBatches(dataset_dir, handoff_dir, split, mode="val", batch=batch, workers=workers, device=device)
     trainer, was_training = None, False
@@ -294,7 +299,7 @@ def validate_rcnn(dataset_dir, handoff_dir, model, split="val", batch=2, workers
         batch_frames, seen = [], []
         for bi, bt in enumerate(data):
             b, off = len(bt.names), len(seen)
-            with image_pyramid.image_branch(image_branch):
+            with image_pyramid.image_branch(image_branch), image_pyramid.image_precision(image_precision):
                 parts, cls_logits, target = rcnn_val_forward(trainer, bt)
             losses[bi] = torch.stack([parts[k] for k in RCNN_LOSSES])
             argmax_accuracy(cls_logits, target, b, correct[off:off + b])
@@ -334,12 +339,16 @@ def build_parser():
             sp.add_argument("--seed", type=int, default=0, help="seed of the point sampling")
         sp.add_argument("--image-branch", choices=image_pyramid.IMAGE_BRANCHES, default="torch",
                         help="native: the VGG pyramid on this package's channel-last convolution kernels instead of the vendor library")
+        sp.add_argument("--image-precision", choices=image_pyramid.IMAGE_PRECISIONS, default="fp32",
+                        help="bf16: with --image-branch native, the pyramid's convolutions on the bf16 matrix cores (fp32 tensors and accumulation)")
     return ap
 
 
 def main(argv=None):
     ap = build_parser()
     args = ap.parse_args(argv)
+    if args.image_precision == "bf16" and args.image_branch != "native":
+        ap.error("--image-precision bf16 needs --image-branch native")
     if (args.model is None) == (args.checkpoint_dir is None):
         ap.error("give either MODEL.pt or --checkpoint-dir")
     if args.checkpoint_dir is not None:
@@ -351,10 +360,10 @@ def main(argv=None):
     for step, path in todo:
         if args.stage == "rpn":
             res = validate_rpn(args.dataset_dir, path, args.split, args.config, args.batch, args.seed, args.workers,
-                               image_branch=args.image_branch)
+                               image_branch=args.image_branch, image_precision=args.image_precision)
         else:
             res = validate_rcnn(args.dataset_dir, args.handoff_dir, path, args.split, args.batch, args.workers,
-                                image_branch=args.image_branch)
+                                image_branch=args.image_branch, image_precision=args.image_precision)
         for line in summary_lines(args.stage, step, res["totals"]):
             print(line)
         if args.out:

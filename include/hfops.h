@@ -571,6 +571,21 @@ int hf_conv3x3_nhwc(int b, int h, int w, int cin, int cout, const float *x, cons
 int hf_upconv3x3s2_nhwc(int b, int h, int w, int cin, int cout, const float *x, const float *wt, const float *scale,
                         const float *shift, int relu, float *y, int y_stride, int y_col, hf_stream_t stream);
 int hf_maxpool2x2_nhwc(int b, int h, int w, int c, const float *x, int x_stride, int x_col, float *y, hf_stream_t stream);
+/* The same two convolutions on the bf16 matrix cores, inference only (image_pyramid.image_precision("bf16")),
+ * csrc/conv_nhwc_bf16.hip.  Semantics of hf_conv3x3_nhwc / hf_upconv3x3s2_nhwc: tap numbering, zero padding, in_sub not applied
+ * to the padding, the parity classes with their 1, 2, 2 and 4 taps, y = z * scale + shift rounded in two steps, relu, the column
+ * slice, the limits and the HF_EINVAL cases (before any HIP call).  Two differences.  Weights: wt_bf16 (9,cout,cin) bf16, the fp32
+ * tap matrices passed through hf_f32_to_bf16.  Activation operand: bf16(fl32(x - in_sub)) inside the image and zero outside -- one
+ * fp32 subtraction, then the packed hardware conversion (nearest even), between the global load and the LDS store.  x, scale,
+ * shift and y stay fp32 in memory; products of two bf16 values are exact in fp32 and accumulate in fp32
+ * (v_mfma_f32_16x16x32_bf16) over the flattened (tap, channel) axis in a fixed order: two calls give the same bits.  Any cin, any
+ * cout in 1..256, any y_col / y_stride: cin % 4 == 0 with x 16-byte and wt_bf16 8-byte aligned loads quads, anything else takes a
+ * scalar staging path; y is stored 16 bytes at a time where cout, y_col, y_stride are multiples of 4 and y is 16-byte aligned.
+ * No workspace, no allocation, no host round trip, no environment variable: capturable. */
+int hf_conv3x3_nhwc_bf16(int b, int h, int w, int cin, int cout, const float *x, const float *in_sub, const uint16_t *wt_bf16,
+                         const float *scale, const float *shift, int relu, float *y, int y_stride, int y_col, hf_stream_t stream);
+int hf_upconv3x3s2_nhwc_bf16(int b, int h, int w, int cin, int cout, const float *x, const uint16_t *wt_bf16, const float *scale,
+                             const float *shift, int relu, float *y, int y_stride, int y_col, hf_stream_t stream);
 /* The image pyramid's training direction (image_pyramid.forward_train), csrc/conv_nhwc.hip.  Same tensors, same limits, same
  * argument checks as the three entry points above (HF_EINVAL before any HIP call); no allocation, no host round trip, no
  * floating-point atomic, capturable; two calls on the same inputs give the same bits.
